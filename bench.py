@@ -7,7 +7,15 @@ K x n median scoring of every chromosome, the budgeted chain solve (the referenc
 evaluations per chromosome, rocco/dp.py:89-164) and the run-length decode to merged intervals.
 Inputs (synthetic K x n matrices, rocco_amd/synth.py) are resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line; its `roofline` block is read off the
+timed steps' own median launches.  `--full` adds every leg beside the headline, each after the timed region: the
+two halves of a step timed on their own, the CPU baseline and the oracle parity check, the count-path scoring rows,
+the solve by kind of track, the composed driver and, at N > 1, every rank's check against the oracle.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64 / float32, at most 64 MB):
+the interval rows of every chromosome, its penalty / count / objective, and a fixed seeded sample of the scores and
+the solution.  The inputs depend on the arguments only, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 starts the N ranks itself (python -m torch.distributed.run, one process per GPU,
 before anything in this process touches the GPU) and relays rank 0's JSON line; under a launcher
@@ -46,16 +54,26 @@ def parse_args(argv=None):
     ap.add_argument("--gamma", type=float, default=1.0)
     ap.add_argument("--chroms", type=str, default="", help="comma list (default: whole genome)")
     ap.add_argument("--seed", type=int, default=20240)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-composed", action="store_true", help="skip the composed-driver leg (next_rows.composed_driver)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every leg beside the headline as well (halves of a step, CPU baseline, "
+                         "parity against the oracle, count-path rows, solve by track kind, composed driver; N > 1: every "
+                         "rank's oracle check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the legs behind it")
+    ap.add_argument("--no-composed", action="store_true",
+                    help="with --full: skip the composed-driver leg (next_rows.composed_driver)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="the timed steps and their roofline block only (for profiler runs: the kernel statistics then "
-                         "hold the steps' launches and nothing else)")
+                    help="the timed steps and their roofline block only, even with --full (what a run without --full "
+                         "does; for profiler runs: the kernel statistics then hold the steps' launches and nothing else)")
     ap.add_argument("--cpu-sample", type=str, default="chr1")
     ap.add_argument("--rehearse", action="store_true",
                     help="no device work: every rank fabricates its interval lists and runs the launch, partition, "
                          "gather, timing and reporting code only (CPU test of the N > 1 path, backend gloo)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -114,6 +132,54 @@ def _cpu_solve_worker(job):
 def _file_sha256(path):
     with open(path, "rb") as fh:
         return hashlib.sha256(fh.read()).hexdigest()
+
+
+DUMP_BYTES_MAX = 64 << 20
+DUMP_SAMPLE = 1 << 20  # loci in the scores / solution sample
+DUMP_SEED = 20240
+
+
+def _sample_positions(total, count):
+    """Sorted distinct positions of a fixed seeded sample of range(total) (all of them when count >= total)."""
+    if count >= total:
+        return np.arange(total, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, size=count, dtype=np.int64))
+
+
+def dump_outputs(out_dir, res, merged, units):
+    """What the last timed step computed, as .npy files under out_dir: per chromosome of this rank (genome order) its
+    penalty, count and objective; the interval rows (chromosome, begin locus, end locus) of every chromosome that came
+    back; the scores and the solution at a fixed seeded sample of the loci, this rank's chromosomes laid end to end.
+    The rows are sampled the same way only if they would not fit in DUMP_BYTES_MAX beside the rest."""
+    import torch
+
+    order = sorted(range(len(res)), key=lambda i: units[i])
+    out = {"chromosome_index": np.array([units[i] for i in order], dtype=np.float64)}
+    for key in ("selection_penalty", "selected_count", "penalized_objective"):
+        out[key] = np.array([res[i][key] for i in order], dtype=np.float64)
+    starts = np.concatenate([[0], np.cumsum([res[i]["n"] for i in order])]).astype(np.int64)
+    pos = _sample_positions(int(starts[-1]), DUMP_SAMPLE)
+    scores, solution = [], []
+    for k, i in enumerate(order):
+        lo, hi = np.searchsorted(pos, [starts[k], starts[k + 1]])
+        idx = torch.from_numpy(pos[lo:hi] - starts[k]).to(res[i]["scores"].device)
+        scores.append(res[i]["scores"].index_select(0, idx).double().cpu().numpy())
+        solution.append(res[i]["solution"].index_select(0, idx).float().cpu().numpy())
+    out["sample_locus"] = pos.astype(np.float64)
+    out["scores_sample"] = np.concatenate(scores)
+    out["solution_sample"] = np.concatenate(solution)
+    rows = [np.column_stack([np.full(len(r), u), np.asarray(r)]) for u, r in sorted(merged.items())]
+    intervals = np.concatenate(rows).astype(np.float64) if rows else np.zeros((0, 3))
+    room = DUMP_BYTES_MAX - sum(a.nbytes for a in out.values())
+    if intervals.nbytes > room:
+        keep = _sample_positions(len(intervals), room // (4 * intervals.itemsize))  # a row and its index
+        out["interval_row"] = keep.astype(np.float64)
+        intervals = intervals[keep]
+    out["intervals"] = intervals
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES_MAX
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def rehearse(args, rank, world):
@@ -463,13 +529,17 @@ def main():
         res, merged = one_step(median_events if rank == 0 else None)
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, merged, mine)
+    # every leg below except the roofline block runs only with --full
+    full = args.full and not args.headline_only
     # ---- every rank checks its SHORTEST chromosome against the oracle (after the timed region; N > 1 only -- at N = 1
     # the `parity` block below does the same on the longest): scores against np.median, penalty / count / solution
     # against the reference's calibration restated on the CPU, and the rows that came back through the gather against
     # the records of that solution.  The verdicts are summed into `parity_ranks_ok`: a SCALE record then proves that
     # every rank produced, and the exchange delivered, the reference's answer.
     rank_ok, rank_check = 1.0, None
-    if world > 1 and works and not args.headline_only:
+    if world > 1 and works and full:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle as po
 
@@ -538,7 +608,7 @@ def main():
                                 "zone_iters": r["info"].get("zone_iters", -1)}
 
     # ---- the two halves of a step on their own (rank 0; after the timed region) ----
-    if rank == 0 and world == 1 and roofline is not None and not args.headline_only:
+    if rank == 0 and world == 1 and roofline is not None and full:
         from rocco_amd import dp as _dp
 
         mats = [w.matrix_t for w in works]
@@ -576,7 +646,7 @@ def main():
     cpu_baseline = None
     parity = None
     m_t = None
-    if args.headline_only:
+    if not full:
         args.no_cpu_baseline = True
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -737,7 +807,7 @@ def main():
             "unit": "loci/s",
             "n_gpus": world,
             "ranks_seen": ranks_seen,
-            "parity_ranks_ok": parity_ranks_ok if world > 1 else (None if parity is None else int(
+            "parity_ranks_ok": (parity_ranks_ok if full else None) if world > 1 else (None if parity is None else int(
                 parity["scores_bit_exact"] and parity["solution_bit_exact"] and parity["bed3_identical"]
                 and parity["penalty_abs_diff"] == 0.0)),
             "rank0_parity_check": rank_check,

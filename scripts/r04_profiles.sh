@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 R="$GRAFT_REPO_ROOT"; O="$R/gpurun_out/r04"; mkdir -p "$O"
 cd "$R"
 rm -rf /tmp/prof_bench /tmp/prof_calib /tmp/prof_count /tmp/prof_normal
-timeout -k 10 900 python3 bench.py --steps 20 --warmup 5 > "$O/bench_line.json" 2> "$O/bench_line.err"
+timeout -k 10 900 python3 bench.py --steps 20 --warmup 5 --full > "$O/bench_line.json" 2> "$O/bench_line.err"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -o b -- python3 "$R/bench.py" --steps 20 --warmup 5 --headline-only > "$O/bench_line_under_rocprof.json" 2> "$O/bench_under_rocprof.err"
 cp /tmp/prof_bench/b_kernel_stats.csv "$O/kernel_stats.csv"
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_calib -- python3 "$R/scripts/chain_timeline.py" all > "$O/calib_tl.log" 2>&1

@@ -1,15 +1,14 @@
 """CPU: the oracle's restatement of the cross-fit Whittaker baseline (oracle/baseline_oracle.c) against
-the golden vectors written from the reference's own backend, and against that backend itself when its
-build (oracle/_ref/libbaseline_ref.so) is present; plus the host helpers of rocco_amd.inference."""
-import ctypes
+the golden vectors written from the reference's own backend, and against the recorded outputs of that backend on
+seeded inputs (tests/reference_record.py); plus the host helpers of rocco_amd.inference."""
 import os
 
 import numpy as np
-import pytest
+
+import reference_record
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "baseline_vectors.npz")
-dp = ctypes.POINTER(ctypes.c_double)
 
 
 def oracle_baseline(oracle, matrix, lam):
@@ -23,20 +22,19 @@ def test_oracle_reproduces_golden_baselines_bit_for_bit(oracle):
         assert got.tobytes() == gold[f"{name}_baseline"].tobytes(), name
 
 
-def test_oracle_matches_compiled_reference_backend(oracle):
-    path = os.path.join(ROOT, "oracle", "_ref", "libbaseline_ref.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref/libbaseline_ref.so not built (reference not present)")
-    ref = ctypes.CDLL(path).rocco_crossfit_whittaker_baseline_matrix_f64
-    ref.argtypes = [dp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_double, dp]
-    ref.restype = ctypes.c_int
+def reference_backend_cases():
+    """(case name, matrix, lambda): the seeded inputs on which the reference's backend was recorded."""
     rng = np.random.default_rng(5)
     for n in (1, 3, 24, 25, 27, 100, 4097, 33333):
         for lam in (0.36, 4.67e5, 1e-3, 1e9):
-            m = np.ascontiguousarray(rng.normal(0, 1, (2, n)) * rng.choice([1, 100]))
-            want = np.empty_like(m)
-            assert ref(m.ctypes.data_as(dp), 2, n, lam, want.ctypes.data_as(dp)) == 0
-            assert oracle_baseline(oracle, m, lam).tobytes() == want.tobytes(), (n, lam)
+            yield f"n={n} lambda={lam!r}", np.ascontiguousarray(rng.normal(0, 1, (2, n)) * rng.choice([1, 100])), lam
+
+
+def test_oracle_matches_compiled_reference_backend(oracle):
+    """The reference's rocco_crossfit_whittaker_baseline_matrix_f64, bit for bit."""
+    want = reference_record.recorded("baseline_backend")
+    for name, m, lam in reference_backend_cases():
+        assert reference_record.digest(oracle_baseline(oracle, m, lam)) == want[name], name
 
 
 def test_window_and_penalty_rules():

@@ -1,11 +1,11 @@
 """CPU: the oracle's restatement of the centred-WLS backend (oracle/wls_oracle.c) against the golden
-vectors written from the reference's own backend, and against that backend itself when its build
-(oracle/_ref/libwls_ref.so) is present."""
-import ctypes
+vectors written from the reference's own backend, and against the recorded outputs of that backend on seeded
+inputs (tests/reference_record.py)."""
 import os
 
 import numpy as np
-import pytest
+
+import reference_record
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "wls_vectors.npz")
@@ -28,29 +28,21 @@ def test_oracle_reproduces_golden_wls_tracks_bit_for_bit(oracle):
         assert np.array_equal(dfw, gold[f"{name}_df_window"]), name
 
 
-def test_oracle_matches_compiled_reference_backend(oracle):
-    path = os.path.join(ROOT, "oracle", "_ref", "libwls_ref.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref/libwls_ref.so not built (reference not present)")
-    dp = ctypes.POINTER(ctypes.c_double)
-    ref = ctypes.CDLL(path).rocco_score_centered_wls_f64
-    ref.argtypes = [dp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                    ctypes.c_int, ctypes.c_int, ctypes.c_double, dp, dp, dp, dp, dp, dp, dp,
-                    ctypes.POINTER(ctypes.c_int)]
-    ref.restype = ctypes.c_int
+def reference_backend_cases():
+    """(case name, matrix): the seeded inputs on which the reference's backend was recorded."""
     rng = np.random.default_rng(11)
     for n in (1, 4, 5, 33, 1000, 50001):
         for K in (1, 4):
-            m = np.ascontiguousarray(np.round(rng.normal(0, 1, (K, n)), 2))  # rounded: plenty of ties
-            tracks = [np.empty(n) for _ in range(6)]
-            df, win = ctypes.c_double(), ctypes.c_int()
-            assert ref(m.ctypes.data_as(dp), K, n, 1.0, 5.0, 0.0, 0, 31, 0.01,
-                       *[t.ctypes.data_as(dp) for t in tracks], ctypes.byref(df), ctypes.byref(win)) == 0
-            got = oracle.score_centered_wls(m)
-            want = (tracks[5], tracks[0], tracks[1], tracks[2], tracks[3], tracks[4])
-            for g, w in zip(got[:6], want):
-                assert g.tobytes() == w.tobytes(), (n, K)
-            assert got[6] == df.value and got[7] == win.value
+            yield f"n={n} K={K}", np.ascontiguousarray(np.round(rng.normal(0, 1, (K, n)), 2))  # rounded: plenty of ties
+
+
+def test_oracle_matches_compiled_reference_backend(oracle):
+    """Every output of the reference's rocco_score_centered_wls_f64 (tracks in its order: mean, raw, prior, moderated,
+    se, scores; then df and window), bit for bit."""
+    want = reference_record.recorded("wls_backend")
+    for name, m in reference_backend_cases():
+        got = oracle.score_centered_wls(m)
+        assert reference_record.digest(*got[1:6], got[0], float(got[6]), int(got[7])) == want[name], name
 
 
 def test_oracle_score_loci_wls_known_answers(oracle):
