@@ -86,6 +86,8 @@ def _solve_group(chroms: Sequence[ChromWork], scores: list, score_stats=None, un
     """Calibrate and decode the given chromosomes on the calling thread's current stream / solver; count-path
     chromosomes (scores[i] is None) are scored here first, so that the groups' chain kernels -- one latency-bound
     wavefront per row and parity -- run side by side as well."""
+    import torch
+
     if any(s is None for s in scores):
         score_stats = None
     scores = [s if s is not None else _score_wls(c) for c, s in zip(chroms, scores)]
@@ -95,24 +97,31 @@ def _solve_group(chroms: Sequence[ChromWork], scores: list, score_stats=None, un
     # every chromosome's runs as ONE table of (unit, begin, end) rows: three launches, one synchronisation, and the
     # table reaches pinned host memory in the same breath (a run has at least one selected locus and on real tracks
     # about twenty: a fifth of the selected loci, never less than 4096 rows, travels before the synchronisation)
-    selected = sum(int(count) for (_p, _s, _v, count, _i) in solved)
-    if len(chroms) <= 48:
-        table_t, offsets, host_rows = _rocco.decode_runs_table_device(
-            [sol_t for (_p, sol_t, _v, _c, _i) in solved], units=units, capacity_rows=max(1024, selected // 2 + 64),
+    # (a table holds at most 48 solutions: more chromosomes are decoded in slices of 48 and the slices joined; a slice's
+    # host rows are the solver's pinned buffer, which the next slice's decode overwrites, so they are copied first)
+    units = list(range(len(chroms))) if units is None else [int(u) for u in units]
+    tables, hosts, offsets = [], [], [0]
+    for at in range(0, len(chroms), 48):
+        part = solved[at:at + 48]
+        selected = sum(int(count) for (_p, _s, _v, count, _i) in part)
+        part_t, part_off, part_host = _rocco.decode_runs_table_device(
+            [sol_t for (_p, sol_t, _v, _c, _i) in part], units=units[at:at + 48], capacity_rows=max(1024, selected // 2 + 64),
             eager_rows=max(4096, selected // 5))
-        runs = [(table_t[offsets[i]:offsets[i + 1], 1], table_t[offsets[i]:offsets[i + 1], 2]) for i in range(len(chroms))]
-    else:
-        table_t, offsets, host_rows = None, None, None
-        runs = _rocco.decode_runs_batch_device([sol_t for (_p, sol_t, _v, _c, _i) in solved],
-                                               capacities=[max(1024, c.n // 64) for c in chroms])
+        tables.append(part_t)
+        hosts.append(part_host if len(chroms) <= 48 else part_host.copy())
+        offsets += [offsets[-1] + o for o in part_off[1:]]
+    table_t = tables[0] if len(tables) == 1 else torch.cat(tables, dim=0)
+    host_rows = hosts[0] if len(hosts) == 1 else np.concatenate(hosts, axis=0)
+    runs = [(table_t[offsets[i]:offsets[i + 1], 1], table_t[offsets[i]:offsets[i + 1], 2]) for i in range(len(chroms))]
     for i, (c, s_t, (penalty, sol_t, value, count, info), (begin_t, end_t)) in enumerate(zip(chroms, scores, solved, runs)):
         out.append({
             "name": c.name, "n": c.n, "selected_count": count, "selection_penalty": penalty,
             "penalized_objective": value, "path": info["path"], "info": info,
             "begin": begin_t, "end": end_t, "solution": sol_t, "step": c.step, "start": c.start,
             "effect_mean": getattr(c, "_effect_mean", None), "scores": s_t,
-            # the group's whole table (device; host view valid until this device's next decode) and this chromosome's rows
-            "rows": table_t, "rows_host": host_rows, "row_range": None if offsets is None else (offsets[i], offsets[i + 1]),
+            # the group's whole table (device; on the host a view valid until this device's next decode, a copy when the
+            # table was joined from slices) and this chromosome's rows
+            "rows": table_t, "rows_host": host_rows, "row_range": (offsets[i], offsets[i + 1]),
         })
     return out
 
@@ -272,11 +281,7 @@ def interval_rows(results: Sequence[dict], host: bool = True):
     tables, seen = [], set()
     for r in results:
         t = r["rows_host"] if host else r["rows"]
-        if t is None:  # more chromosomes than one table holds: rows from the per-chromosome tensors
-            unit = torch.full_like(r["begin"], -1)
-            rows = torch.stack([unit, r["begin"], r["end"]], dim=1)
-            tables.append(rows.cpu().numpy() if host else rows)
-        elif id(t) not in seen:
+        if id(t) not in seen:
             seen.add(id(t))
             tables.append(t)
     if len(tables) == 1:
