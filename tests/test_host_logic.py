@@ -217,3 +217,71 @@ def test_host_logic_under_address_and_undefined_behaviour_sanitizers():
     assert run.returncode == 0, run.stdout + run.stderr
     assert "160 cases, 0 mismatches" in run.stdout
     assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr
+
+
+# ---- the envelope of the fast path's gates (inputs: tests/envelope_cases.py; the same rungs run on the GPU in
+# tests/test_gpu_calibration_envelope.py, so a failure there can be placed: search.cpp here, the device side there) ----
+
+def _calibrations_agree(oracle, s, gamma, target, where):
+    import envelope_cases as ec
+
+    ref = oracle.calibrate_selection_penalty(s, oracle.build_switch_costs(s, gamma), target, return_evaluations=True)
+    pen, sol, val, cnt, info = hl.calibrate(s, gamma, target)
+    assert pen == ref[0] and cnt == ref[3], (where, pen, ref[0], cnt, ref[3], info)
+    assert np.array_equal(sol, ref[1]), (where, info)
+    assert info["evaluations"] == ref[4], (where, info["evaluations"], ref[4], info)
+    assert ec.values_agree(val, ref[2], ref[3], s, ref[0], info["path"] == 2, sequential=True), (where, val, ref[2], info)
+    if s.size > 1 and not ec.inside_gates(s, gamma):
+        assert info["path"] == 2, (where, info)
+    return ref, info
+
+
+@pytest.mark.parametrize("n", [33, 8191, 8193, 70000])
+def test_envelope_gate_ladder(oracle, n):
+    """One gate at a time, from just inside to far outside (switch cost, magnitude, spread), on the `peaks` and
+    `integers` tracks at budgets 0.02 and 0.5: penalty, count, solution AND the number of chain evaluations are the
+    reference's.  On the offsets +-1e20 (short tracks) and 1e300 the reference widens its bracket once: 63 evaluations."""
+    import envelope_cases as ec
+
+    widened = 0
+    for rung in ec.LADDER:
+        for kind in ("peaks", "integers"):
+            s, gamma = ec.rung_problem(rung, kind, n)
+            for budget in ec.ladder_budgets(rung):
+                ref, _info = _calibrations_agree(oracle, s, gamma, int(np.floor(n * budget)), (rung, kind, n, budget))
+                if ec.widened(rung, n):
+                    assert ref[4] == 63, (rung, kind, n, budget, ref[4])
+                    widened += 1
+    assert widened == (3 if n <= 8193 else 1) * 2 * 2
+
+
+@pytest.mark.parametrize("kind", ["peaks", "integers", "normal"])
+@pytest.mark.parametrize("n", [2, 3, 8193, 70000])
+def test_envelope_targets(oracle, kind, n):
+    """Targets from below zero to past the end; target >= n is one evaluation at penalty 0 (rocco/dp.py:102-108)."""
+    import envelope_cases as ec
+
+    s = ec.track(kind, n)
+    for target in ec.targets_for(n):
+        ref, info = _calibrations_agree(oracle, s, 1.0, target, (kind, n, target))
+        if target >= n:
+            assert ref[4] == 1 and ref[0] == 0.0 and info["evaluations"] == 1
+
+
+@pytest.mark.parametrize("n", [33, 8193, 70000])
+def test_envelope_fixed_penalties(oracle, n):
+    """solve_fixed on the magnitude rungs at penalties outside, inside and absurdly far from the scores, exactly on a
+    score, and on / next to the calibrated penalty."""
+    import envelope_cases as ec
+
+    for rung in ec.MAGNITUDE_LADDER:
+        for kind in ("peaks", "integers"):
+            s, gamma = ec.rung_problem(rung, kind, n)
+            costs = oracle.build_switch_costs(s, gamma)
+            calibrated = oracle.calibrate_selection_penalty(s, costs, int(np.floor(n * 0.02)))[0]
+            for lam in ec.fixed_penalties(s, calibrated):
+                sol, val, cnt, info = hl.solve_fixed(s, gamma, lam)
+                o_sol, o_val, o_cnt = oracle.solve_penalized_chain(s, costs, lam)
+                assert np.array_equal(sol, o_sol) and cnt == o_cnt, (rung, kind, n, lam, info)
+                assert ec.values_agree(val, o_val, o_cnt, s, lam, info["path"] == 2, sequential=True), (
+                    rung, kind, n, lam, val, o_val, info)

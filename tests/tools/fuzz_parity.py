@@ -23,15 +23,15 @@ while time.time() < t_end:
     elif kind == "const": s = np.full(n, float(rng.normal()))
     elif kind == "sparse": s = np.where(rng.random(n) < 0.02, rng.gamma(6.0, 1.0, n), 0.0)
     elif kind == "tiny": s = rng.normal(0, 1e-9, n)
-    elif kind == "offset": s = float(rng.choice([1e3, 3e4, -1e6, 1e9])) + rng.gamma(1.0, 1.0, n)
+    elif kind == "offset": s = float(rng.choice([1e3, 3e4, -1e6, 1e9, 9e11, 1e15])) + rng.gamma(1.0, 1.0, n)
     else: s = rng.normal(0, 1e6, n)
-    gamma = float(rng.choice([0.0, 0.5, 1.0, 3.0, 10.0, float(abs(rng.normal()) * 2)]))
+    gamma = float(rng.choice([0.0, 1e-3, 0.5, 1.0, 3.0, 10.0, 1e6, float(abs(rng.normal()) * 2)]))
     use_vec = n > 1 and rng.random() < 0.25
     costs = rng.gamma(1.0, gamma + 0.1, n - 1) if use_vec else gamma
     o_costs = costs if use_vec else po.build_switch_costs(s, gamma)
     try:
         if rng.random() < 0.5:
-            budget = float(rng.choice([0.005, 0.02, 0.05, 0.1, 0.3]))
+            budget = float(rng.choice([0.005, 0.02, 0.05, 0.1, 0.3, 0.5, 0.9]))
             target = int(np.floor(n * budget))
             g = dp.calibrate_selection_penalty(s, costs, target)
             o = po.calibrate_selection_penalty(s, o_costs, target)
