@@ -95,8 +95,56 @@ int rocco_hip_score_trimmed_mean(rocco_hip_solver *solver, const void *matrix_de
 
 /* np.power(scores, power) (rocco/rocco.py:255, 304): exact for power 2 (NumPy squares); any other exponent through the
  * device's pow -- NumPy's own pow differs between its SVML and libm builds in the last place, so no algorithm matches
- * it on every host (power 1, the driver's value, never comes here). */
+ * it on every host (power 1, the driver's value, never comes here).  As in NumPy a NaN stays NaN, a negative finite value
+ * under a fractional exponent gives NaN, and power 0 gives 1 for every value. */
 int rocco_hip_power_f64(rocco_hip_solver *solver, const double *x_dev, double power, double *out_dev, size_t n, void *stream);
+
+/* ---- dispersion ----------------------------------------------------------------------------
+ * Replace rocco/rocco.py:307-355 `score_dispersion_chrom`, one entry per method.  Matrix conventions of
+ * rocco_hip_score_median (row-major [K][row_stride], dtype 0 = float64 / 1 = float32 widened to float64, one result per
+ * column); 2 <= K -- K == 1 (rocco.py:318-319, zeros) is answered by the caller.  A NaN anywhere in a column gives NaN.
+ * Up to K = 100 each is ONE launch that reads the matrix once with the column in registers (only the trimmed std at
+ * 80 < K < 100 reads it twice, see below); above that, rank counting and plain loops with no speed claim.  Every result is bit for bit that of
+ * NumPy 2.2 / SciPy 1.15 on the same column.
+ *
+ * method="mad" (rocco.py:324-325, stats.median_abs_deviation(m, axis=0)): np.median of |column - np.median(column)|;
+ * no sum is formed (the mean of the two middle values for even K). */
+int rocco_hip_score_mad(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride,
+                        double *scores_dev, void *stream);
+
+/* method="iqr" (rocco.py:326-327, stats.iqr(m, rng=rng, axis=0)): the upper percentile minus the lower one, each by
+ * np.percentile's linear rule.  The caller turns a percentile q into (index, g) with NumPy's own arithmetic:
+ * vi = (K - 1) * np.true_divide(q, 100), index = floor(vi), g = vi - index (0 <= g < 1); with a = sorted[index],
+ * b = sorted[min(index + 1, K - 1)] and d = b - a the value is a + d g for g < 0.5 and b - d (1 - g) otherwise.
+ * (index_lo, g_lo) belongs to the smaller percentile (SciPy sorts `rng`).  No sum is formed. */
+int rocco_hip_score_percentile_range(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n,
+                                     size_t row_stride, int index_lo, double g_lo, int index_hi, double g_hi,
+                                     double *scores_dev, void *stream);
+
+/* method="std" (rocco.py:328-329, np.std(m, axis=0)): sum / K, the squared deviations summed and divided by K, sqrt.
+ * Summation order, both sums alike: pairwise_order == 0 adds the rows one after the other, as NumPy reduces axis 0 of a
+ * matrix with n > 1; pairwise_order != 0 adds the K entries of each column in NumPy's pairwise order (see
+ * rocco_hip_score_trimmed_mean), as NumPy reduces the single column of a K x 1 matrix -- K <= 1024 then. */
+int rocco_hip_score_std(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride,
+                        int pairwise_order, double *scores_dev, void *stream);
+
+/* method="tstd" (rocco.py:330-348).  DIVERGENCE: the reference hands stats.tstd the two limits as n-vectors, which SciPy
+ * cannot broadcast against the K x n matrix (ValueError for every K != n; for K == n limits along the wrong axis).
+ * Built here is what its own tmean branch (rocco.py:273-297) does per column: stats.tstd(column, limits=(q_lo, q_hi),
+ * inclusive=(True, True)) with q_lo / q_hi the order statistics of ranks rank_lo <= rank_hi (np.quantile(...,
+ * method="nearest") at tprop and 1 - tprop).  Summation order: values outside the limits count as 0.0; the mean and the
+ * squared deviations are each summed in NumPy's pairwise order over the K entries in row order and divided by the
+ * number kept, and the variance is multiplied by kept / (kept - 1) (NaN when at most one value is kept).  Kept
+ * infinities as in SciPy, which leaves their NaN deviations out: +inf with infinities at one end, NaN at both.
+ * take_root != 0: the result is the correctly rounded sqrt of that variance.  take_root == 0: the variance itself
+ * (stats.tvar), for a caller that takes the root as SciPy does -- `var ** 0.5` on a NumPy scalar is the host libm's pow,
+ * which is not correctly rounded (glibc 2.35: 8 of 10 000 values differ from sqrt in the last place) and not the same
+ * function on every host, so no device algorithm reproduces it everywhere.
+ * The sort destroys the row order the sums need: for K <= 80 and K == 100 an unpermuted copy of the column stays in
+ * registers beside the sorted one (one read of the matrix); only for 80 < K < 100 the column is read a second time.
+ * K <= 1024 (the written-out depth of the pairwise order); ROCCO_HIP_EINVAL above. */
+int rocco_hip_score_trimmed_std(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n,
+                                size_t row_stride, int rank_lo, int rank_hi, int take_root, double *scores_dev, void *stream);
 
 /* ---- chain solve at a fixed selection penalty ----------------------------------------------
  * Replaces rocco/_chain_dp.c:9-213 `solve_penalized_chain` (Python wrapper rocco/dp.py:49-86).

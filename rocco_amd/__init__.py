@@ -27,6 +27,7 @@ from .rocco import (  # noqa: F401
     chrom_solution_to_bed,
     combine_chrom_results,
     score_central_tendency_chrom,
+    score_dispersion_chrom,
     solve_cached_chromosomes,
 )
 

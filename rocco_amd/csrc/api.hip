@@ -281,6 +281,58 @@ int rocco_hip_score_mean(rocco_hip_solver *solver, const void *matrix_dev, int d
     return launch_column_mean(matrix_dev, dtype, K, n, row_stride, scores_dev, (hipStream_t)stream);
 }
 
+// the checks the four dispersion entries share (K == 1 is answered by the caller without a launch: rocco/rocco.py:318-319)
+static bool dispersion_args_ok(const rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride,
+                               const double *scores_dev)
+{
+    return solver != nullptr && (n == 0 || (matrix_dev != nullptr && scores_dev != nullptr)) && K >= 2 && K <= 0x7FFFFFFF &&
+           row_stride >= n && (dtype == 0 || dtype == 1);
+}
+
+int rocco_hip_score_mad(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride,
+                        double *scores_dev, void *stream)
+{
+    if (!dispersion_args_ok(solver, matrix_dev, dtype, K, n, row_stride, scores_dev)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    return launch_mad(matrix_dev, dtype, K, n, row_stride, scores_dev, (hipStream_t)stream);
+}
+
+int rocco_hip_score_percentile_range(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n,
+                                     size_t row_stride, int index_lo, double g_lo, int index_hi, double g_hi,
+                                     double *scores_dev, void *stream)
+{
+    if (!dispersion_args_ok(solver, matrix_dev, dtype, K, n, row_stride, scores_dev) || index_lo < 0 || index_hi < 0 ||
+        (size_t)index_lo >= K || (size_t)index_hi >= K || !(g_lo >= 0.0 && g_lo < 1.0) || !(g_hi >= 0.0 && g_hi < 1.0)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    return launch_percentile_range(matrix_dev, dtype, K, n, row_stride, index_lo, g_lo, index_hi, g_hi, scores_dev,
+                                   (hipStream_t)stream);
+}
+
+int rocco_hip_score_std(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride,
+                        int pairwise_order, double *scores_dev, void *stream)
+{
+    if (!dispersion_args_ok(solver, matrix_dev, dtype, K, n, row_stride, scores_dev)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    return launch_std(matrix_dev, dtype, K, n, row_stride, pairwise_order, scores_dev, (hipStream_t)stream);
+}
+
+int rocco_hip_score_trimmed_std(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n,
+                                size_t row_stride, int rank_lo, int rank_hi, int take_root, double *scores_dev, void *stream)
+{
+    if (!dispersion_args_ok(solver, matrix_dev, dtype, K, n, row_stride, scores_dev) || rank_lo < 0 || rank_hi < rank_lo ||
+        (size_t)rank_hi >= K) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    return launch_trimmed_std(matrix_dev, dtype, K, n, row_stride, rank_lo, rank_hi, take_root, scores_dev, (hipStream_t)stream);
+}
+
 int rocco_hip_solve_penalized_chain_f64(rocco_hip_solver *solver, const double *scores_dev,
                                         const double *switch_costs_dev, double gamma, size_t n,
                                         double selection_penalty, uint8_t *solution_dev,

@@ -76,6 +76,16 @@ int launch_trimmed_mean(const void *matrix_dev, int dtype, size_t K, size_t n, s
                         double *scores_dev, hipStream_t stream);
 int launch_power(const double *x_dev, double p, double *out_dev, size_t n, hipStream_t stream);
 
+// ---- dispersion.hip -------------------------------------------------------------------------
+// column-wise dispersion of a [K][row_stride] matrix, 2 <= K (matrix conventions of launch_median)
+int launch_mad(const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, double *scores_dev, hipStream_t stream);
+int launch_percentile_range(const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, int index_lo, double g_lo,
+                            int index_hi, double g_hi, double *scores_dev, hipStream_t stream);
+int launch_std(const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, int pairwise_order, double *scores_dev,
+               hipStream_t stream);
+int launch_trimmed_std(const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, int rank_lo, int rank_hi,
+                       int take_root, double *scores_dev, hipStream_t stream);
+
 // ---- decode.hip -----------------------------------------------------------------------------
 // scratch: at least decode_scratch_bytes(n) bytes
 size_t decode_scratch_bytes(size_t n);

@@ -11,6 +11,7 @@
 // K), which leaves the middle order statistics unchanged.  HBM-bound: 8K (or 4K) bytes read and
 // 8 bytes written per locus.
 #include "kernels.h"
+#include "select_network.h"
 
 #include <limits>
 
@@ -23,51 +24,6 @@
 namespace rocco {
 
 namespace {
-
-template <int N>
-__device__ __forceinline__ void select_middle(double (&v)[N])
-{
-    // Batcher's merge exchange for arbitrary N; every index below is a compile-time constant
-    // once the loops are fully unrolled.
-#pragma unroll
-    for (int p = 1; p < N; p <<= 1) {
-#pragma unroll
-        for (int k = p; k >= 1; k >>= 1) {
-#pragma unroll
-            for (int j = k % p; j <= N - 1 - k; j += 2 * k) {
-#pragma unroll
-                for (int i = 0; i <= ((k - 1 < N - j - k - 1) ? (k - 1) : (N - j - k - 1)); ++i) {
-                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
-                        const double a = v[i + j];
-                        const double b = v[i + j + k];
-                        v[i + j] = fmin(a, b);
-                        v[i + j + k] = fmax(a, b);
-                    }
-                }
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ bool is_nan_bits(double x)
-{
-    // this file is compiled with -fno-honor-nans (so that the network is bare v_min_f64 / v_max_f64);
-    // NaN tests therefore go through the bit pattern
-    return (__double_as_longlong(x) & 0x7FFFFFFFFFFFFFFFLL) > 0x7FF0000000000000LL;
-}
-
-// Workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  Rows are not aligned to
-// cache lines (n is arbitrary), so neighbouring workgroups share the line that straddles their
-// boundary in every row: give each XCD one contiguous range of loci so that the shared lines meet
-// in one L2 instead of being fetched from memory twice.
-__device__ __forceinline__ unsigned xcd_contiguous_block()
-{
-    const unsigned nblk = gridDim.x;
-    const unsigned per = nblk / 8U, rem = nblk % 8U;
-    const unsigned xcd = blockIdx.x % 8U, slot = blockIdx.x / 8U;
-    // XCD x owns per + (x < rem) workgroups, laid out one range after the other
-    return xcd * per + (xcd < rem ? xcd : rem) + slot;
-}
 
 // EXACT: K == KP is known at compile time (no padding, unpredicated loads).
 // `col0` is the workgroup's first column and `lane` the thread's distance from it: every row is read at (scalar row
@@ -654,7 +610,12 @@ __global__ __launch_bounds__(256) void power_kernel(const double *__restrict__ x
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         const double v = x[i];
-        out[i] = (p == 2.0) ? (v * v) : pow(v, p);
+        // this file is compiled with -fno-honor-nans, under which pow answers 0 for a NaN: the cases whose answer is NaN
+        // -- a NaN score, a negative finite score under a fractional exponent -- are answered from the bit pattern
+        const bool finite = (__double_as_longlong(v) & 0x7FF0000000000000LL) != 0x7FF0000000000000LL;
+        const bool nan_result = is_nan_bits(v) || (finite && v < 0.0 && p != floor(p));
+        const double r = (p == 2.0) ? (v * v) : pow(nan_result ? 1.0 : v, p);
+        out[i] = (p == 0.0) ? 1.0 : (nan_result ? __longlong_as_double(0x7FF8000000000000LL) : r);  // np.power(nan, 0) is 1
     }
 }
 
