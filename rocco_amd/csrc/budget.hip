@@ -21,6 +21,7 @@
 #include "model_chain.h"
 #include "chain_fast.h"
 #include "lean.h"
+#include "lean_tasks.h"
 #include "search.h"
 
 namespace rocco {
@@ -119,8 +120,6 @@ int grid_exponent(double cmax, double lo, double hi)
     return (int)std::ceil(std::log2(8.0 * r)) - 52;
 }
 
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 std::atomic<long long> g_model_chain_counters[6];
 
 class HipEvaluator : public Evaluator {
@@ -140,6 +139,41 @@ public:
         const char *value = std::getenv(name);
         env_cache_.emplace_back(name, value);
         return value;
+    }
+    bool env_set(const char *name) const { return env(name) != nullptr; }
+    // typed readers: `unset` when the variable is not set
+    int env_int(const char *name, int unset) const
+    {
+        const char *e = env(name);
+        return e != nullptr ? std::atoi(e) : unset;
+    }
+    long long env_ll(const char *name, long long unset) const
+    {
+        const char *e = env(name);
+        return e != nullptr ? std::atoll(e) : unset;
+    }
+    bool env_flag(const char *name, bool unset) const { return env_int(name, unset ? 1 : 0) != 0; }
+    double env_double(const char *name, double unset) const
+    {
+        const char *e = env(name);
+        return e != nullptr ? std::atof(e) : unset;
+    }
+    // comma list of positive numbers, e.g. "2.2" or "2.2,1.0"; false: not set, `out` untouched
+    bool env_list(const char *name, std::vector<double> &out) const
+    {
+        const char *e = env(name);
+        if (e == nullptr) {
+            return false;
+        }
+        out.clear();
+        for (const char *q = e; *q != '\0';) {
+            char *end = nullptr;
+            const double v = std::strtod(q, &end);
+            if (end == q) break;
+            if (v > 0.0) out.push_back(v);
+            q = (*end == ',') ? end + 1 : end;
+        }
+        return true;
     }
 
     std::vector<DevProblem> probs;
@@ -344,8 +378,7 @@ public:
 
     bool lean_map_takes(size_t problem) const
     {
-        const char *flag = env("ROCCO_HIP_LEAN_MAP");
-        const bool enabled = (flag != nullptr) ? std::atoi(flag) != 0 : true;
+        const bool enabled = env_flag("ROCCO_HIP_LEAN_MAP", true);
         const DevProblem &p = probs[problem];
         return enabled && solver_->lean != 0 && p.costs == nullptr && p.emap == nullptr && p.n >= 2 &&
                (force_lean_map_ || (lean_ready_ && p.compacted && p.lean_orig != nullptr));
@@ -377,45 +410,27 @@ public:
             const MapRequest &r = *reqs[i];
             const DevProblem &p = probs[r.problem];
             LeanTask &t = tasks[i];
-            t.s = p.scores;
-            t.m = (long long)p.n;
-            t.c_raw = p.gamma;
-            t.magic = std::ldexp(1.5, 52 + p.qexp);
-            t.big = std::ldexp(1.0, 50 + p.qexp);
-            t.n_tiles = (int)((p.n + kLeanTile - 1) / kLeanTile);
-            t.n_points = 1;
-            t.n_groups = 1;
-            t.unit_begin = units;
-            t.point_begin = (int)i;
-            t.rec_begin = units;
-            t.bits_begin = 0;
-            t.off_begin = 0;
-            t.result_begin = (int)i;
-            t.tile_stride = 1;
-            t.independent = 0;
-            t.store = 0;
-            t.emap = nullptr;
-            t.wcap = nullptr;
-            t.clean_chunks = nullptr;
-            t.cmax = t.sabs = 0.0;
-            t.qexp = p.qexp;
-            t.batch = 1;
+            t = lean_task(p.scores, (long long)p.n, p.gamma, p.qexp, LeanTaskKind::map(), 1);
+            t.unit_begin = t.rec_begin = units;
+            t.point_begin = t.result_begin = (int)i;
             points[i] = r.lambda_ref;
             units += t.n_tiles;
         }
-        const size_t b_tasks = align_up(T * sizeof(LeanTask), 256);
-        const size_t b_points = align_up(T * sizeof(double), 256);
-        const size_t b_codes = align_up(T * sizeof(LeanMapCodeTask), 256);
-        const size_t up_bytes = b_tasks + b_points + b_codes;
-        const size_t b_results = align_up(T * sizeof(LeanResult), 256);
-        const size_t b_gc = align_up((size_t)units * kLeanThreads * sizeof(double), 256);
-        const size_t b_gb = align_up((size_t)units * sizeof(double), 256);
-        if ((rc = solver_->dev_map.reserve(up_bytes + b_results + b_gc + b_gb + 256)) != ROCCO_HIP_OK) return rc;
-        if ((rc = solver_->host_map_stage.reserve(up_bytes + 256)) != ROCCO_HIP_OK) return rc;
+        // device: [tasks][points][code tasks] (uploaded) [results][gains per chunk][gains per tile]
+        Layout lay;
+        const size_t o_tasks = lay.at(T * sizeof(LeanTask));
+        const size_t o_points = lay.at(T * sizeof(double));
+        const size_t o_codes = lay.at(T * sizeof(LeanMapCodeTask));
+        lay.end_upload();
+        const size_t o_results = lay.at(T * sizeof(LeanResult));
+        const size_t o_gc = lay.at((size_t)units * kLeanThreads * sizeof(double));
+        const size_t o_gb = lay.at((size_t)units * sizeof(double));
+        if ((rc = solver_->dev_map.reserve(lay.bytes() + 256)) != ROCCO_HIP_OK) return rc;
+        if ((rc = solver_->host_map_stage.reserve(lay.uploaded + 256)) != ROCCO_HIP_OK) return rc;
         char *dv = (char *)solver_->dev_map.ptr;
         char *h = (char *)solver_->host_map_stage.ptr;
-        double *gain_chunk = (double *)(dv + up_bytes + b_results);
-        double *gain_block = (double *)(dv + up_bytes + b_results + b_gc);
+        double *gain_chunk = (double *)(dv + o_gc);
+        double *gain_block = (double *)(dv + o_gb);
         for (size_t i = 0; i < T; ++i) {
             LeanMapCodeTask &c = codes[i];
             c.gain_chunk = gain_chunk + (size_t)tasks[i].rec_begin * kLeanThreads;
@@ -426,43 +441,18 @@ public:
             c.n_tiles = tasks[i].n_tiles;
             c.block_begin = tasks[i].unit_begin;
         }
-        std::memcpy(h, tasks.data(), T * sizeof(LeanTask));
-        std::memcpy(h + b_tasks, points.data(), T * sizeof(double));
-        std::memcpy(h + b_tasks + b_points, codes.data(), T * sizeof(LeanMapCodeTask));
-        unsigned *error_host = (unsigned *)(h + up_bytes);
+        std::memcpy(h + o_tasks, tasks.data(), T * sizeof(LeanTask));
+        std::memcpy(h + o_points, points.data(), T * sizeof(double));
+        std::memcpy(h + o_codes, codes.data(), T * sizeof(LeanMapCodeTask));
+        unsigned *error_host = (unsigned *)(h + lay.uploaded);
         *error_host = 0u;
         lean_map_error_ = error_host;
-        ROCCO_HIP_TRY(hipMemcpyAsync(dv, h, up_bytes, hipMemcpyHostToDevice, stream_));
-        // round scratch as the lean rounds keep it (lean_enqueue)
-        const size_t b_look = align_up(256 + (size_t)units * 4 * sizeof(unsigned long long), 256);
-        {
-            const void *old_ptr = solver_->dev_lean_look.ptr;
-            const size_t old_bytes = solver_->dev_lean_look.bytes;
-            if ((rc = solver_->dev_lean_look.reserve(b_look)) != ROCCO_HIP_OK) return rc;
-            if (solver_->lean_look_dirty != 0 || solver_->dev_lean_look.ptr != old_ptr || solver_->dev_lean_look.bytes != old_bytes) {
-                ROCCO_HIP_TRY(hipMemsetAsync(solver_->dev_lean_look.ptr, 0xFF, solver_->dev_lean_look.bytes, stream_));
-                ROCCO_HIP_TRY(hipMemsetAsync((char *)solver_->dev_lean_look.ptr + 128, 0, 4, stream_));
-                solver_->lean_look_dirty = 0;
-            }
-        }
-        if ((rc = solver_->dev_lean_round.reserve(align_up((size_t)units * sizeof(LeanTileRec), 256) + 256)) != ROCCO_HIP_OK) return rc;
-        char *look = (char *)solver_->dev_lean_look.ptr;
-        LeanLaunch L;
-        L.tasks = (const LeanTask *)dv;
+        ROCCO_HIP_TRY(hipMemcpyAsync(dv, h, lay.uploaded, hipMemcpyHostToDevice, stream_));
+        if ((rc = reserve_round_scratch(units, false)) != ROCCO_HIP_OK) return rc;
+        LeanLaunch L = round_launch((const LeanTask *)(dv + o_tasks), (const double *)(dv + o_points), (LeanResult *)(dv + o_results));
         L.n_tasks = (int)T;
         L.n_units = units;
-        L.points = (const double *)(dv + b_tasks);
-        L.ticket = (unsigned *)look;
-        L.look = (unsigned long long *)(look + 256);
-        L.recs = (LeanTileRec *)solver_->dev_lean_round.ptr;
-        L.bits = (unsigned *)solver_->dev_lean_pool.ptr;
-        L.tile_off = (unsigned *)solver_->dev_lean_pool.ptr;
-        L.results = (LeanResult *)(dv + up_bytes);
-        L.error = (unsigned *)(look + 128);
         L.error_out = error_host;
-        L.self_reset = 1;
-        L.pad = 0;
-        L.ctl = nullptr;
         LeanMapOut out;
         out.gain_chunk = gain_chunk;
         out.gain_block = gain_block;
@@ -470,9 +460,9 @@ public:
         if ((rc = launch_lean_map(L, out, stream_)) != ROCCO_HIP_OK) return rc;
         if ((rc = launch_lean_finish(L, (int)T, stream_)) != ROCCO_HIP_OK) return rc;
         solver_->lean_look_dirty = 0;
-        if ((rc = launch_lean_mapcode((const LeanMapCodeTask *)(dv + b_tasks + b_points), (int)T, units, stream_)) != ROCCO_HIP_OK) return rc;
+        if ((rc = launch_lean_mapcode((const LeanMapCodeTask *)(dv + o_codes), (int)T, units, stream_)) != ROCCO_HIP_OK) return rc;
         lean_maps_built += (long long)T;
-        if (env("ROCCO_HIP_DEBUG") != nullptr) {
+        if (env_set("ROCCO_HIP_DEBUG")) {
             std::fprintf(stderr, "[lean map] %zu problems, %d tiles\n", T, units);
         }
         return ROCCO_HIP_OK;
@@ -942,8 +932,7 @@ public:
     // rounding-model probes of a compacted problem with a map in place go through lean_model_kernel
     bool model_eligible(size_t problem) const
     {
-        const char *flag = env("ROCCO_HIP_LEAN_MODEL");  // (read per call: tests switch it within one process)
-        const bool enabled = flag == nullptr || std::atoi(flag) != 0;
+        const bool enabled = env_flag("ROCCO_HIP_LEAN_MODEL", true);  // (read per call: tests switch it within one process)
         const DevProblem &p = probs[problem];
         return enabled && !force_full_ && solver_->lean != 0 && lean_ready_ && ((p.compacted && p.lean_orig != nullptr) || model_any_) &&
                p.costs == nullptr && p.emap != nullptr && p.n >= 2;
@@ -960,15 +949,15 @@ public:
         if (!model_eligible(problem)) {
             return 0;
         }
-        if (const char *e = env("ROCCO_HIP_MODEL_DEPTH")) {
-            return std::max(1, std::min(6, std::atoi(e)));
+        if (const int fixed = model_depth_fixed()) {
+            return fixed;
         }
         // (the problems still asking: those of the last rounding-model round; before the first one, every compacted problem)
         long long tiles = model_tiles_last_round_;
         if (tiles <= 0) {
             for (size_t b = 0; b < probs.size(); ++b) {
                 if (probs[b].compacted && probs[b].costs == nullptr) {
-                    tiles += (long long)((probs[b].n + kLeanTile - 1) / kLeanTile);
+                    tiles += lean_tiles(probs[b].n);
                 }
             }
         }
@@ -979,13 +968,19 @@ public:
         return depth;
     }
 
+    // ROCCO_HIP_MODEL_DEPTH: the levels of every rounding-model round, 1 .. 6 (0: not set, the rule above)
+    int model_depth_fixed() const
+    {
+        return env_set("ROCCO_HIP_MODEL_DEPTH") ? std::max(1, std::min(6, env_int("ROCCO_HIP_MODEL_DEPTH", 0))) : 0;
+    }
+
     long long model_tiles_last_round_ = 0;
 
     static constexpr long long kPilotMinTiles = 128;
 
     bool can_pilot(size_t problem) const override
     {
-        return lean_eligible(problem) && (long long)((probs[problem].n + kLeanTile - 1) / kLeanTile) >= kPilotMinTiles;
+        return lean_eligible(problem) && lean_tiles(probs[problem].n) >= kPilotMinTiles;
     }
 
     int bound_points(size_t problem, int default_points, double base_hint) const override
@@ -1013,7 +1008,7 @@ public:
         }
         // a round on a small level costs its launch latency whatever it evaluates (one tile and 8 penalties per
         // workgroup: up to 256 of them run at once), a pass over a long one its evaluations
-        const long long small = env("ROCCO_HIP_POINTS_SMALL") ? std::atoll(env("ROCCO_HIP_POINTS_SMALL")) : 256000;
+        const long long small = env_ll("ROCCO_HIP_POINTS_SMALL", 256000);
         int pts = (m > 8000000) ? 3 : ((m > 2000000) ? 4 : ((m > 4 * small) ? 8 : ((m > 2 * small) ? 16 : ((m > small) ? 32 : 64))));
         if (!deep) {
             pts = std::min(pts, 8);
@@ -1053,6 +1048,62 @@ public:
         }
         ls.pool_at = at + bytes;
         return (char *)solver_->dev_lean_pool.ptr + at;
+    }
+
+    LeanWcapSlot wcap_slot(size_t problem) const { return lean_wcap_slot(solver_->dev_lean_wcap.ptr, probs.size(), problem); }
+
+    // a problem whose binade map changed since its tolerance cap was computed: one more task for launch_lean_wcap
+    void add_wcap_task(DevProblem &p, const LeanWcapSlot &slot, std::vector<LeanWcapTask> &tasks, int &blocks)
+    {
+        if (p.wcap_version == p.map_version) {
+            return;
+        }
+        tasks.push_back(lean_wcap_task(p.emap, p.scores, (long long)p.n, p.qexp, p.cmax, p.sabs, slot, blocks));
+        blocks += lean_tiles(p.n);
+        p.wcap_version = p.map_version;
+    }
+
+    // Round scratch for `records` tile records.  Tickets, the error word and the hand-off granules live in a buffer of their
+    // own that every round leaves as it found it (lean_finish_kernel restores what the round used: tickets and granules
+    // all-ones, error zero), so no fill is issued per round; it is initialised when it grows, after a failed round, or when
+    // `force_fill` asks.  The records are plain scratch.
+    int reserve_round_scratch(long long records, bool force_fill)
+    {
+        DeviceBuffer &look = solver_->dev_lean_look;
+        const void *old_ptr = look.ptr;
+        const size_t old_bytes = look.bytes;
+        int rc;
+        if ((rc = look.reserve(align_up(256 + (size_t)records * 4 * sizeof(unsigned long long), 256))) != ROCCO_HIP_OK) return rc;
+        if (force_fill || solver_->lean_look_dirty != 0 || look.ptr != old_ptr || look.bytes != old_bytes) {
+            ROCCO_HIP_TRY(hipMemsetAsync(look.ptr, 0xFF, look.bytes, stream_));
+            ROCCO_HIP_TRY(hipMemsetAsync((char *)look.ptr + 128, 0, 4, stream_));
+            solver_->lean_look_dirty = 0;
+        }
+        return solver_->dev_lean_round.reserve(align_up((size_t)records * sizeof(LeanTileRec), 256) + 256);
+    }
+
+    // A launch over that scratch whose kept-locus words and tile offsets go to the level pool; sizes, `error_out` and `ctl`
+    // are the caller's.
+    LeanLaunch round_launch(const LeanTask *tasks, const double *points, LeanResult *results) const
+    {
+        char *look = (char *)solver_->dev_lean_look.ptr;
+        LeanLaunch L;
+        L.tasks = tasks;
+        L.n_tasks = 0;
+        L.n_units = 0;
+        L.points = points;
+        L.ticket = (unsigned *)look;
+        L.look = (unsigned long long *)(look + 256);
+        L.recs = (LeanTileRec *)solver_->dev_lean_round.ptr;
+        L.bits = (unsigned *)solver_->dev_lean_pool.ptr;
+        L.tile_off = (unsigned *)solver_->dev_lean_pool.ptr;
+        L.results = results;
+        L.error = (unsigned *)(look + 128);
+        L.error_out = nullptr;
+        L.self_reset = 1;
+        L.pad = 0;
+        L.ctl = nullptr;
+        return L;
     }
 
     static double separator_score(double base, double gamma) { return std::floor(base - 2.0 * gamma - 2.0); }
@@ -1217,7 +1268,7 @@ public:
                         }
                     }
                 }
-                if (env("ROCCO_HIP_DEBUG") != nullptr) {
+                if (env_set("ROCCO_HIP_DEBUG")) {
                     std::fprintf(stderr, "[model chain] ended: %d rounds asked something, %d problems stopped at an open outcome\n",
                                  rep->rounds_run, rep->stopped);
                 }
@@ -1263,8 +1314,7 @@ public:
     // every request of the round is a rounding-model probe that says how the bisection goes on: run the rounds ahead
     bool model_chain_wanted(const std::vector<LeanReq> &reqs) const
     {
-        const char *flag = env("ROCCO_HIP_MODEL_CHAIN");
-        if ((flag != nullptr && std::atoi(flag) == 0) || model_any_ || reqs.empty() || reqs.size() > (size_t)kModelChainMaxProblems) {
+        if (!env_flag("ROCCO_HIP_MODEL_CHAIN", true) || model_any_ || reqs.empty() || reqs.size() > (size_t)kModelChainMaxProblems) {
             return false;
         }
         int rounds = 0;
@@ -1299,49 +1349,12 @@ public:
             DevProblem &p = probs[r.problem];
             const BisectionAhead &a = r.probe->ahead;
             model_chain_problems_[i] = r.problem;
-            double *wcap = (double *)solver_->dev_lean_wcap.ptr + r.problem;
-            unsigned *counters = (unsigned *)((char *)solver_->dev_lean_wcap.ptr + align_up(probs.size() * sizeof(double), 256)) + 512 * r.problem;
-            if (p.wcap_version != p.map_version) {
-                LeanWcapTask wt;
-                wt.emap = p.emap;
-                wt.s = p.scores;
-                wt.m = (long long)p.n;
-                wt.qexp = p.qexp;
-                wt.e_floor = std::ilogb(2.0 * p.cmax + 2.0 * p.sabs + (p.sabs + 2.0) + 2.0);  // (|penalty| <= sabs + 2)
-                wt.counters = counters;
-                wt.clean_chunks = counters + 384;
-                wt.wcap = wcap;
-                wt.block_begin = wcap_blocks;
-                wt.pad = 0;
-                wcap_blocks += (int)((p.n + kLeanTile - 1) / kLeanTile);
-                wcap_tasks.push_back(wt);
-                p.wcap_version = p.map_version;
-            }
+            const LeanWcapSlot slot = wcap_slot(r.problem);
+            add_wcap_task(p, slot, wcap_tasks, wcap_blocks);
+            // (the director sets n_points, n_groups, unit_begin, rec_begin and batch round by round)
             LeanTask &t = tasks[i];
-            t.s = p.scores;
-            t.m = (long long)p.n;
-            t.c_raw = p.gamma;
-            t.magic = std::ldexp(1.5, 52 + p.qexp);
-            t.big = std::ldexp(1.0, 50 + p.qexp);
-            t.n_tiles = (int)((p.n + kLeanTile - 1) / kLeanTile);
-            t.n_points = 0;
-            t.n_groups = 0;
-            t.unit_begin = 0;
-            t.point_begin = (int)i * kLeanMaxPoints;
-            t.rec_begin = 0;
-            t.bits_begin = 0;
-            t.off_begin = 0;
-            t.result_begin = (int)i * kLeanMaxPoints;
-            t.tile_stride = 1;
-            t.independent = 0;
-            t.store = 0;
-            t.emap = p.emap;
-            t.wcap = wcap;
-            t.clean_chunks = counters + 384;
-            t.cmax = p.cmax;
-            t.sabs = p.sabs;
-            t.qexp = p.qexp;
-            t.batch = kLeanModelBatch;
+            t = lean_task(p.scores, (long long)p.n, p.gamma, p.qexp, LeanTaskKind::model(p.emap, slot.wcap, slot.clean_chunks, p.cmax, p.sabs), 0);
+            t.point_begin = t.result_begin = (int)i * kLeanMaxPoints;
             tiles += t.n_tiles;
             ModelChainWalk &w = walk[i];
             w.lower = a.lower;
@@ -1368,76 +1381,54 @@ public:
             depth_floor = std::max(depth_floor, a.depth_floor);
             rounds = std::max(rounds, (a.iters_left + a.open_depth - 1) / a.open_depth);
         }
-        if (const char *e = std::getenv("ROCCO_HIP_MODEL_CHAIN_ROUNDS")) {
-            rounds = std::atoi(e);
-        }
+        rounds = env_int("ROCCO_HIP_MODEL_CHAIN_ROUNDS", rounds);
         rounds = std::max(1, std::min(kModelChainMaxRounds, rounds));
         model_tiles_last_round_ = tiles + model_tiles_answered_;
 
-        // device: [tasks][walk][wcap tasks] (uploaded) [state][points][results][ctl][globals]
-        const size_t b_tasks = align_up(B * sizeof(LeanTask), 256);
-        const size_t b_walk = align_up(B * sizeof(ModelChainWalk), 256);
-        const size_t b_wcap = align_up(wcap_tasks.size() * sizeof(LeanWcapTask), 256);
-        const size_t up_bytes = b_tasks + b_walk + b_wcap;
-        const size_t b_state = align_up(B * sizeof(ModelChainState), 256);
-        const size_t b_points = align_up(B * kLeanMaxPoints * sizeof(double), 256);
-        const size_t b_results = align_up(B * kLeanMaxPoints * sizeof(LeanResult), 256);
-        // what writes the final solutions at the chain's end (lean.h: LeanTask::store == 2): two 256-word planes and one
-        // entering value per (tile, penalty) pair of every round; ROCCO_HIP_CHAIN_WRITE=0: nothing is kept, the final windows
-        // run as before
-        const char *write_env = std::getenv("ROCCO_HIP_CHAIN_WRITE");
-        long long cap_pairs = (write_env != nullptr && std::atoi(write_env) == 0) ? 0 : std::max<long long>(tiles * 7, 2048);
+        // what writes the final solutions at the chain's end (lean.h: LeanTask::store == 2) is kept per (tile, penalty) pair of
+        // every round; ROCCO_HIP_CHAIN_WRITE=0: nothing is kept, the final windows run as before
+        long long cap_pairs = env_flag("ROCCO_HIP_CHAIN_WRITE", true) ? std::max<long long>(tiles * 7, 2048) : 0;
         if ((size_t)rounds * (size_t)cap_pairs * 2 * 256 * sizeof(unsigned) > ((size_t)1 << 30)) {
             cap_pairs = 0;  // (more than 1 GiB of class words: not worth it, the windows run)
         }
-        const size_t b_bits = align_up((size_t)rounds * (size_t)cap_pairs * 2 * 256 * sizeof(unsigned), 256);
-        const size_t b_enter = align_up((size_t)rounds * (size_t)cap_pairs * sizeof(unsigned), 256);
-        const size_t b_writes = align_up(B * sizeof(LeanWriteTask), 256);
-        const size_t dev_bytes = up_bytes + b_state + b_points + b_results + 512 + b_writes + 256 + b_enter + b_bits;
-        // host-coherent: [report][n_points per round and problem][finals][facts]
-        const size_t b_np = align_up((size_t)rounds * B * sizeof(int), 256);
-        const size_t b_finals = align_up(B * sizeof(ModelChainFinal), 256);
-        const size_t follow_bytes = 256 + b_np + b_finals + (size_t)rounds * B * kLeanMaxPoints * sizeof(ModelChainFact);
-        if ((rc = solver_->dev_chain.reserve(dev_bytes + 256)) != ROCCO_HIP_OK) return rc;
-        if ((rc = solver_->host_chain.reserve(up_bytes + 256)) != ROCCO_HIP_OK) return rc;
+        const ModelChainLayout lay = model_chain_layout(B, wcap_tasks.size(), rounds, cap_pairs);
+        if ((rc = solver_->dev_chain.reserve(lay.dev_bytes + 256)) != ROCCO_HIP_OK) return rc;
+        if ((rc = solver_->host_chain.reserve(lay.up_bytes + 256)) != ROCCO_HIP_OK) return rc;
         solver_->host_follow.coherent = true;
-        if ((rc = solver_->host_follow.reserve(follow_bytes + 256)) != ROCCO_HIP_OK) return rc;
+        if ((rc = solver_->host_follow.reserve(lay.follow_bytes + 256)) != ROCCO_HIP_OK) return rc;
         char *dv = (char *)solver_->dev_chain.ptr;
         char *h = (char *)solver_->host_chain.ptr;
         char *f = (char *)solver_->host_follow.ptr;
-        std::memcpy(h, tasks.data(), B * sizeof(LeanTask));
-        std::memcpy(h + b_tasks, walk.data(), B * sizeof(ModelChainWalk));
-        if (!wcap_tasks.empty()) std::memcpy(h + b_tasks + b_walk, wcap_tasks.data(), wcap_tasks.size() * sizeof(LeanWcapTask));
+        std::memcpy(h + lay.tasks, tasks.data(), B * sizeof(LeanTask));
+        std::memcpy(h + lay.walk, walk.data(), B * sizeof(ModelChainWalk));
+        if (!wcap_tasks.empty()) std::memcpy(h + lay.wcap, wcap_tasks.data(), wcap_tasks.size() * sizeof(LeanWcapTask));
         mark("model chain: tables built");
-        ROCCO_HIP_TRY(hipMemcpyAsync(dv, h, up_bytes, hipMemcpyHostToDevice, stream_));
+        ROCCO_HIP_TRY(hipMemcpyAsync(dv, h, lay.up_bytes, hipMemcpyHostToDevice, stream_));
         if (!wcap_tasks.empty()) {
-            if ((rc = launch_lean_wcap((const LeanWcapTask *)(dv + b_tasks + b_walk), (int)wcap_tasks.size(), wcap_blocks, stream_)) != ROCCO_HIP_OK) return rc;
+            if ((rc = launch_lean_wcap((const LeanWcapTask *)(dv + lay.wcap), (int)wcap_tasks.size(), wcap_blocks, stream_)) != ROCCO_HIP_OK) return rc;
         }
         ModelChainArgs A;
         A.n_problems = (int)B;
         A.depth0 = depth0;
         A.depth_floor = depth_floor;
-        A.depth_fixed = env("ROCCO_HIP_MODEL_DEPTH") ? std::max(1, std::min(6, std::atoi(env("ROCCO_HIP_MODEL_DEPTH")))) : 0;
-        A.adapt_batch = (env("ROCCO_HIP_LEAN_BATCH") == nullptr || std::atoi(env("ROCCO_HIP_LEAN_BATCH")) != 0) ? 1 : 0;
+        A.depth_fixed = model_depth_fixed();
+        A.adapt_batch = env_flag("ROCCO_HIP_LEAN_BATCH", true) ? 1 : 0;
         A.cap_pairs = (int)cap_pairs;
-        A.tasks = (LeanTask *)dv;
-        A.walk = (const ModelChainWalk *)(dv + b_tasks);
-        A.state = (ModelChainState *)(dv + up_bytes);
-        A.points = (double *)(dv + up_bytes + b_state);
-        A.results = (LeanResult *)(dv + up_bytes + b_state + b_points);
-        A.ctl = (LeanRoundCtl *)(dv + up_bytes + b_state + b_points + b_results);
-        A.globals = (int *)(dv + up_bytes + b_state + b_points + b_results + 256);
-        A.report = (ModelChainReport *)f;
-        A.n_points_out = (int *)(f + 256);
-        A.finals = (ModelChainFinal *)(f + 256 + b_np);
-        A.facts = (ModelChainFact *)(f + 256 + b_np + b_finals);
-        {
-            char *tail = dv + up_bytes + b_state + b_points + b_results + 512;
-            A.writes = (LeanWriteTask *)tail;
-            A.n_writes = (int *)(tail + b_writes);
-            A.entering = (unsigned *)(tail + b_writes + 256);
-            A.bits = (unsigned *)(tail + b_writes + 256 + b_enter);
-        }
+        A.tasks = (LeanTask *)(dv + lay.tasks);
+        A.walk = (const ModelChainWalk *)(dv + lay.walk);
+        A.state = (ModelChainState *)(dv + lay.state);
+        A.points = (double *)(dv + lay.points);
+        A.results = (LeanResult *)(dv + lay.results);
+        A.ctl = (LeanRoundCtl *)(dv + lay.ctl);
+        A.globals = (int *)(dv + lay.globals);
+        A.writes = (LeanWriteTask *)(dv + lay.writes);
+        A.n_writes = (int *)(dv + lay.n_writes);
+        A.entering = (unsigned *)(dv + lay.entering);
+        A.bits = (unsigned *)(dv + lay.bits);
+        A.report = (ModelChainReport *)(f + lay.report);
+        A.n_points_out = (int *)(f + lay.n_points);
+        A.finals = (ModelChainFinal *)(f + lay.finals);
+        A.facts = (ModelChainFact *)(f + lay.facts);
         model_chain_finals_ = A.finals;
         std::memset(f, 0, 256);
         model_chain_report_ = A.report;
@@ -1447,57 +1438,19 @@ public:
             facts_.resize(probs.size());
         }
 
-        // round scratch as the regular rounds keep it (lean_enqueue): sized for the deepest round a chain may plan
-        const long long max_recs = tiles * (long long)(kLeanMaxPoints - 1);
-        const size_t b_look = align_up(256 + (size_t)max_recs * 4 * sizeof(unsigned long long), 256);
-        {
-            const void *old_ptr = solver_->dev_lean_look.ptr;
-            const size_t old_bytes = solver_->dev_lean_look.bytes;
-            if ((rc = solver_->dev_lean_look.reserve(b_look)) != ROCCO_HIP_OK) return rc;
-            if (solver_->lean_look_dirty != 0 || solver_->dev_lean_look.ptr != old_ptr || solver_->dev_lean_look.bytes != old_bytes) {
-                ROCCO_HIP_TRY(hipMemsetAsync(solver_->dev_lean_look.ptr, 0xFF, solver_->dev_lean_look.bytes, stream_));
-                ROCCO_HIP_TRY(hipMemsetAsync((char *)solver_->dev_lean_look.ptr + 128, 0, 4, stream_));
-                solver_->lean_look_dirty = 0;
-            }
-        }
-        if ((rc = solver_->dev_lean_round.reserve(align_up((size_t)max_recs * sizeof(LeanTileRec), 256) + 256)) != ROCCO_HIP_OK) return rc;
-        char *look = (char *)solver_->dev_lean_look.ptr;
-        LeanLaunch L;
-        L.tasks = A.tasks;
-        L.n_tasks = 0;
-        L.n_units = 0;
-        L.points = A.points;
-        L.ticket = (unsigned *)look;
-        L.look = (unsigned long long *)(look + 256);
-        L.recs = (LeanTileRec *)solver_->dev_lean_round.ptr;
+        // round scratch sized for the deepest round a chain may plan
+        if ((rc = reserve_round_scratch(tiles * (long long)(kLeanMaxPoints - 1), false)) != ROCCO_HIP_OK) return rc;
+        LeanLaunch L = round_launch(A.tasks, A.points, A.results);
         L.bits = A.bits;          // (rounding-model tasks keep nothing in the level pool: the chain's own word arrays)
         L.tile_off = A.entering;
-        L.results = A.results;
-        L.error = (unsigned *)(look + 128);
-        L.error_out = nullptr;
-        L.self_reset = 1;
-        L.pad = 0;
         L.ctl = A.ctl;
         LeanLaunch M = L;
-        M.ticket = (unsigned *)look + 2;
+        M.ticket = L.ticket + 2;
         const int grid_eval = (int)std::max(1LL, std::min(512LL, tiles * 16));
         const int grid_finish = (int)std::max(1LL, std::min(1536LL, (long long)B * (kLeanMaxPoints - 1)));
         solver_->lean_look_dirty = 1;
-        // (round 5: evaluation and finish of a round as one launch, as the threshold search's rounds)
-        const int fused_mode = env("ROCCO_HIP_CHAIN_FUSED") == nullptr ? 0 : std::atoi(env("ROCCO_HIP_CHAIN_FUSED"));
-        const bool fused = fused_mode == 1 || fused_mode == 3;
-        A.reset = LeanRoundReset{nullptr, 0, nullptr, nullptr};
-        if (fused) {
-            const size_t words = (size_t)kLeanProgressPairs + (size_t)B * (size_t)kLeanMaxPoints;
-            if ((rc = solver_->dev_lean_progress.reserve(words * sizeof(unsigned))) != ROCCO_HIP_OK) return rc;
-            A.reset = LeanRoundReset{(unsigned *)solver_->dev_lean_progress.ptr, (int)words, L.ticket, L.error};
-        }
         for (int r = 0; r < rounds; ++r) {
             if ((rc = launch_model_chain_director(A, r, 0, stream_)) != ROCCO_HIP_OK) return rc;
-            if (fused) {
-                if ((rc = launch_lean_round_chain(M, nullptr, A.reset.progress, grid_eval, 1, stream_)) != ROCCO_HIP_OK) return rc;
-                continue;
-            }
             if ((rc = launch_lean_model_chain(M, grid_eval, stream_)) != ROCCO_HIP_OK) return rc;
             if ((rc = launch_lean_finish_chain(L, grid_finish, stream_)) != ROCCO_HIP_OK) return rc;
         }
@@ -1507,8 +1460,7 @@ public:
             if ((rc = launch_lean_write_solutions(A.writes, A.n_writes, (int)std::max(1LL, std::min(256LL, tiles)), stream_)) != ROCCO_HIP_OK) return rc;
             // ... and, behind them, their scatter into the callers' buffers and their objective sums (for every problem of the
             // chain: what was not written is scattered and summed again when its window has run)
-            const char *pf = env("ROCCO_HIP_PREFETCH_OBJECTIVE");
-            if (pf == nullptr || std::atoi(pf) != 0) {
+            if (env_flag("ROCCO_HIP_PREFETCH_OBJECTIVE", true)) {
                 if ((rc = prefetch_objectives(model_chain_problems_)) != ROCCO_HIP_OK) return rc;
                 objective_behind_chain_ = true;
             }
@@ -1521,7 +1473,7 @@ public:
         model_chain_ingested_ = 0;
         t_mchain_submit_ += now_us() - t0;
         mark("model chain: queued");
-        if (env("ROCCO_HIP_DEBUG") != nullptr) {
+        if (env_set("ROCCO_HIP_DEBUG")) {
             std::fprintf(stderr, "[model chain] %zu problems, %lld tiles, %d rounds queued (depth %d, floor %d)\n", B, tiles, rounds, depth0,
                          depth_floor);
         }
@@ -1585,62 +1537,29 @@ public:
         std::vector<size_t> post_req;
         int units = 0, recs = 0, results = 0, pre_blocks = 0, post_blocks = 0;
         const unsigned *pool_words = (const unsigned *)solver_->dev_lean_pool.ptr;
+        // a task takes the next tickets of its launch, the next penalties, records and results of the round
+        auto place = [&](LeanTask &t, LeanReq &r, std::vector<LeanTask> &launch_tasks, int &launch_units) {
+            t.unit_begin = launch_units;
+            t.point_begin = (int)points.size();
+            t.rec_begin = recs;
+            t.result_begin = r.result_begin = results;
+            launch_units += t.n_tiles * t.n_groups;
+            recs += t.n_tiles * t.n_points;
+            results += t.n_points;
+            points.insert(points.end(), r.lambdas.begin(), r.lambdas.end());
+            launch_tasks.push_back(t);
+        };
         for (LeanReq &r : reqs) {
             DevProblem &p = probs[r.problem];
             LeanState &ls = lean_[r.problem];
             if (r.model) {
                 // the compacted problem itself, chunk modes from its binade map; its own launch (other kernel)
-                double *wcap = (double *)solver_->dev_lean_wcap.ptr + r.problem;
-                if (p.wcap_version != p.map_version) {
-                    LeanWcapTask wt;
-                    wt.emap = p.emap;
-                    wt.s = p.scores;
-                    wt.m = (long long)p.n;
-                    wt.qexp = p.qexp;
-                    wt.e_floor = std::ilogb(2.0 * p.cmax + 2.0 * p.sabs + (p.sabs + 2.0) + 2.0);  // (|penalty| <= sabs + 2)
-                    wt.counters = (unsigned *)((char *)solver_->dev_lean_wcap.ptr + align_up(probs.size() * sizeof(double), 256)) + 512 * r.problem;
-                    wt.clean_chunks = wt.counters + 384;
-                    wt.wcap = wcap;
-                    wt.block_begin = wcap_blocks;
-                    wt.pad = 0;
-                    wcap_blocks += (int)((p.n + kLeanTile - 1) / kLeanTile);
-                    wcap_tasks.push_back(wt);
-                    p.wcap_version = p.map_version;
-                }
-                const int np = (int)r.lambdas.size();
-                const int nt = (int)((p.n + kLeanTile - 1) / kLeanTile);
-                model_tiles += nt;
-                LeanTask t;
-                t.s = p.scores;
-                t.m = (long long)p.n;
-                t.c_raw = p.gamma;
-                t.magic = std::ldexp(1.5, 52 + p.qexp);
-                t.big = std::ldexp(1.0, 50 + p.qexp);
-                t.n_tiles = nt;
-                t.n_points = np;
-                t.n_groups = (np + kLeanModelBatch - 1) / kLeanModelBatch;
-                t.unit_begin = model_units;
-                t.point_begin = (int)points.size();
-                t.rec_begin = recs;
-                t.bits_begin = 0;
-                t.off_begin = 0;
-                t.result_begin = results;
-                t.tile_stride = 1;
-                t.independent = 0;
-                t.store = 0;
-                t.emap = p.emap;
-                t.wcap = wcap;
-                t.clean_chunks = (const unsigned *)((char *)solver_->dev_lean_wcap.ptr + align_up(probs.size() * sizeof(double), 256)) + 512 * r.problem + 384;
-                t.cmax = p.cmax;
-                t.sabs = p.sabs;
-                t.qexp = p.qexp;
-                t.batch = kLeanModelBatch;
-                r.result_begin = results;
-                model_units += nt * t.n_groups;
-                recs += nt * np;
-                results += np;
-                points.insert(points.end(), r.lambdas.begin(), r.lambdas.end());
-                model_tasks.push_back(t);
+                const LeanWcapSlot slot = wcap_slot(r.problem);
+                add_wcap_task(p, slot, wcap_tasks, wcap_blocks);
+                LeanTask t = lean_task(p.scores, (long long)p.n, p.gamma, p.qexp,
+                                       LeanTaskKind::model(p.emap, slot.wcap, slot.clean_chunks, p.cmax, p.sabs), (int)r.lambdas.size());
+                model_tiles += t.n_tiles;
+                place(t, r, model_tasks, model_units);
                 continue;
             }
             if (ls.levels.empty()) {
@@ -1652,47 +1571,17 @@ public:
             }
             if (r.pilot) {
                 // every stride-th tile of the caller's array, each as a chain of its own; nothing is kept
-                const long long all_tiles = (long long)((p.n + kLeanTile - 1) / kLeanTile);
-                const long long pilot_tiles = env("ROCCO_HIP_PILOT_TILES") ? std::max(2, std::atoi(env("ROCCO_HIP_PILOT_TILES"))) : 16;
+                const long long all_tiles = lean_tiles(p.n);
+                const long long pilot_tiles = env_set("ROCCO_HIP_PILOT_TILES") ? std::max(2, env_int("ROCCO_HIP_PILOT_TILES", 0)) : 16;
                 const int stride = (int)std::max(4LL, all_tiles / pilot_tiles);  // about 16 tiles per chromosome
-                const int nt = (int)((all_tiles + stride - 1) / stride);
+                LeanTask t = lean_task(p.scores, (long long)p.n, p.gamma, p.qexp, LeanTaskKind::pilot(stride), (int)r.lambdas.size());
                 long long sampled = 0;
-                for (int k = 0; k < nt; ++k) {
+                for (int k = 0; k < t.n_tiles; ++k) {
                     const long long at = (long long)k * stride * kLeanTile;
                     sampled += std::min((long long)kLeanTile, (long long)p.n - at);
                 }
                 r.pilot_scale = (double)p.n / (double)std::max(1LL, sampled);
-                const int np = (int)r.lambdas.size();
-                LeanTask t;
-                t.s = p.scores;
-                t.m = (long long)p.n;
-                t.c_raw = p.gamma;
-                t.magic = std::ldexp(1.5, 52 + p.qexp);
-                t.big = std::ldexp(1.0, 50 + p.qexp);
-                t.n_tiles = nt;
-                t.n_points = np;
-                t.n_groups = (np + kLeanBatch - 1) / kLeanBatch;
-                t.unit_begin = units;
-                t.point_begin = (int)points.size();
-                t.rec_begin = recs;
-                t.bits_begin = 0;
-                t.off_begin = 0;
-                t.result_begin = results;
-                t.tile_stride = stride;
-                t.independent = 1;
-                t.store = 0;
-                t.emap = nullptr;
-                t.wcap = nullptr;
-                t.clean_chunks = nullptr;
-                t.cmax = t.sabs = 0.0;
-                t.qexp = p.qexp;
-                t.batch = kLeanBatch;
-                r.result_begin = results;
-                units += nt * t.n_groups;
-                recs += nt * np;
-                results += np;
-                points.insert(points.end(), r.lambdas.begin(), r.lambdas.end());
-                tasks.push_back(t);
+                place(t, r, tasks, units);
                 continue;
             }
             const double lam_min = *std::min_element(r.lambdas.begin(), r.lambdas.end());
@@ -1717,7 +1606,7 @@ public:
                     double *cs = (double *)lean_alloc(ls, (size_t)cl * sizeof(double));
                     int *co = (int *)lean_alloc(ls, (size_t)cl * sizeof(int));
                     if (cs != nullptr && co != nullptr) {
-                        const int nt = (int)((lv.m + kLeanTile - 1) / kLeanTile);
+                        const int nt = lean_tiles(lv.m);
                         LeanCompactTask ct;
                         ct.s = lv.s;
                         ct.orig = lv.orig;
@@ -1747,7 +1636,7 @@ public:
             }
             LeanLevel &lv = ls.levels.back();
             const int np = (int)r.lambdas.size();
-            const int nt = (int)((lv.m + kLeanTile - 1) / kLeanTile);
+            const int nt = lean_tiles(lv.m);
             if (lv.cap_points < np) {
                 // storage of this level's evaluations (level 0 never takes more than 8 penalties a round)
                 const int cap = std::max(np, (ls.levels.size() > 1) ? kLeanMaxPoints : 8);
@@ -1760,36 +1649,9 @@ public:
                 lv.cap_points = cap;
             }
             lv.has_eval = false;
-            LeanTask t;
-            t.s = lv.s;
-            t.m = lv.m;
-            t.c_raw = p.gamma;
-            t.magic = std::ldexp(1.5, 52 + p.qexp);
-            t.big = std::ldexp(1.0, 50 + p.qexp);
-            t.n_tiles = nt;
-            t.n_points = np;
-            t.n_groups = (np + kLeanBatch - 1) / kLeanBatch;
-            t.unit_begin = units;
-            t.point_begin = (int)points.size();
-            t.rec_begin = recs;
-            t.bits_begin = (long long)(lv.bits - pool_words);
-            t.off_begin = (long long)(lv.tile_off - pool_words);
-            t.result_begin = results;
-            t.tile_stride = 1;
-            t.independent = 0;
-            t.store = 1;
-            t.emap = nullptr;
-            t.wcap = nullptr;
-            t.clean_chunks = nullptr;
-            t.cmax = t.sabs = 0.0;
-            t.qexp = p.qexp;
-            t.batch = kLeanBatch;
-            r.result_begin = results;
-            units += nt * t.n_groups;
-            recs += nt * np;
-            results += np;
-            points.insert(points.end(), r.lambdas.begin(), r.lambdas.end());
-            tasks.push_back(t);
+            LeanTask t = lean_task(lv.s, lv.m, p.gamma, p.qexp,
+                                   LeanTaskKind::bound_stored((long long)(lv.bits - pool_words), (long long)(lv.tile_off - pool_words)), np);
+            place(t, r, tasks, units);
             if (r.comp != nullptr) {
                 // final compaction at lambdas[0]: its length is only known after the round
                 r.mark = ls.pool_at;
@@ -1818,32 +1680,9 @@ public:
                 }
             }
         }
-        // Penalties per workgroup: a workgroup's time grows with what it carries (about 6 us + 4 us per penalty), a
-        // round's with the number of waves of workgroups the device needs (512 at a time).  While the whole round fits
-        // at once, carry less per workgroup.
-        const bool adapt = env("ROCCO_HIP_LEAN_BATCH") == nullptr || std::atoi(env("ROCCO_HIP_LEAN_BATCH")) != 0;
-        auto rebatch = [](std::vector<LeanTask> &ts, int full, int &total_units) {
-            for (int b = 2; b < full; b *= 2) {
-                long long u = 0;
-                for (const LeanTask &t : ts) {
-                    u += (long long)t.n_tiles * ((t.n_points + b - 1) / b);
-                }
-                if (u <= 512) {
-                    int at = 0;
-                    for (LeanTask &t : ts) {
-                        t.batch = b;
-                        t.n_groups = (t.n_points + b - 1) / b;
-                        t.unit_begin = at;
-                        at += t.n_tiles * t.n_groups;
-                    }
-                    total_units = at;
-                    return;
-                }
-            }
-        };
-        if (adapt) {
-            rebatch(tasks, kLeanBatch, units);
-            rebatch(model_tasks, kLeanModelBatch, model_units);
+        if (env_flag("ROCCO_HIP_LEAN_BATCH", true)) {
+            lean_rebatch(tasks, kLeanBatch, units);
+            lean_rebatch(model_tasks, kLeanModelBatch, model_units);
         }
         lean_units += units + model_units;
         if (model_tiles + model_tiles_answered_ > 0) {
@@ -1853,23 +1692,23 @@ public:
         tasks.insert(tasks.end(), model_tasks.begin(), model_tasks.end());
 
         // descriptors: [pre][tasks (bound, then rounding-model)][points][post]
-        const size_t b_pre = align_up(pre.size() * sizeof(LeanCompactTask), 256);
-        const size_t b_tasks = align_up(tasks.size() * sizeof(LeanTask), 256);
-        const size_t b_points = align_up(points.size() * sizeof(double), 256);
-        const size_t b_post = align_up(post.size() * sizeof(LeanCompactTask), 256);
-        const size_t b_wcap = align_up(wcap_tasks.size() * sizeof(LeanWcapTask), 256);
-        const size_t desc = b_pre + b_tasks + b_points + b_post + b_wcap;
-        if ((rc = solver_->dev_lean_desc.reserve(desc + 256)) != ROCCO_HIP_OK) return rc;
-        if ((rc = solver_->host_lean_stage.reserve(desc + 256)) != ROCCO_HIP_OK) return rc;
+        Layout desc;
+        const size_t o_pre = desc.at(pre.size() * sizeof(LeanCompactTask));
+        const size_t o_tasks = desc.at(tasks.size() * sizeof(LeanTask));
+        const size_t o_points = desc.at(points.size() * sizeof(double));
+        const size_t o_post = desc.at(post.size() * sizeof(LeanCompactTask));
+        const size_t o_wcap = desc.at(wcap_tasks.size() * sizeof(LeanWcapTask));
+        if ((rc = solver_->dev_lean_desc.reserve(desc.bytes() + 256)) != ROCCO_HIP_OK) return rc;
+        if ((rc = solver_->host_lean_stage.reserve(desc.bytes() + 256)) != ROCCO_HIP_OK) return rc;
         char *h = (char *)solver_->host_lean_stage.ptr;
         char *d = (char *)solver_->dev_lean_desc.ptr;
-        if (!pre.empty()) std::memcpy(h, pre.data(), pre.size() * sizeof(LeanCompactTask));
-        std::memcpy(h + b_pre, tasks.data(), tasks.size() * sizeof(LeanTask));
-        std::memcpy(h + b_pre + b_tasks, points.data(), points.size() * sizeof(double));
-        if (!post.empty()) std::memcpy(h + b_pre + b_tasks + b_points, post.data(), post.size() * sizeof(LeanCompactTask));
-        if (!wcap_tasks.empty()) std::memcpy(h + b_pre + b_tasks + b_points + b_post, wcap_tasks.data(), wcap_tasks.size() * sizeof(LeanWcapTask));
+        if (!pre.empty()) std::memcpy(h + o_pre, pre.data(), pre.size() * sizeof(LeanCompactTask));
+        std::memcpy(h + o_tasks, tasks.data(), tasks.size() * sizeof(LeanTask));
+        std::memcpy(h + o_points, points.data(), points.size() * sizeof(double));
+        if (!post.empty()) std::memcpy(h + o_post, post.data(), post.size() * sizeof(LeanCompactTask));
+        if (!wcap_tasks.empty()) std::memcpy(h + o_wcap, wcap_tasks.data(), wcap_tasks.size() * sizeof(LeanWcapTask));
         const double le1 = now_us();
-        ROCCO_HIP_TRY(hipMemcpyAsync(d, h, desc, hipMemcpyHostToDevice, stream_));
+        ROCCO_HIP_TRY(hipMemcpyAsync(d, h, desc.bytes(), hipMemcpyHostToDevice, stream_));
         const double le2 = now_us();
         t_lean_cpu_ += le1 - le0;
         t_lean_h2d_ += le2 - le1;
@@ -1879,57 +1718,25 @@ public:
             ~Launches() { acc += now_us() - t0; }
         } launches{t_lean_launch_, le2};
         if (!wcap_tasks.empty()) {
-            if ((rc = launch_lean_wcap((const LeanWcapTask *)(d + b_pre + b_tasks + b_points + b_post), (int)wcap_tasks.size(), wcap_blocks,
-                                       stream_)) != ROCCO_HIP_OK) return rc;
+            if ((rc = launch_lean_wcap((const LeanWcapTask *)(d + o_wcap), (int)wcap_tasks.size(), wcap_blocks, stream_)) != ROCCO_HIP_OK) return rc;
         }
 
-        // Round scratch.  Tickets, the error word and the hand-off granules live in a buffer of their own that every
-        // round leaves as it found it (lean_finish_kernel restores what the round used: tickets and granules all-ones,
-        // error zero), so no fill is issued per round; it is initialised when it grows or after a failed round.  The
-        // records are plain scratch.  Results and the error word are written straight into pinned host memory by the
-        // finish kernel.
-        const char *fills = env("ROCCO_HIP_LEAN_FILLS");
-        const bool self_reset = fills == nullptr || std::atoi(fills) == 0;
-        const size_t b_look = align_up(256 + (size_t)recs * 4 * sizeof(unsigned long long), 256);
-        const size_t b_recs = align_up((size_t)recs * sizeof(LeanTileRec), 256);
-        const size_t b_res = align_up((size_t)results * sizeof(LeanResult) + 64, 256);
-        {
-            const void *old_ptr = solver_->dev_lean_look.ptr;
-            const size_t old_bytes = solver_->dev_lean_look.bytes;
-            if ((rc = solver_->dev_lean_look.reserve(b_look)) != ROCCO_HIP_OK) return rc;
-            if (!self_reset || solver_->lean_look_dirty != 0 || solver_->dev_lean_look.ptr != old_ptr || solver_->dev_lean_look.bytes != old_bytes) {
-                ROCCO_HIP_TRY(hipMemsetAsync(solver_->dev_lean_look.ptr, 0xFF, solver_->dev_lean_look.bytes, stream_));
-                ROCCO_HIP_TRY(hipMemsetAsync((char *)solver_->dev_lean_look.ptr + 128, 0, 4, stream_));
-                solver_->lean_look_dirty = 0;
-            }
-        }
-        if ((rc = solver_->dev_lean_round.reserve(b_recs + 256)) != ROCCO_HIP_OK) return rc;
-        if ((rc = solver_->host_lean_back.reserve(b_res)) != ROCCO_HIP_OK) return rc;
-        char *look = (char *)solver_->dev_lean_look.ptr;
-        unsigned *error = (unsigned *)(look + 128);
+        // Round scratch (ROCCO_HIP_LEAN_FILLS=1: filled every round).  Results and the error word are written straight into
+        // pinned host memory by the finish kernel.
+        if ((rc = reserve_round_scratch(recs, env_flag("ROCCO_HIP_LEAN_FILLS", false))) != ROCCO_HIP_OK) return rc;
+        if ((rc = solver_->host_lean_back.reserve(align_up((size_t)results * sizeof(LeanResult) + 64, 256))) != ROCCO_HIP_OK) return rc;
         LeanResult *results_host = (LeanResult *)solver_->host_lean_back.ptr;
         unsigned *error_host = (unsigned *)((char *)solver_->host_lean_back.ptr + (size_t)results * sizeof(LeanResult));
         error_host[0] = 0u;
         error_host[1] = 0u;  // second slot: the word of a compaction launched BEHIND the finish kernel
+        LeanLaunch L = round_launch((const LeanTask *)(d + o_tasks), (const double *)(d + o_points), results_host);
+        unsigned *error = L.error;
         if (!pre.empty()) {
-            if ((rc = launch_lean_compact((const LeanCompactTask *)d, (int)pre.size(), pre_blocks, error, stream_)) != ROCCO_HIP_OK) return rc;
+            if ((rc = launch_lean_compact((const LeanCompactTask *)(d + o_pre), (int)pre.size(), pre_blocks, error, stream_)) != ROCCO_HIP_OK) return rc;
         }
-        LeanLaunch L;
-        L.tasks = (const LeanTask *)(d + b_pre);
         L.n_tasks = n_bound_tasks;
         L.n_units = units;
-        L.points = (const double *)(d + b_pre + b_tasks);
-        L.ticket = (unsigned *)look;
-        L.look = (unsigned long long *)(look + 256);
-        L.recs = (LeanTileRec *)solver_->dev_lean_round.ptr;
-        L.bits = (unsigned *)solver_->dev_lean_pool.ptr;
-        L.tile_off = (unsigned *)solver_->dev_lean_pool.ptr;
-        L.results = results_host;
-        L.error = error;
         L.error_out = error_host;
-        L.self_reset = 1;
-        L.pad = 0;
-        L.ctl = nullptr;
         solver_->lean_look_dirty = 1;  // until the finish kernel that restores the scratch is in the stream
         if ((rc = launch_lean_eval(L, stream_)) != ROCCO_HIP_OK) return rc;
         if (!model_tasks.empty()) {
@@ -1937,7 +1744,7 @@ public:
             M.tasks = L.tasks + n_bound_tasks;
             M.n_tasks = (int)model_tasks.size();
             M.n_units = model_units;
-            M.ticket = (unsigned *)look + 2;
+            M.ticket = L.ticket + 2;
             if ((rc = launch_lean_model(M, stream_)) != ROCCO_HIP_OK) return rc;
         }
         L.n_tasks = (int)tasks.size();  // the finish launch closes every task's fill
@@ -1945,8 +1752,7 @@ public:
         solver_->lean_look_dirty = 0;
         if (!post.empty()) {
             // (rare since levels are adopted: a final compaction behind the finish kernel reports through a copy)
-            if ((rc = launch_lean_compact((const LeanCompactTask *)(d + b_pre + b_tasks + b_points), (int)post.size(), post_blocks,
-                                          error, stream_)) != ROCCO_HIP_OK) return rc;
+            if ((rc = launch_lean_compact((const LeanCompactTask *)(d + o_post), (int)post.size(), post_blocks, error, stream_)) != ROCCO_HIP_OK) return rc;
             // its own pinned slot: the finish kernel has already written the evaluation's word to slot 0 (and cleared the
             // device word), and a spin-limit failure recorded there must survive this copy
             ROCCO_HIP_TRY(hipMemcpyAsync(error_host + 1, error, sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
@@ -1954,7 +1760,7 @@ public:
         }
         lean_result_count_ = results;
         lean_inflight_ = reqs;
-        if (env("ROCCO_HIP_DEBUG") != nullptr) {
+        if (env_set("ROCCO_HIP_DEBUG")) {
             std::fprintf(stderr, "[lean round %d] %zu tasks (%zu rounding-model), %d + %d workgroups, %zu compactions before, %zu after\n",
                          lean_rounds, tasks.size(), model_tasks.size(), units, model_units, pre.size(), post.size());
         }
@@ -2009,7 +1815,7 @@ public:
                 }
                 lean_model_points += (long long)r.lambdas.size();
                 lean_model_open += (long long)open;
-                if (env("ROCCO_HIP_DEBUG") != nullptr) {
+                if (env_set("ROCCO_HIP_DEBUG")) {
                     std::fprintf(stderr, "[lean model] problem %zu (n=%zu): %zu penalties, first %.17g -> count %lld, %zu not certified (reasons %lld)\n",
                                  r.problem, p.n, r.lambdas.size(), r.lambdas[0], res[r.result_begin].count, open, why);
                 }
@@ -2029,7 +1835,7 @@ public:
                     r.probe->results[i].count = res[r.result_begin + (int)i].count;
                 }
             }
-            if (env("ROCCO_HIP_DEBUG") != nullptr) {
+            if (env_set("ROCCO_HIP_DEBUG")) {
                 std::fprintf(stderr, "[lean] problem %zu level %zu (m=%lld, base %.17g): %zu penalties, first %.17g -> count %lld, child %lld\n",
                              r.problem, ls.levels.size() - 1, lv.m, lv.base, np, r.lambdas[0], res[r.result_begin].count,
                              res[r.result_begin].child_len);
@@ -2043,7 +1849,7 @@ public:
                     r.comp->n_new = (size_t)cl;
                     r.comp->score_floor = r.sep;
                 }
-                if (!r.comp->done && env("ROCCO_HIP_DEBUG") != nullptr) {
+                if (!r.comp->done && env_set("ROCCO_HIP_DEBUG")) {
                     std::fprintf(stderr, "[lean] problem %zu: final compaction declined (child %lld of %zu)\n", r.problem, cl, p.n);
                 }
             }
@@ -2141,7 +1947,7 @@ public:
                 req.done = true;
                 req.n_new = (size_t)lv.m;
                 req.score_floor = lv.sep;
-                if (env("ROCCO_HIP_DEBUG") != nullptr) {
+                if (env_set("ROCCO_HIP_DEBUG")) {
                     std::fprintf(stderr, "[lean] problem %zu: level %zu (m=%lld, base %.17g) adopted for penalties >= %.17g\n",
                                  req.problem, k, lv.m, lv.base, req.lambda_base);
                 }
@@ -2193,7 +1999,7 @@ public:
                         q.results = res;
                         model_chain_hits += (long long)q.lambdas.size();
                         lean_model_points += (long long)q.lambdas.size();
-                        model_tiles_answered_ += (long long)((probs[q.problem].n + kLeanTile - 1) / kLeanTile);
+                        model_tiles_answered_ += lean_tiles(probs[q.problem].n);
                         continue;
                     }
                 }
@@ -2274,9 +2080,8 @@ public:
             // windows that each write the solution of one penalty and nothing else: the calibration's last round when every
             // step was decided -- their objectives ride behind them
             std::vector<size_t> final_problems;
-            const char *pf = env("ROCCO_HIP_PREFETCH_OBJECTIVE");
             const size_t open_windows = windows.size() - answered_problems.size();
-            if ((pf == nullptr || std::atoi(pf) != 0) && open_windows > 0 && tasks.size() == open_windows && lean_inflight_.empty()) {
+            if (env_flag("ROCCO_HIP_PREFETCH_OBJECTIVE", true) && open_windows > 0 && tasks.size() == open_windows && lean_inflight_.empty()) {
                 for (size_t i = 0; i < windows.size(); ++i) {
                     if (!window_answered_[i] && windows[i].lambda_lo == windows[i].lambda_hi) {
                         final_problems.push_back(windows[i].problem);
@@ -2370,8 +2175,9 @@ public:
         ran = false;
         const double tc0 = now_us();
         const size_t B = probs.size();
-        const char *flag = std::getenv("ROCCO_HIP_CHAIN");
-        if ((flag != nullptr && std::atoi(flag) == 0) || solver_->lean == 0 || B == 0 || B > (size_t)kChainMaxProblems ||
+        // ROCCO_HIP_CHAIN: 0 forbids the chain, any other value forces it, unset leaves it to the batch's size
+        const bool forced = env_set("ROCCO_HIP_CHAIN");
+        if (!env_flag("ROCCO_HIP_CHAIN", true) || solver_->lean == 0 || B == 0 || B > (size_t)kChainMaxProblems ||
             !opt.use_bounds || opt.force_exact || !opt.use_compaction) {
             return ROCCO_HIP_OK;
         }
@@ -2379,7 +2185,7 @@ public:
         long long tiles0 = 0;
         for (size_t b = 0; b < B; ++b) {
             any = any || lean_eligible(b);
-            tiles0 += (long long)((probs[b].n + kLeanTile - 1) / kLeanTile);
+            tiles0 += lean_tiles(probs[b].n);
             if (probs[b].n >= ((size_t)1 << 31)) {
                 return ROCCO_HIP_OK;
             }
@@ -2391,48 +2197,38 @@ public:
         // in turn-around; what the chain gains is in the rounds' shape (three short pilot rounds of eight penalties, two
         // penalties on the pass over every locus), which pays on a genome (7 555 tiles: 2.80 -> 2.60 ms per calibration) and not
         // on a rank's shard of one (973 tiles at N = 8: 0.94 -> 1.07 ms).  Below `min_tiles` the host sequences the rounds.
-        const long long min_tiles = std::getenv("ROCCO_HIP_CHAIN_MIN_TILES") ? std::atoll(std::getenv("ROCCO_HIP_CHAIN_MIN_TILES")) : 4096;
-        if (tiles0 < min_tiles && flag == nullptr) {
+        if (tiles0 < env_ll("ROCCO_HIP_CHAIN_MIN_TILES", 4096) && !forced) {
             return ROCCO_HIP_OK;
         }
         int rc;
         if ((rc = lean_prepare()) != ROCCO_HIP_OK) return rc;
         ChainTuning tune;
-        tune.pilot_rounds = std::getenv("ROCCO_HIP_CHAIN_PILOT_ROUNDS") ? std::atoi(std::getenv("ROCCO_HIP_CHAIN_PILOT_ROUNDS")) : 6;
-        tune.pilot_points = std::getenv("ROCCO_HIP_CHAIN_PILOT_POINTS") ? std::atoi(std::getenv("ROCCO_HIP_CHAIN_PILOT_POINTS")) : 8;
+        tune.pilot_rounds = env_int("ROCCO_HIP_CHAIN_PILOT_ROUNDS", 6);
+        tune.pilot_points = env_int("ROCCO_HIP_CHAIN_PILOT_POINTS", 8);
         if (opt.pilot_rounds <= 0) {
             tune.pilot_rounds = 0;
         }
-        tune.wgs = std::getenv("ROCCO_HIP_CHAIN_WGS") ? std::max(64, std::atoi(std::getenv("ROCCO_HIP_CHAIN_WGS"))) : 512;
-        tune.pilot_wgs = std::getenv("ROCCO_HIP_CHAIN_PILOT_WGS") ? std::max(64, std::atoi(std::getenv("ROCCO_HIP_CHAIN_PILOT_WGS"))) : 512;
-        tune.pilot_tiles = std::getenv("ROCCO_HIP_CHAIN_PILOT_TILES") ? std::max(2, std::atoi(std::getenv("ROCCO_HIP_CHAIN_PILOT_TILES"))) : 16;
-        tune.big_points = std::getenv("ROCCO_HIP_CHAIN_BIG_POINTS") ? std::atoi(std::getenv("ROCCO_HIP_CHAIN_BIG_POINTS")) : 2;
+        tune.wgs = std::max(64, env_int("ROCCO_HIP_CHAIN_WGS", 512));
+        tune.pilot_wgs = std::max(64, env_int("ROCCO_HIP_CHAIN_PILOT_WGS", 512));
+        tune.pilot_tiles = std::max(2, env_int("ROCCO_HIP_CHAIN_PILOT_TILES", 16));
+        tune.big_points = env_int("ROCCO_HIP_CHAIN_BIG_POINTS", 2);
         tune.search_gate = opt.search_gate;
         tune.survey_gate = opt.survey_gate;
-        tune.interpolate = std::getenv("ROCCO_HIP_CHAIN_INTERP") ? std::atoi(std::getenv("ROCCO_HIP_CHAIN_INTERP")) : 0;
-        tune.spread = std::getenv("ROCCO_HIP_CHAIN_SPREAD") ? std::atof(std::getenv("ROCCO_HIP_CHAIN_SPREAD")) : 0.005;
+        tune.interpolate = env_int("ROCCO_HIP_CHAIN_INTERP", 0);
+        tune.spread = env_double("ROCCO_HIP_CHAIN_SPREAD", 0.005);
         if (!(tune.spread > 0.0 && tune.spread < 0.5)) {
             tune.spread = 0.005;
         }
-        tune.soft_mult = std::getenv("ROCCO_HIP_CHAIN_SOFT") ? std::atof(std::getenv("ROCCO_HIP_CHAIN_SOFT")) : 0.8;
+        tune.soft_mult = env_double("ROCCO_HIP_CHAIN_SOFT", 0.8);
         {
             std::vector<double> mults = {2.2, 1.2};
-            if (const char *e = std::getenv("ROCCO_HIP_CHAIN_LEVELS")) {
-                mults.clear();
-                for (const char *q = e; *q != '\0';) {
-                    char *end = nullptr;
-                    const double v = std::strtod(q, &end);
-                    if (end == q) break;
-                    if (v > 0.0) mults.push_back(v);
-                    q = (*end == ',') ? end + 1 : end;
-                }
-            }
+            env_list("ROCCO_HIP_CHAIN_LEVELS", mults);
             tune.n_mults = (int)std::min(mults.size(), (size_t)kChainMaxMults);
             for (int k = 0; k < kChainMaxMults; ++k) {
                 tune.mults[k] = (k < tune.n_mults) ? mults[(size_t)k] : 0.0;
             }
         }
-        const int R = std::getenv("ROCCO_HIP_CHAIN_ROUNDS") ? std::max(1, std::atoi(std::getenv("ROCCO_HIP_CHAIN_ROUNDS"))) : 12;
+        const int R = std::max(1, env_int("ROCCO_HIP_CHAIN_ROUNDS", 12));
 
         // ---- statistics pass: descriptors as in compute_stats ----
         std::vector<int2> blockmap;
@@ -2444,32 +2240,28 @@ public:
         }
         const size_t nbt = blockmap.size();
         // ---- one device buffer: [ctl][inputs][stats tasks][blockmap] (uploaded) [probs][stats] (downloaded) [rest] ----
-        size_t off = 0;
-        auto carve = [&off](size_t bytes) {
-            const size_t at = off;
-            off += align_up(bytes, 256);
-            return at;
-        };
-        const size_t o_ctl = carve(sizeof(LeanRoundCtl));
-        const size_t o_in = carve(B * sizeof(ChainInput));
-        const size_t o_stasks = carve(B * sizeof(StatsTask));
-        const size_t o_bmap = carve(nbt * sizeof(int2));
-        const size_t up_bytes = off;
-        const size_t o_probs = carve(B * sizeof(ChainProb));
-        const size_t o_stats = carve(B * 5 * sizeof(double));
-        const size_t o_ctl_back = carve(sizeof(LeanRoundCtl));
-        const size_t down_bytes = off - o_probs;
-        const size_t o_hot = carve(B * sizeof(ChainHot));
-        const size_t o_pilot = carve(B * sizeof(ChainPilot));
-        const size_t o_evals = carve(B * sizeof(ChainEvals));
-        const size_t o_tasks = carve(B * sizeof(LeanTask));
-        const size_t o_points = carve(B * kLeanMaxPoints * sizeof(double));
-        const size_t o_results = carve(B * kLeanMaxPoints * sizeof(LeanResult));
-        const size_t o_pre = carve(B * sizeof(LeanCompactTask));
-        const size_t o_part = carve(nbt * 5 * sizeof(double));
-        const bool want_trace = std::getenv("ROCCO_HIP_CHAIN_TRACE") != nullptr;
-        const size_t o_trace = carve((size_t)(R + 2) * 8 * sizeof(long long));
-        if ((rc = solver_->dev_chain.reserve(off + 256)) != ROCCO_HIP_OK) return rc;
+        Layout lay;
+        const size_t o_ctl = lay.at(sizeof(LeanRoundCtl));
+        const size_t o_in = lay.at(B * sizeof(ChainInput));
+        const size_t o_stasks = lay.at(B * sizeof(StatsTask));
+        const size_t o_bmap = lay.at(nbt * sizeof(int2));
+        lay.end_upload();
+        const size_t up_bytes = lay.uploaded;
+        const size_t o_probs = lay.at(B * sizeof(ChainProb));
+        const size_t o_stats = lay.at(B * 5 * sizeof(double));
+        const size_t o_ctl_back = lay.at(sizeof(LeanRoundCtl));
+        const size_t down_bytes = lay.bytes() - o_probs;
+        const size_t o_hot = lay.at(B * sizeof(ChainHot));
+        const size_t o_pilot = lay.at(B * sizeof(ChainPilot));
+        const size_t o_evals = lay.at(B * sizeof(ChainEvals));
+        const size_t o_tasks = lay.at(B * sizeof(LeanTask));
+        const size_t o_points = lay.at(B * kLeanMaxPoints * sizeof(double));
+        const size_t o_results = lay.at(B * kLeanMaxPoints * sizeof(LeanResult));
+        const size_t o_pre = lay.at(B * sizeof(LeanCompactTask));
+        const size_t o_part = lay.at(nbt * 5 * sizeof(double));
+        const bool want_trace = env_set("ROCCO_HIP_CHAIN_TRACE");
+        const size_t o_trace = lay.at((size_t)(R + 2) * 8 * sizeof(long long));
+        if ((rc = solver_->dev_chain.reserve(lay.bytes() + 256)) != ROCCO_HIP_OK) return rc;
         if ((rc = solver_->host_chain.reserve(std::max(up_bytes, down_bytes) + 256)) != ROCCO_HIP_OK) return rc;
         char *dv = (char *)solver_->dev_chain.ptr;
         char *h = (char *)solver_->host_chain.ptr;
@@ -2499,19 +2291,7 @@ public:
 
         // ---- round scratch (as lean_enqueue keeps it) ----
         const long long rec_cap = 8 * (tiles0 + (long long)tune.wgs) + 64 * (long long)B;
-        const size_t b_look = align_up(256 + (size_t)rec_cap * 4 * sizeof(unsigned long long), 256);
-        {
-            const void *old_ptr = solver_->dev_lean_look.ptr;
-            const size_t old_bytes = solver_->dev_lean_look.bytes;
-            if ((rc = solver_->dev_lean_look.reserve(b_look)) != ROCCO_HIP_OK) return rc;
-            if (solver_->lean_look_dirty != 0 || solver_->dev_lean_look.ptr != old_ptr || solver_->dev_lean_look.bytes != old_bytes) {
-                ROCCO_HIP_TRY(hipMemsetAsync(solver_->dev_lean_look.ptr, 0xFF, solver_->dev_lean_look.bytes, stream_));
-                ROCCO_HIP_TRY(hipMemsetAsync((char *)solver_->dev_lean_look.ptr + 128, 0, 4, stream_));
-                solver_->lean_look_dirty = 0;
-            }
-        }
-        if ((rc = solver_->dev_lean_round.reserve(align_up((size_t)rec_cap * sizeof(LeanTileRec), 256) + 256)) != ROCCO_HIP_OK) return rc;
-        char *look = (char *)solver_->dev_lean_look.ptr;
+        if ((rc = reserve_round_scratch(rec_cap, false)) != ROCCO_HIP_OK) return rc;
 
         ChainArgs A;
         A.n_problems = (int)B;
@@ -2532,7 +2312,7 @@ public:
         A.tune = tune;
         // the report comes through host-coherent memory as soon as the searches have ended (chain.h: ChainArgs::follow);
         // ROCCO_HIP_CHAIN_FOLLOW=0: through a copy at the end of the stream
-        const bool follow = std::getenv("ROCCO_HIP_CHAIN_FOLLOW") == nullptr || std::atoi(std::getenv("ROCCO_HIP_CHAIN_FOLLOW")) != 0;
+        const bool follow = env_flag("ROCCO_HIP_CHAIN_FOLLOW", true);
         A.follow = nullptr;
         A.follow_words = (int)((o_ctl_back - o_probs) / 8);
         A.follow_ctl_word = A.follow_words;
@@ -2543,53 +2323,14 @@ public:
             std::memset(solver_->host_follow.ptr, 0, 256);
         }
 
-        LeanLaunch L;
-        L.tasks = A.tasks;
-        L.n_tasks = 0;
-        L.n_units = 0;
-        L.points = A.points;
-        L.ticket = (unsigned *)look;
-        L.look = (unsigned long long *)(look + 256);
-        L.recs = (LeanTileRec *)solver_->dev_lean_round.ptr;
-        L.bits = (unsigned *)solver_->dev_lean_pool.ptr;
-        L.tile_off = (unsigned *)solver_->dev_lean_pool.ptr;
-        L.results = A.results;
-        L.error = (unsigned *)(look + 128);
-        L.error_out = nullptr;
-        L.self_reset = 1;
-        L.pad = 0;
+        LeanLaunch L = round_launch(A.tasks, A.points, A.results);
         L.ctl = A.ctl;
         const int eval_grid = (int)std::min<long long>(512, std::max<long long>(1, tiles0 * 8));
         const int compact_grid = (int)std::min<long long>(1024, std::max<long long>(1, tiles0));
         const int finish_grid = (int)std::min<size_t>(2048, B * (size_t)kLeanMaxPoints);
         solver_->lean_look_dirty = 1;  // until every finish launch that restores the scratch is in the stream
-        // Round 5, measured and NOT adopted: a round's compaction, evaluation and finish as ONE launch
-        // (lean.h: LeanRoundReset; the director in front of the next round restores what the finish launch restored).  Whole
-        // genome, same box, interleaved: three launches 2.71-2.87 ms, one launch 3.29-3.45 (the pairs of a round are finished
-        // by the few workgroups that held the last tiles instead of 1 536 at once, and the compactions run two to a CU behind
-        // fences), compactions + evaluation as one and the finish apart 3.11-3.18; the rounding-model rounds as one launch
-        // 2.71-2.90 against 2.71-2.87.  ROCCO_HIP_CHAIN_FUSED: 0 (default) neither chain, 1 both, 2 the threshold search only,
-        // 3 the rounding-model rounds only, 4 the threshold search's compactions + evaluation.
-        const int fused_mode = env("ROCCO_HIP_CHAIN_FUSED") == nullptr ? 0 : std::atoi(env("ROCCO_HIP_CHAIN_FUSED"));
-        const bool fused = fused_mode == 1 || fused_mode == 2, half_fused = fused_mode == 4;  // (4: compactions + evaluation, finish apart)
-        A.reset = LeanRoundReset{nullptr, 0, nullptr, nullptr};
-        if (fused || half_fused) {
-            const size_t words = (size_t)kLeanProgressPairs + B * (size_t)kLeanMaxPoints;
-            if ((rc = solver_->dev_lean_progress.reserve(words * sizeof(unsigned))) != ROCCO_HIP_OK) return rc;
-            A.reset = LeanRoundReset{(unsigned *)solver_->dev_lean_progress.ptr, half_fused ? kLeanProgressPairs : (int)words,
-                                     half_fused ? nullptr : L.ticket, L.error};
-        }
         for (int r = 0; r < R; ++r) {
             if ((rc = launch_chain_director(A, r, 0, stream_)) != ROCCO_HIP_OK) return rc;
-            if (fused) {
-                if ((rc = launch_lean_round_chain(L, A.pre, A.reset.progress, eval_grid, 0, stream_)) != ROCCO_HIP_OK) return rc;
-                continue;
-            }
-            if (half_fused) {
-                if ((rc = launch_lean_round_chain(L, A.pre, A.reset.progress, eval_grid, 0, stream_, 0)) != ROCCO_HIP_OK) return rc;
-                if ((rc = launch_lean_finish_chain(L, finish_grid, stream_)) != ROCCO_HIP_OK) return rc;
-                continue;
-            }
             if ((rc = launch_lean_compact_chain(A.pre, A.ctl, compact_grid, stream_)) != ROCCO_HIP_OK) return rc;
             if ((rc = launch_lean_eval_chain(L, eval_grid, stream_)) != ROCCO_HIP_OK) return rc;
             if ((rc = launch_lean_finish_chain(L, finish_grid, stream_)) != ROCCO_HIP_OK) return rc;
@@ -2657,8 +2398,8 @@ public:
         }
         stats_out.assign(hstats, hstats + 5 * B);
         pre.assign(B, Presearch());
-        const bool debug = env("ROCCO_HIP_DEBUG") != nullptr;
-        const bool chain_debug = std::getenv("ROCCO_HIP_CHAIN_DEBUG") != nullptr;
+        const bool debug = env_set("ROCCO_HIP_DEBUG");
+        const bool chain_debug = env_set("ROCCO_HIP_CHAIN_DEBUG");
         bool grid_ok = true;
         for (size_t b = 0; b < B; ++b) {
             const ChainProb &r = rep[b];
@@ -2836,7 +2577,7 @@ private:
             if (rt[t].survey) {
                 ft.frz_out = p.frz;
             }
-            if (env("ROCCO_HIP_DEBUG") != nullptr) {
+            if (env_set("ROCCO_HIP_DEBUG")) {
                 const char *kind = rt[t].record ? "spine" : (rt[t].survey ? "survey" : (rt[t].window ? "window" : (rt[t].map ? "map" : "probe")));
                 std::fprintf(stderr, "[round %d] %s problem %zu: %zu lambdas (first %.17g, margin %.3g), %zu / %d blocks%s\n",
                              rounds, kind, rt[t].problem, rt[t].lambdas.size(), rt[t].lambdas[0], rt[t].margin,
@@ -2925,13 +2666,14 @@ private:
         blocks_launched += (long long)NB;
 
         // ---- descriptor upload ----
-        const size_t b_tasks = align_up(T * sizeof(FastTask), 256);
-        const size_t b_chains = align_up(C * sizeof(FastChain), 256);
-        const size_t b_slots = align_up(S * sizeof(FastSlot), 256);
-        const size_t b_map = align_up(NB * sizeof(int2), 256);
-        const size_t b_mapall = align_up(NBA * sizeof(int2), 256);
-        const size_t b_skip = align_up(skip_bytes.size() + 1, 256);
-        const size_t desc_bytes = b_tasks + b_chains + b_slots + b_map + b_mapall + b_skip;
+        Layout desc;
+        const size_t d_tasks = desc.at(T * sizeof(FastTask));
+        const size_t d_chains = desc.at(C * sizeof(FastChain));
+        const size_t d_slots = desc.at(S * sizeof(FastSlot));
+        const size_t d_map = desc.at(NB * sizeof(int2));
+        const size_t d_mapall = desc.at(NBA * sizeof(int2));
+        const size_t d_skip = desc.at(skip_bytes.size() + 1);
+        const size_t desc_bytes = desc.bytes();
         int rc;
         if ((rc = solver_->dev_tasks.reserve(desc_bytes)) != ROCCO_HIP_OK) return rc;
         if ((rc = solver_->host_stage.reserve(desc_bytes)) != ROCCO_HIP_OK) return rc;
@@ -2941,57 +2683,52 @@ private:
         t_prep_ += tt1 - tt0;
         for (size_t t = 0; t < T; ++t) {
             if (skip_off[t] >= 0) {  // record rounds: "not evaluated this round" instead of "frozen"
-                tasks[t].frz.flag = (uint8_t *)(dd + b_tasks + b_chains + b_slots + b_map + b_mapall + skip_off[t]);
+                tasks[t].frz.flag = (uint8_t *)(dd + d_skip + skip_off[t]);
             }
         }
-        std::memcpy(h, tasks.data(), T * sizeof(FastTask));
-        std::memcpy(h + b_tasks, chains.data(), C * sizeof(FastChain));
-        std::memcpy(h + b_tasks + b_chains, slots.data(), S * sizeof(FastSlot));
-        std::memcpy(h + b_tasks + b_chains + b_slots, blockmap.data(), NB * sizeof(int2));
-        std::memcpy(h + b_tasks + b_chains + b_slots + b_map, blockmap_all.data(), NBA * sizeof(int2));
+        std::memcpy(h + d_tasks, tasks.data(), T * sizeof(FastTask));
+        std::memcpy(h + d_chains, chains.data(), C * sizeof(FastChain));
+        std::memcpy(h + d_slots, slots.data(), S * sizeof(FastSlot));
+        std::memcpy(h + d_map, blockmap.data(), NB * sizeof(int2));
+        std::memcpy(h + d_mapall, blockmap_all.data(), NBA * sizeof(int2));
         if (!skip_bytes.empty()) {
-            std::memcpy(h + b_tasks + b_chains + b_slots + b_map + b_mapall, skip_bytes.data(), skip_bytes.size());
+            std::memcpy(h + d_skip, skip_bytes.data(), skip_bytes.size());
         }
         ROCCO_HIP_TRY(hipMemcpyAsync(dd, h, desc_bytes, hipMemcpyHostToDevice, stream_));
 
-        // ---- scratch carve ----
-        size_t off = 0;
-        auto carve = [&off](size_t bytes) {
-            const size_t at = off;
-            off += align_up(bytes, 256);
-            return at;
-        };
-        const size_t o_agg_a = carve((size_t)chain_chunks * 8), o_agg_lo = carve((size_t)chain_chunks * 8),
-                     o_agg_hi = carve((size_t)chain_chunks * 8), o_pstar = carve((size_t)chain_chunks);
-        const size_t o_blk_a = carve((size_t)chain_blocks * 8), o_blk_lo = carve((size_t)chain_blocks * 8),
-                     o_blk_hi = carve((size_t)chain_blocks * 8), o_din = carve((size_t)chain_blocks * 8);
-        const size_t o_lcc = carve((size_t)slot_chunks);
-        const size_t o_wc = carve((size_t)slot_chunks * 8), o_gc = carve(any_map ? (size_t)slot_chunks * 8 : 8);
-        const size_t o_lcb = carve((size_t)slot_blocks * 4), o_lcin = carve((size_t)slot_blocks * 4);
-        const size_t o_wb = carve((size_t)slot_blocks * 8), o_winb = carve((size_t)slot_blocks * 8);
-        const size_t o_gb = carve((size_t)slot_blocks * 8), o_ginb = carve((size_t)slot_blocks * 8);
-        const size_t o_fvlo = carve((size_t)slot_blocks), o_fvhi = carve((size_t)slot_blocks);
-        const size_t o_plo = carve((size_t)slot_blocks * 4), o_phi = carve((size_t)slot_blocks * 4);
-        const size_t o_blo = carve((size_t)slot_blocks * 4), o_bhi = carve((size_t)slot_blocks * 4);
-        const size_t o_rin = carve((size_t)slot_blocks);
-        const size_t o_rdin = carve((size_t)rec_entries * 8 + 8), o_rgain = carve((size_t)rec_entries * 8 + 8);
-        const size_t o_rd = carve((size_t)rec_entries * 4 + 8), o_rv = carve((size_t)rec_entries * 4 + 8);
-        const size_t o_rf = carve((size_t)rec_entries + 8);
-        const size_t o_rgs = carve((size_t)rec_groups * 8 + 8), o_rgo = carve((size_t)rec_groups + 8);
-        const size_t o_ss = carve(T * sizeof(int));
-        const size_t o_res = carve(S * sizeof(FastSlotResult));
-        if ((rc = solver_->dev_params.reserve(off)) != ROCCO_HIP_OK) return rc;
+        // ---- scratch ----
+        Layout scratch;
+        const size_t o_agg_a = scratch.at((size_t)chain_chunks * 8), o_agg_lo = scratch.at((size_t)chain_chunks * 8),
+                     o_agg_hi = scratch.at((size_t)chain_chunks * 8), o_pstar = scratch.at((size_t)chain_chunks);
+        const size_t o_blk_a = scratch.at((size_t)chain_blocks * 8), o_blk_lo = scratch.at((size_t)chain_blocks * 8),
+                     o_blk_hi = scratch.at((size_t)chain_blocks * 8), o_din = scratch.at((size_t)chain_blocks * 8);
+        const size_t o_lcc = scratch.at((size_t)slot_chunks);
+        const size_t o_wc = scratch.at((size_t)slot_chunks * 8), o_gc = scratch.at(any_map ? (size_t)slot_chunks * 8 : 8);
+        const size_t o_lcb = scratch.at((size_t)slot_blocks * 4), o_lcin = scratch.at((size_t)slot_blocks * 4);
+        const size_t o_wb = scratch.at((size_t)slot_blocks * 8), o_winb = scratch.at((size_t)slot_blocks * 8);
+        const size_t o_gb = scratch.at((size_t)slot_blocks * 8), o_ginb = scratch.at((size_t)slot_blocks * 8);
+        const size_t o_fvlo = scratch.at((size_t)slot_blocks), o_fvhi = scratch.at((size_t)slot_blocks);
+        const size_t o_plo = scratch.at((size_t)slot_blocks * 4), o_phi = scratch.at((size_t)slot_blocks * 4);
+        const size_t o_blo = scratch.at((size_t)slot_blocks * 4), o_bhi = scratch.at((size_t)slot_blocks * 4);
+        const size_t o_rin = scratch.at((size_t)slot_blocks);
+        const size_t o_rdin = scratch.at((size_t)rec_entries * 8 + 8), o_rgain = scratch.at((size_t)rec_entries * 8 + 8);
+        const size_t o_rd = scratch.at((size_t)rec_entries * 4 + 8), o_rv = scratch.at((size_t)rec_entries * 4 + 8);
+        const size_t o_rf = scratch.at((size_t)rec_entries + 8);
+        const size_t o_rgs = scratch.at((size_t)rec_groups * 8 + 8), o_rgo = scratch.at((size_t)rec_groups + 8);
+        const size_t o_ss = scratch.at(T * sizeof(int));
+        const size_t o_res = scratch.at(S * sizeof(FastSlotResult));
+        if ((rc = solver_->dev_params.reserve(scratch.bytes())) != ROCCO_HIP_OK) return rc;
         char *sc = (char *)solver_->dev_params.ptr;
 
         FastLaunch L;
-        L.tasks = (const FastTask *)dd;
-        L.chains = (const FastChain *)(dd + b_tasks);
-        L.slots = (const FastSlot *)(dd + b_tasks + b_chains);
-        L.blockmap = (const int2 *)(dd + b_tasks + b_chains + b_slots);
+        L.tasks = (const FastTask *)(dd + d_tasks);
+        L.chains = (const FastChain *)(dd + d_chains);
+        L.slots = (const FastSlot *)(dd + d_slots);
+        L.blockmap = (const int2 *)(dd + d_map);
         L.n_tasks = (int)T;
         L.n_chains = (int)C;
         L.n_slots = (int)S;
-        L.blockmap_all = (const int2 *)(dd + b_tasks + b_chains + b_slots + b_map);
+        L.blockmap_all = (const int2 *)(dd + d_mapall);
         L.n_blocks_total = (int)NB;
         L.n_blocks_all = (int)NBA;
         {
@@ -3051,8 +2788,7 @@ private:
             for (size_t t = 0; t < T; ++t) {
                 only_maps = only_maps && rt[t].map;
             }
-            const char *defer = env("ROCCO_HIP_DEFER_MAPS");
-            if (may_defer && only_maps && (defer == nullptr || std::atoi(defer) != 0)) {
+            if (may_defer && only_maps && env_flag("ROCCO_HIP_DEFER_MAPS", true)) {
                 // nothing of a map round is read on the host (adopt_maps only takes the pointers over)
                 t_launch_ += now_us() - tt1;
                 return stage_mark();
@@ -3102,7 +2838,7 @@ private:
             for (int k = 0; k < tasks[t].slot_count; ++k) {
                 if (hr[tasks[t].slot_begin + k].overflow) {
                     // a lane was still stepping when it reached a block that was not evaluated
-                    if (env("ROCCO_HIP_DEBUG") != nullptr) {
+                    if (env_set("ROCCO_HIP_DEBUG")) {
                         std::fprintf(stderr, "[spine] problem %zu: repeated in full\n", rt[t].problem);
                     }
                     no_frozen_ = true;
@@ -3141,7 +2877,7 @@ private:
                     }
                 }
                 p.active_blocks.swap(active);
-                if (env("ROCCO_HIP_DEBUG") != nullptr) {
+                if (env_set("ROCCO_HIP_DEBUG")) {
                     std::fprintf(stderr, "[survey] problem %zu: bracket [%.17g, %.17g] width %.3g active %zu / %d blocks\n",
                                  rt[t].problem, rt[t].lambdas[0], rt[t].lambdas[1],
                                  rt[t].lambdas[1] - rt[t].lambdas[0], p.active_blocks.size(), nb);
@@ -3167,7 +2903,7 @@ private:
                     rt[t].spine->stepped[k] = hr[ft.slot_begin + k].uncertain;
                 }
                 rt[t].spine->selected = (ft.sel_depth > 0) ? hr[ft.slot_begin].e_global : -1;
-                if (env("ROCCO_HIP_DEBUG") != nullptr) {
+                if (env_set("ROCCO_HIP_DEBUG")) {
                     std::fprintf(stderr, "[spine] problem %zu: lane 0 stepped %lld chunks of %lld\n", rt[t].problem,
                                  (long long)hr[ft.slot_begin].uncertain, (long long)((p.n + kChunk - 1) / kChunk));
                     std::fprintf(stderr, "[spine] prof (100 MHz ticks): fetch %lld loop %lld (steps %lld) slow groups %lld\n",
@@ -3276,6 +3012,33 @@ int prepare(HipEvaluator &ev, std::vector<ChainProblem> &problems, const std::ve
     return ROCCO_HIP_OK;
 }
 
+// One problem on an evaluator of its own: the set-up every single-problem entry point shares.
+struct SingleProblem {
+    HipEvaluator ev;
+    std::vector<ChainProblem> problems;
+    SingleProblem(rocco_hip_solver *solver, hipStream_t stream, const double *scores_dev, const double *switch_costs_dev, double gamma,
+                  size_t n, uint8_t *solution_dev = nullptr)
+        : ev(solver, stream), problems(1)
+    {
+        DevProblem d;
+        d.scores = scores_dev;
+        d.costs = (n > 1) ? switch_costs_dev : nullptr;
+        d.gamma = gamma;
+        d.n = n;
+        d.solution = solution_dev;
+        ev.probs.push_back(d);
+        problems[0].n = n;
+        problems[0].gamma = gamma;
+    }
+    // statistics and grid of the problem; `emap_dev`: a binade map the caller brings
+    int prepare_problem(const std::vector<double> *fixed_lambdas = nullptr, const uint8_t *emap_dev = nullptr)
+    {
+        const int rc = prepare(ev, problems, fixed_lambdas);
+        ev.probs[0].emap = const_cast<uint8_t *>(emap_dev);
+        return rc;
+    }
+};
+
 }  // namespace
 
 void model_chain_counters(long long out[4])
@@ -3296,25 +3059,16 @@ int solve_fixed_penalty(rocco_hip_solver *solver, const double *scores_dev,
                         uint8_t *solution_dev, double *value_out, long long *count_out, int *path_out,
                         hipStream_t stream)
 {
-    HipEvaluator ev(solver, stream);
-    DevProblem d;
-    d.scores = scores_dev;
-    d.costs = (n > 1) ? switch_costs_dev : nullptr;
-    d.gamma = gamma;
-    d.n = n;
     int rc;
     if (solution_dev == nullptr) {  // the fast path always materialises; give it scratch
         if ((rc = solver->dev_solution.reserve(n)) != ROCCO_HIP_OK) return rc;
-        d.solution = (uint8_t *)solver->dev_solution.ptr;
-    } else {
-        d.solution = solution_dev;
+        solution_dev = (uint8_t *)solver->dev_solution.ptr;
     }
-    ev.probs.push_back(d);
-    std::vector<ChainProblem> problems(1);
-    problems[0].n = n;
-    problems[0].gamma = gamma;
+    SingleProblem one(solver, stream, scores_dev, switch_costs_dev, gamma, n, solution_dev);
+    HipEvaluator &ev = one.ev;
+    std::vector<ChainProblem> &problems = one.problems;
     std::vector<double> lambdas = {lambda};
-    if ((rc = prepare(ev, problems, &lambdas)) != ROCCO_HIP_OK) return rc;
+    if ((rc = one.prepare_problem(&lambdas)) != ROCCO_HIP_OK) return rc;
     SearchOptions opt;
     opt.force_exact = solver->force_exact != 0;
     std::vector<CalibrationResult> res;
@@ -3329,18 +3083,10 @@ int delta_build_map(rocco_hip_solver *solver, const double *scores_dev, const do
                     double gamma, size_t n, double lambda_ref, double margin, uint8_t *emap_dev,
                     hipStream_t stream)
 {
-    HipEvaluator ev(solver, stream);
-    DevProblem d;
-    d.scores = scores_dev;
-    d.costs = (n > 1) ? switch_costs_dev : nullptr;
-    d.gamma = gamma;
-    d.n = n;
-    ev.probs.push_back(d);
-    std::vector<ChainProblem> problems(1);
-    problems[0].n = n;
-    problems[0].gamma = gamma;
+    SingleProblem one(solver, stream, scores_dev, switch_costs_dev, gamma, n);
+    HipEvaluator &ev = one.ev;
     int rc;
-    if ((rc = prepare(ev, problems, nullptr)) != ROCCO_HIP_OK) return rc;
+    if ((rc = one.prepare_problem()) != ROCCO_HIP_OK) return rc;
     std::vector<MapRequest> reqs(1);
     reqs[0].problem = 0;
     reqs[0].lambda_ref = lambda_ref;
@@ -3354,18 +3100,10 @@ int delta_build_map(rocco_hip_solver *solver, const double *scores_dev, const do
 int delta_build_map_lean(rocco_hip_solver *solver, const double *scores_dev, double gamma, size_t n, double lambda_ref,
                          double margin, uint8_t *emap_dev, hipStream_t stream)
 {
-    HipEvaluator ev(solver, stream);
-    DevProblem d;
-    d.scores = scores_dev;
-    d.costs = nullptr;
-    d.gamma = gamma;
-    d.n = n;
-    ev.probs.push_back(d);
-    std::vector<ChainProblem> problems(1);
-    problems[0].n = n;
-    problems[0].gamma = gamma;
+    SingleProblem one(solver, stream, scores_dev, nullptr, gamma, n);
+    HipEvaluator &ev = one.ev;
     int rc;
-    if ((rc = prepare(ev, problems, nullptr)) != ROCCO_HIP_OK) return rc;
+    if ((rc = one.prepare_problem()) != ROCCO_HIP_OK) return rc;
     ev.force_lean_map_ = true;
     if (!ev.lean_map_takes(0)) {
         set_last_error("lean map: not available for this array (lean evaluation off, or fewer than two loci)");
@@ -3385,20 +3123,10 @@ int delta_spine(rocco_hip_solver *solver, const double *scores_dev, const double
                 double gamma, size_t n, const uint8_t *emap_dev, const double *lambdas, size_t n_lambdas,
                 int solution_index, uint8_t *solution_dev, long long *counts_out, hipStream_t stream)
 {
-    HipEvaluator ev(solver, stream);
-    DevProblem d;
-    d.scores = scores_dev;
-    d.costs = (n > 1) ? switch_costs_dev : nullptr;
-    d.gamma = gamma;
-    d.n = n;
-    d.solution = solution_dev;
-    ev.probs.push_back(d);
-    std::vector<ChainProblem> problems(1);
-    problems[0].n = n;
-    problems[0].gamma = gamma;
+    SingleProblem one(solver, stream, scores_dev, switch_costs_dev, gamma, n, solution_dev);
+    HipEvaluator &ev = one.ev;
     int rc;
-    if ((rc = prepare(ev, problems, nullptr)) != ROCCO_HIP_OK) return rc;
-    ev.probs[0].emap = const_cast<uint8_t *>(emap_dev);
+    if ((rc = one.prepare_problem(nullptr, emap_dev)) != ROCCO_HIP_OK) return rc;
     std::vector<SpineRequest> reqs(1);
     reqs[0].problem = 0;
     reqs[0].lambdas.assign(lambdas, lambdas + n_lambdas);
@@ -3407,7 +3135,7 @@ int delta_spine(rocco_hip_solver *solver, const double *scores_dev, const double
     for (size_t i = 0; i < n_lambdas; ++i) {
         counts_out[i] = reqs[0].counts[i];
     }
-    if (getenv("ROCCO_HIP_DEBUG") != nullptr) {
+    if (ev.env_set("ROCCO_HIP_DEBUG")) {
         fprintf(stderr, "[rocco_hip] spine: n=%zu chunks=%zu stepped[0]=%lld\n", n, (n + 31) / 32, reqs[0].stepped[0]);
     }
     return ROCCO_HIP_OK;
@@ -3417,19 +3145,10 @@ int delta_probe(rocco_hip_solver *solver, const double *scores_dev, const double
                 double gamma, size_t n, const uint8_t *emap_dev, const double *lambdas, size_t n_lambdas,
                 rocco_hip_probe_stats *stats_out, hipStream_t stream)
 {
-    HipEvaluator ev(solver, stream);
-    DevProblem d;
-    d.scores = scores_dev;
-    d.costs = (n > 1) ? switch_costs_dev : nullptr;
-    d.gamma = gamma;
-    d.n = n;
-    ev.probs.push_back(d);
-    std::vector<ChainProblem> problems(1);
-    problems[0].n = n;
-    problems[0].gamma = gamma;
+    SingleProblem one(solver, stream, scores_dev, switch_costs_dev, gamma, n);
+    HipEvaluator &ev = one.ev;
     int rc;
-    if ((rc = prepare(ev, problems, nullptr)) != ROCCO_HIP_OK) return rc;
-    ev.probs[0].emap = const_cast<uint8_t *>(emap_dev);
+    if ((rc = one.prepare_problem(nullptr, emap_dev)) != ROCCO_HIP_OK) return rc;
     std::vector<ProbeRequest> reqs(1);
     reqs[0].problem = 0;
     reqs[0].lambdas.assign(lambdas, lambdas + n_lambdas);
@@ -3446,19 +3165,10 @@ int delta_probe(rocco_hip_solver *solver, const double *scores_dev, const double
 int delta_model_lean(rocco_hip_solver *solver, const double *scores_dev, double gamma, size_t n, const uint8_t *emap_dev,
                      const double *lambdas, size_t n_lambdas, long long *counts_out, long long *open_out, hipStream_t stream)
 {
-    HipEvaluator ev(solver, stream);
-    DevProblem d;
-    d.scores = scores_dev;
-    d.costs = nullptr;
-    d.gamma = gamma;
-    d.n = n;
-    ev.probs.push_back(d);
-    std::vector<ChainProblem> problems(1);
-    problems[0].n = n;
-    problems[0].gamma = gamma;
+    SingleProblem one(solver, stream, scores_dev, nullptr, gamma, n);
+    HipEvaluator &ev = one.ev;
     int rc;
-    if ((rc = prepare(ev, problems, nullptr)) != ROCCO_HIP_OK) return rc;
-    ev.probs[0].emap = const_cast<uint8_t *>(emap_dev);
+    if ((rc = one.prepare_problem(nullptr, emap_dev)) != ROCCO_HIP_OK) return rc;
     ev.probs[0].map_version = 1;
     if ((rc = ev.lean_prepare()) != ROCCO_HIP_OK) return rc;
     ev.model_any_ = true;
@@ -3484,18 +3194,10 @@ int delta_bound_rounds(rocco_hip_solver *solver, const double *scores_dev, doubl
                        const double *lambdas, const int *round_sizes, int n_rounds, double *lambdas_used_out,
                        long long *counts_out, long long *level_len_out, hipStream_t stream)
 {
-    HipEvaluator ev(solver, stream);
-    DevProblem d;
-    d.scores = scores_dev;
-    d.costs = nullptr;
-    d.gamma = gamma;
-    d.n = n;
-    ev.probs.push_back(d);
-    std::vector<ChainProblem> problems(1);
-    problems[0].n = n;
-    problems[0].gamma = gamma;
+    SingleProblem one(solver, stream, scores_dev, nullptr, gamma, n);
+    HipEvaluator &ev = one.ev;
     int rc;
-    if ((rc = prepare(ev, problems, nullptr)) != ROCCO_HIP_OK) return rc;
+    if ((rc = one.prepare_problem()) != ROCCO_HIP_OK) return rc;
     if (!ev.lean_eligible(0)) {
         set_last_error("rocco_hip_delta_bound_rounds_f64: the lean evaluation is switched off for this solver");
         return ROCCO_HIP_EINVAL;
@@ -3528,20 +3230,10 @@ int delta_window(rocco_hip_solver *solver, const double *scores_dev, const doubl
                  double gamma, size_t n, const uint8_t *emap_dev, double lambda_lo, double lambda_hi,
                  uint8_t *solution_dev, rocco_hip_window_stats *stats_out, hipStream_t stream)
 {
-    HipEvaluator ev(solver, stream);
-    DevProblem d;
-    d.scores = scores_dev;
-    d.costs = (n > 1) ? switch_costs_dev : nullptr;
-    d.gamma = gamma;
-    d.n = n;
-    d.solution = solution_dev;
-    ev.probs.push_back(d);
-    std::vector<ChainProblem> problems(1);
-    problems[0].n = n;
-    problems[0].gamma = gamma;
+    SingleProblem one(solver, stream, scores_dev, switch_costs_dev, gamma, n, solution_dev);
+    HipEvaluator &ev = one.ev;
     int rc;
-    if ((rc = prepare(ev, problems, nullptr)) != ROCCO_HIP_OK) return rc;
-    ev.probs[0].emap = const_cast<uint8_t *>(emap_dev);
+    if ((rc = one.prepare_problem(nullptr, emap_dev)) != ROCCO_HIP_OK) return rc;
     std::vector<WindowRequest> reqs(1);
     reqs[0].problem = 0;
     reqs[0].lambda_lo = lambda_lo;
@@ -3595,40 +3287,31 @@ int solve_budget_batch(rocco_hip_solver *solver, size_t n_tasks, const rocco_hip
     SearchOptions opt;
     opt.force_exact = solver->force_exact != 0;
     opt.spec_depth = solver->spec_depth;
-    if (const char *e = std::getenv("ROCCO_HIP_BIG_ROUND")) opt.big_round_loci = std::atof(e);
-    if (const char *e = std::getenv("ROCCO_HIP_SMALL_ROUND")) opt.small_round_loci = std::atof(e);
-    if (const char *e = std::getenv("ROCCO_HIP_SURVEY_GATE")) opt.survey_gate = std::atof(e);
-    if (const char *e = std::getenv("ROCCO_HIP_TINY_ROUND")) opt.tiny_round_loci = std::atof(e);
-    if (const char *e = std::getenv("ROCCO_HIP_MAP_REBUILD")) opt.map_rebuild_ratio = std::atof(e);
-    if (const char *e = std::getenv("ROCCO_HIP_BOUNDS")) opt.use_bounds = std::atoi(e) != 0;
-    if (const char *e = std::getenv("ROCCO_HIP_SEARCH_GATE")) opt.search_gate = std::atof(e);
-    if (const char *e = std::getenv("ROCCO_HIP_SEARCH_POINTS")) opt.search_points = std::max(1, std::atoi(e));
-    if (const char *e = std::getenv("ROCCO_HIP_SEARCH_INTERP")) opt.search_interpolate = std::atoi(e) != 0;
+    opt.big_round_loci = ev.env_double("ROCCO_HIP_BIG_ROUND", opt.big_round_loci);
+    opt.small_round_loci = ev.env_double("ROCCO_HIP_SMALL_ROUND", opt.small_round_loci);
+    opt.survey_gate = ev.env_double("ROCCO_HIP_SURVEY_GATE", opt.survey_gate);
+    opt.tiny_round_loci = ev.env_double("ROCCO_HIP_TINY_ROUND", opt.tiny_round_loci);
+    opt.map_rebuild_ratio = ev.env_double("ROCCO_HIP_MAP_REBUILD", opt.map_rebuild_ratio);
+    opt.use_bounds = ev.env_flag("ROCCO_HIP_BOUNDS", opt.use_bounds);
+    opt.search_gate = ev.env_double("ROCCO_HIP_SEARCH_GATE", opt.search_gate);
+    if (ev.env_set("ROCCO_HIP_SEARCH_POINTS")) opt.search_points = std::max(1, ev.env_int("ROCCO_HIP_SEARCH_POINTS", 0));
+    opt.search_interpolate = ev.env_flag("ROCCO_HIP_SEARCH_INTERP", opt.search_interpolate);
     std::vector<CalibrationResult> res;
     const double t_solve0 = HipEvaluator::now_us();
-    ev.marks_on_ = std::getenv("ROCCO_HIP_TIMING") != nullptr && std::atoi(std::getenv("ROCCO_HIP_TIMING")) >= 2;
+    ev.marks_on_ = ev.env_int("ROCCO_HIP_TIMING", 0) >= 2;
     ev.mark("solve begins");
-    if (const char *e = std::getenv("ROCCO_HIP_COMPACT")) opt.use_compaction = std::atoi(e) != 0;
-    if (const char *e = std::getenv("ROCCO_HIP_PILOT_ROUNDS")) opt.pilot_rounds = std::atoi(e);
-    if (const char *e = std::getenv("ROCCO_HIP_PILOT_POINTS")) opt.pilot_points = std::atoi(e);
-    if (const char *e = std::getenv("ROCCO_HIP_ALIGN_MAPS")) opt.align_maps = std::atoi(e) != 0;
-    if (const char *e = std::getenv("ROCCO_HIP_ALIGN_WINDOWS")) opt.align_windows = std::atoi(e) != 0;
-    if (const char *e = std::getenv("ROCCO_HIP_PILOT_LEVELS")) {  // comma list, e.g. "2.2" or "2.2,1.0"
-        opt.pilot_levels.clear();
-        for (const char *q = e; *q != '\0';) {
-            char *end = nullptr;
-            const double v = std::strtod(q, &end);
-            if (end == q) break;
-            if (v > 0.0) opt.pilot_levels.push_back(v);
-            q = (*end == ',') ? end + 1 : end;
-        }
-    }
+    opt.use_compaction = ev.env_flag("ROCCO_HIP_COMPACT", opt.use_compaction);
+    opt.pilot_rounds = ev.env_int("ROCCO_HIP_PILOT_ROUNDS", opt.pilot_rounds);
+    opt.pilot_points = ev.env_int("ROCCO_HIP_PILOT_POINTS", opt.pilot_points);
+    opt.align_maps = ev.env_flag("ROCCO_HIP_ALIGN_MAPS", opt.align_maps);
+    opt.align_windows = ev.env_flag("ROCCO_HIP_ALIGN_WINDOWS", opt.align_windows);
+    ev.env_list("ROCCO_HIP_PILOT_LEVELS", opt.pilot_levels);
     struct LeanOverride {  // ROCCO_HIP_LEAN overrides the solver's setting for this call only
         rocco_hip_solver *solver;
         int saved;
         ~LeanOverride() { solver->lean = saved; }
     } lean_override{solver, solver->lean};
-    if (const char *e = std::getenv("ROCCO_HIP_LEAN")) solver->lean = std::atoi(e) != 0;
+    if (ev.env_set("ROCCO_HIP_LEAN")) solver->lean = ev.env_flag("ROCCO_HIP_LEAN", true) ? 1 : 0;
     // the threshold search of every eligible problem as one chain of launches behind the statistics pass (chain.h); what
     // it leaves open the host-sequenced rounds of calibrate_batch finish
     std::vector<double> chain_stats;
@@ -3653,7 +3336,7 @@ int solve_budget_batch(rocco_hip_solver *solver, size_t n_tasks, const rocco_hip
     g_model_chain_counters[3].fetch_add(ev.model_chain_misses, std::memory_order_relaxed);
     g_model_chain_counters[4].fetch_add(ev.model_chain_written, std::memory_order_relaxed);
     g_model_chain_counters[5].fetch_add(ev.model_chain_windows_answered, std::memory_order_relaxed);
-    if (std::getenv("ROCCO_HIP_DEBUG") != nullptr || std::getenv("ROCCO_HIP_TIMING") != nullptr) {
+    if (ev.env_set("ROCCO_HIP_DEBUG") || ev.env_set("ROCCO_HIP_TIMING")) {
         const double total = HipEvaluator::now_us() - t_solve0;
         std::fprintf(stderr, "[host] solve %.0f us: %d rounds (%d with rounding-model kernels): in the rounds %.0f us = waiting for the device %.0f "
                              "+ reading results %.0f + preparing and submitting %.0f; search logic and the rest %.0f us\n",

@@ -12,6 +12,8 @@
 #include "../../include/rocco_hip.h"
 #include "../../oracle/oracle.h"
 #include "../../rocco_amd/csrc/search.h"
+#include "../../rocco_amd/csrc/chain.h"
+#include "../../rocco_amd/csrc/lean_tasks.h"
 
 using namespace rocco;
 
@@ -464,5 +466,39 @@ int hostlogic_solve_fixed(const double *scores, const double *costs, double gamm
     out_i[0] = res[0].path;
     out_i[4] = res[0].n_diff;
     return 0;
+}
+
+// The three buffers of a chain of rounding-model rounds as the product lays them out (csrc/lean_tasks.h: model_chain_layout,
+// the function budget.hip calls).  `limits`: kChainMaxProblems, kModelChainMaxProblems, kModelChainMaxRounds, kLeanMaxPoints.
+// Per region, in the documented order, its offset and the bytes it has to hold (elements x sizeof, worked out here):
+// 12 regions of the device buffer (the first 3 are the pinned upload), 4 of the host-coherent buffer.  `totals`: bytes of the
+// device buffer, of the upload, of the host-coherent buffer.
+void hostlogic_model_chain_layout(long long B, long long n_wcap, int rounds, long long cap_pairs, int *limits, long long *dev_offsets,
+                                  long long *dev_needs, long long *follow_offsets, long long *follow_needs, long long *totals)
+{
+    limits[0] = kChainMaxProblems;
+    limits[1] = kModelChainMaxProblems;
+    limits[2] = kModelChainMaxRounds;
+    limits[3] = kLeanMaxPoints;
+    const ModelChainLayout m = model_chain_layout((size_t)B, (size_t)n_wcap, rounds, cap_pairs);
+    const size_t b = (size_t)B, r = (size_t)rounds, c = (size_t)cap_pairs, pts = (size_t)kLeanMaxPoints;
+    const size_t dev_off[12] = {m.tasks, m.walk, m.wcap, m.state, m.points, m.results, m.ctl, m.globals, m.writes, m.n_writes, m.entering, m.bits};
+    const size_t dev_need[12] = {b * sizeof(LeanTask), b * sizeof(ModelChainWalk), (size_t)n_wcap * sizeof(LeanWcapTask),
+                                 b * sizeof(ModelChainState), b * pts * sizeof(double), b * pts * sizeof(LeanResult),
+                                 sizeof(LeanRoundCtl), 3 * sizeof(int), b * sizeof(LeanWriteTask), sizeof(int),
+                                 r * c * sizeof(unsigned), r * c * 2 * 256 * sizeof(unsigned)};
+    const size_t fol_off[4] = {m.report, m.n_points, m.finals, m.facts};
+    const size_t fol_need[4] = {sizeof(ModelChainReport), r * b * sizeof(int), b * sizeof(ModelChainFinal), r * b * pts * sizeof(ModelChainFact)};
+    for (int k = 0; k < 12; ++k) {
+        dev_offsets[k] = (long long)dev_off[k];
+        dev_needs[k] = (long long)dev_need[k];
+    }
+    for (int k = 0; k < 4; ++k) {
+        follow_offsets[k] = (long long)fol_off[k];
+        follow_needs[k] = (long long)fol_need[k];
+    }
+    totals[0] = (long long)m.dev_bytes;
+    totals[1] = (long long)m.up_bytes;
+    totals[2] = (long long)m.follow_bytes;
 }
 }

@@ -18,6 +18,25 @@ int hostlogic_calibrate(const double *scores, const double *costs, double gamma,
                         long long *count_out, long long *out_i);
 int hostlogic_solve_fixed(const double *scores, const double *costs, double gamma, size_t n, double lambda, uint8_t *solution,
                           double *value_out, long long *count_out, long long *out_i);
+void hostlogic_model_chain_layout(long long B, long long n_wcap, int rounds, long long cap_pairs, int *limits, long long *dev_offsets,
+                                  long long *dev_needs, long long *follow_offsets, long long *follow_needs, long long *totals);
+}
+
+// the buffers of a chain of rounding-model rounds: every region starts where the one before ends, on a multiple of 256, and
+// holds what it has to (tests/test_host_logic.py checks the same shapes, and the middle one against literal offsets)
+static int layout_faults(long long B, long long n_wcap, int rounds, long long cap_pairs)
+{
+    int limits[4];
+    long long off[16], need[16], totals[3];
+    hostlogic_model_chain_layout(B, n_wcap, rounds, cap_pairs, limits, off, need, off + 12, need + 12, totals);
+    int bad = 0;
+    for (int k = 0; k < 16; ++k) {
+        const bool last = (k == 11 || k == 15);
+        const long long end = last ? totals[k == 11 ? 0 : 2] : off[k + 1];
+        const long long begin_want = (k == 0 || k == 12) ? 0 : off[k - 1] + (need[k - 1] + 255) / 256 * 256;
+        bad += (off[k] % 256 != 0) + (off[k] != begin_want) + (end - off[k] < need[k]);
+    }
+    return bad + (totals[1] != off[3]);
 }
 
 static uint64_t state = 0x9E3779B97F4A7C15ULL;
@@ -117,5 +136,10 @@ int main(int argc, char **argv)
         }
     }
     std::printf("%d cases, %d mismatches\n", cases, bad);
-    return bad == 0 ? 0 : 1;
+    int limits[4];
+    long long off[16], need[16], totals[3];
+    hostlogic_model_chain_layout(1, 0, 1, 0, limits, off, need, off + 12, need + 12, totals);
+    const int layout_bad = layout_faults(1, 0, 1, 0) + layout_faults(1, 1, 3, 2048) + layout_faults(limits[0], limits[0], limits[2], 32768);
+    std::printf("3 layouts, %d faults\n", layout_bad);
+    return (bad == 0 && layout_bad == 0) ? 0 : 1;
 }

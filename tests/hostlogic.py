@@ -25,6 +25,10 @@ def lib():
             dp, dp, ctypes.c_double, ctypes.c_size_t, ctypes.c_double,
             ctypes.POINTER(ctypes.c_uint8), dp, ctypes.POINTER(ctypes.c_longlong),
             ctypes.POINTER(ctypes.c_longlong)]
+        llp = ctypes.POINTER(ctypes.c_longlong)
+        _lib.hostlogic_model_chain_layout.restype = None
+        _lib.hostlogic_model_chain_layout.argtypes = [
+            ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int), llp, llp, llp, llp, llp]
     return _lib
 
 
@@ -71,3 +75,23 @@ def solve_fixed(scores, gamma_or_costs, lam):
                                      ctypes.byref(cnt), info)
     assert rc == 0, rc
     return sol, val.value, cnt.value, {"path": int(info[0]), "n_diff": int(info[4])}
+
+
+MODEL_CHAIN_DEVICE_REGIONS = ["tasks", "walk", "wcap", "state", "points", "results", "ctl", "globals", "writes", "n_writes", "entering", "bits"]
+MODEL_CHAIN_FOLLOW_REGIONS = ["report", "n_points", "finals", "facts"]
+
+
+def model_chain_layout(B, n_wcap, rounds, cap_pairs):
+    """The buffers of a chain of rounding-model rounds as csrc/lean_tasks.h lays them out: per buffer a list of
+    (region, offset, bytes the region must hold) in the documented order, the totals, and the product's limits."""
+    limits = (ctypes.c_int * 4)()
+    dev_off, dev_need = (ctypes.c_longlong * 12)(), (ctypes.c_longlong * 12)()
+    fol_off, fol_need = (ctypes.c_longlong * 4)(), (ctypes.c_longlong * 4)()
+    totals = (ctypes.c_longlong * 3)()
+    lib().hostlogic_model_chain_layout(int(B), int(n_wcap), int(rounds), int(cap_pairs), limits, dev_off, dev_need, fol_off, fol_need, totals)
+    return {
+        "device": list(zip(MODEL_CHAIN_DEVICE_REGIONS, dev_off, dev_need)),
+        "follow": list(zip(MODEL_CHAIN_FOLLOW_REGIONS, fol_off, fol_need)),
+        "device_bytes": totals[0], "upload_bytes": totals[1], "follow_bytes": totals[2],
+        "limits": dict(zip(["chain_max_problems", "model_chain_max_problems", "model_chain_max_rounds", "lean_max_points"], limits)),
+    }

@@ -205,7 +205,8 @@ def test_host_logic_under_address_and_undefined_behaviour_sanitizers():
     """The product's search.cpp (1 400 lines of index-heavy host logic with prefetches ahead of the problem being planned) in
     ONE executable with the harness, the oracle's C sources and a driver, all compiled with -fsanitize=address,undefined
     (tests/host_logic/san_driver.cpp): 160 random calibrations + 320 fixed-penalty solves over six kinds of score arrays
-    and eight imitated device-side behaviours, each compared with the oracle's sequential calibration.  Exit code 0 and an
+    and eight imitated device-side behaviours, each compared with the oracle's sequential calibration, then the buffer
+    layouts of test_model_chain_buffer_layouts (a fault there also makes the exit code 1).  Exit code 0 and an
     empty sanitizer log (CPU only: the pool has no GPU sanitizers)."""
     import os
     import subprocess
@@ -217,6 +218,63 @@ def test_host_logic_under_address_and_undefined_behaviour_sanitizers():
     assert run.returncode == 0, run.stdout + run.stderr
     assert "160 cases, 0 mismatches" in run.stdout
     assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr
+
+
+def _check_layout_regions(regions, total, where):
+    """`regions`: (name, offset, bytes it must hold) in the documented order.  Every region starts on a multiple of 256 where
+    the one before ends, is as long as what it holds rounded up to 256 (so an empty one has length zero and none overlaps
+    another), and the buffer ends with the last."""
+    at = 0
+    for k, (name, off, need) in enumerate(regions):
+        end = regions[k + 1][1] if k + 1 < len(regions) else total
+        assert off % 256 == 0, (where, name, off)
+        assert off == at, (where, name, off, at)  # documented order, no gap, no overlap
+        assert end - off == (need + 255) // 256 * 256, (where, name, off, end, need)
+        if need == 0:
+            assert end == off, (where, name)
+        at = end
+    assert at == total, (where, at, total)
+
+
+def test_model_chain_buffer_layouts():
+    """The device buffer, the pinned upload and the host-coherent buffer of a chain of rounding-model rounds
+    (csrc/lean_tasks.h: model_chain_layout, the function csrc/budget.hip calls): an overlap of two scratch regions may still
+    give right answers on small inputs, so the offsets are checked here, and at one shape against literal numbers."""
+    lim = hl.model_chain_layout(1, 0, 1, 0)["limits"]
+    assert lim["lean_max_points"] == 64
+    shapes = [(1, 0, 1, 0), (1, 1, 3, 2048), (lim["chain_max_problems"], lim["chain_max_problems"], lim["model_chain_max_rounds"], 32768)]
+    for B, n_wcap, rounds, cap_pairs in shapes:
+        lay = hl.model_chain_layout(B, n_wcap, rounds, cap_pairs)
+        where = (B, n_wcap, rounds, cap_pairs)
+        _check_layout_regions(lay["device"], lay["device_bytes"], where)
+        _check_layout_regions(lay["follow"], lay["follow_bytes"], where)
+        # the upload is the device buffer's prefix [tasks][walk][wcap tasks]: it ends where `state` begins
+        assert lay["upload_bytes"] == lay["device"][3][1], where
+    first = hl.model_chain_layout(*shapes[0])
+    sizes = {name: need for name, _off, need in first["device"]}
+    assert sizes["wcap"] == 0 and sizes["entering"] == 0 and sizes["bits"] == 0
+    # B = 1, one wcap task, 3 rounds, cap_pairs = 2048, by hand from the sums the evaluator used to spell out
+    # (up(x) = x rounded up to 256; LeanTask and ModelChainWalk 144 bytes, LeanWcapTask 64, ModelChainState 88, LeanResult 24,
+    # LeanWriteTask 48, ModelChainFinal 32, ModelChainFact 24, 64 penalties per problem and round):
+    #   b_tasks = up(144) = 256, b_walk = up(144) = 256, b_wcap = up(64) = 256           -> up_bytes = 768
+    #   state   at up_bytes = 768,                      b_state   = up(88)      = 256
+    #   points  at 768 + 256 = 1024,                    b_points  = up(64 * 8)  = 512
+    #   results at 1024 + 512 = 1536,                   b_results = up(64 * 24) = 1536
+    #   ctl     at 1536 + 1536 = 3072, globals at ctl + 256 = 3328 (one 512-byte region)
+    #   writes  at 3072 + 512 = 3584,                   b_writes  = up(48) = 256
+    #   n_writes at 3584 + 256 = 3840 (a 256-byte slot)
+    #   entering at 3840 + 256 = 4096,                  b_enter = up(3 * 2048 * 4) = 24576
+    #   bits    at 4096 + 24576 = 28672,                b_bits  = 3 * 2048 * 2 * 256 * 4 = 12582912
+    #   dev_bytes = 28672 + 12582912 = 12611584
+    #   host-coherent: report at 0 (256 bytes), n_points at 256 with up(3 * 1 * 4) = 256, finals at 512 with up(32) = 256,
+    #   facts at 768 with 3 * 1 * 64 * 24 = 4608 -> follow_bytes = 5376
+    middle = hl.model_chain_layout(*shapes[1])
+    assert [(name, off) for name, off, _need in middle["device"]] == [
+        ("tasks", 0), ("walk", 256), ("wcap", 512), ("state", 768), ("points", 1024), ("results", 1536), ("ctl", 3072),
+        ("globals", 3328), ("writes", 3584), ("n_writes", 3840), ("entering", 4096), ("bits", 28672)]
+    assert middle["upload_bytes"] == 768 and middle["device_bytes"] == 12611584
+    assert [(name, off) for name, off, _need in middle["follow"]] == [("report", 0), ("n_points", 256), ("finals", 512), ("facts", 768)]
+    assert middle["follow_bytes"] == 5376
 
 
 # ---- the envelope of the fast path's gates (inputs: tests/envelope_cases.py; the same rungs run on the GPU in
