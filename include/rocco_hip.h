@@ -574,6 +574,46 @@ int rocco_hip_ecdf_survival_f64(rocco_hip_solver *solver, const double *stat_dev
                                 const long long *null_offsets_dev, size_t n_peaks, double *pvals_out_dev, void *stream);
 int rocco_hip_bh_adjust_f64(rocco_hip_solver *solver, const double *pvals_dev, size_t m, double *qvals_out_dev, void *stream);
 
+/* ---- summaries along the locus axis: score quantiles and candidate masks -----------------------------------------------
+ * Replace rocco/rocco.py:358-395 `cscores_quantiles` (logged per chromosome, rocco.py:1071) and rocco/inference.py:32-37,
+ * 382-443 `_robust_scale`, `benjamini_hochberg`, `_standardize_wls_z_scores`, `candidate_mask_from_wls`: each is a few
+ * order statistics of an n-long vector plus one elementwise pass.
+ *
+ * rocco_hip_select_ranks_batch_f64: for each of `count` vectors (vectors_dev / n / centers: host arrays of `count` entries)
+ *   the elements at `n_ranks` (0..16) ascending 0-based ranks -- ranks is a host array [count][n_ranks], any order, duplicates
+ *   allowed, each below its n -- written to values_out_dev[count][n_ranks] (device), and to counts_out_dev[count][4]
+ *   (device) the number of NaNs, of -inf, of +inf and of non-NaN values <= 0.0 (-inf included) of the vector itself in
+ *   either mode.  Order: the order-preserving key of the bit pattern, -0.0 before +0.0, every NaN (either sign) above +inf:
+ *   -inf.. finite.. +inf.. NaN..; a selected element comes back with its own bits, a NaN as the quiet NaN with all
+ *   payload bits set.  mode 0 selects among the values, mode 1 among |x - centers[v]| formed on load (subtraction and
+ *   fabs as written; a non-finite x is keyed as NaN) -- what a MAD needs, with no n-long intermediate; centers may be
+ *   NULL in mode 0.  A radix select: six counting passes (14 + 5 x 10 key bits) over all vectors at once, digit
+ *   histograms in LDS per vector and per still-distinct prefix, one placement launch behind each; 13 launches for up to
+ *   48 vectors whatever n_ranks is (more vectors: group after group of 48), no host synchronisation -- the call returns
+ *   with everything queued on `stream` -- 8 bytes read per value and pass, scratch of 16384 counters per vector and
+ *   nothing in proportion to n.  Results follow from integer counts alone.  n[v] < 2^31; n[v] == 0 only with n_ranks == 0.
+ * rocco_hip_bh_last_passing_rank_f64: *rank_out_dev (device) = the index i into sorted_dev (rocco_hip_sort_f64's output) of
+ *   the last element with sorted[i] <= fdr * ((k + 1) / (double)m) -- product and quotient in the order of inference.py:394
+ *   -- or -1; sorted[i] is the cutoff of the mask.  k is the element's 0-based rank in the reference's order, where
+ *   np.argsort puts every NaN last: the sort orders bit patterns, so NaNs with the sign bit set (0.0 / 0.0 on x86-64) lead
+ *   its output; the kernel finds how many do (`lead`, a bisection) and takes k = i - lead, so that k == i whenever no such
+ *   NaN is present.  No NaN of either sign passes.  The predicate is not monotone in k, so every rank is looked at.
+ * rocco_hip_threshold_mask_f64: mask[i] = ((isfinite(x[i]) ? x[i] / divisor : 0.0) > threshold) &&
+ *   (!use_floor || x[i] > floor_value), one byte 0 / 1 per element; a true IEEE division (inference.py:423, 440-442).
+ * rocco_hip_at_most_mask_f64: mask[i] = x[i] <= cutoff (false for a NaN): the BH mask, p <= sorted[last passing rank].
+ * rocco_hip_divide_finite_f64: out[i] = isfinite(x[i]) ? x[i] / divisor : 0.0 (`standardized`, inference.py:419-423). */
+int rocco_hip_select_ranks_batch_f64(rocco_hip_solver *solver, size_t count, const double *const *vectors_dev, const size_t *n,
+                                     size_t n_ranks, const long long *ranks, int mode, const double *centers,
+                                     double *values_out_dev, long long *counts_out_dev, void *stream);
+int rocco_hip_bh_last_passing_rank_f64(rocco_hip_solver *solver, const double *sorted_dev, size_t m, double fdr,
+                                       long long *rank_out_dev, void *stream);
+int rocco_hip_threshold_mask_f64(rocco_hip_solver *solver, const double *x_dev, size_t n, double divisor, double threshold,
+                                 double floor_value, int use_floor, uint8_t *mask_out_dev, void *stream);
+int rocco_hip_at_most_mask_f64(rocco_hip_solver *solver, const double *x_dev, size_t n, double cutoff, uint8_t *mask_out_dev,
+                               void *stream);
+int rocco_hip_divide_finite_f64(rocco_hip_solver *solver, const double *x_dev, size_t n, double divisor, double *out_dev,
+                                void *stream);
+
 /* bigWig dense fill: the NumPy statements of get_bigwig_chrom_scores after the file has been read
  * (rocco/readtracks.py:141-186) for one track's intervals in ascending order (as pyBigWig returns them).
  * *flags_out: bit 0 non-finite value (147-150), bit 1 non-positive width (153-156), bit 2 variable width (158-161),

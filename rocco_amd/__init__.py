@@ -21,11 +21,23 @@ from .budget import (  # noqa: F401  (rocco/inference.py:988-1148, 1312-1485, 15
 from .inference import crossfit_whittaker_baseline  # noqa: F401  (rocco/_baseline.c:16-104)
 from .inference import score_centered_wls  # noqa: F401  (rocco/_wls.c)
 from .inference import score_loci_wls  # noqa: F401  (rocco/inference.py:302-379)
+from .inference import (  # noqa: F401  (rocco/inference.py:32-37, 382-443, and their tensor-in, tensor-out forms)
+    _robust_scale,
+    _robust_scale_device,
+    _standardize_wls_z_scores,
+    _standardize_wls_z_scores_device,
+    benjamini_hochberg,
+    benjamini_hochberg_device,
+    candidate_mask_from_wls,
+    candidate_mask_from_wls_device,
+)
 from .scores import EmpiricalNull, score_peak_counts  # noqa: F401  (rocco/scores.py:120-149, 560-625)
 from .readtracks import assemble_chrom_matrix, bigwig_dense_fill  # noqa: F401  (rocco/readtracks.py:141-186, 614-633)
 from .rocco import (  # noqa: F401
     chrom_solution_to_bed,
     combine_chrom_results,
+    cscores_quantiles,
+    cscores_quantiles_batch_device,
     score_central_tendency_chrom,
     score_dispersion_chrom,
     solve_cached_chromosomes,

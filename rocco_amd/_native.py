@@ -154,6 +154,18 @@ PROTOTYPES = [
     ("rocco_hip_sorted_probe_f64", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, ctypes.c_size_t, c_double_p, ctypes.c_double, c_double_p,
       ctypes.c_size_t, c_ll_p, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_select_ranks_batch_f64", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), c_size_p, ctypes.c_size_t, c_ll_p, ctypes.c_int, c_double_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("rocco_hip_bh_last_passing_rank_f64", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
+    ("rocco_hip_threshold_mask_f64", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+      ctypes.c_void_p, ctypes.c_void_p]),
+    ("rocco_hip_at_most_mask_f64", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
+    ("rocco_hip_divide_finite_f64", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
     ("rocco_hip_autocovariance_sums_f64", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_int, c_double_p, ctypes.c_void_p]),
     ("rocco_hip_negative_part_f64", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

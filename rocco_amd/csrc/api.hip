@@ -132,6 +132,7 @@ void rocco_hip_solver_destroy(rocco_hip_solver *solver)
     solver->dev_results.release();
     solver->dev_bits.release();
     solver->dev_misc.release();
+    solver->dev_select.release();
     solver->dev_solution.release();
     solver->dev_maps.release();
     solver->dev_frozen.release();
@@ -585,6 +586,75 @@ int rocco_hip_sorted_probe_f64(rocco_hip_solver *solver, const double *sorted_de
         counts_lt_out[i] = hc[2 * i + 1];
     }
     return ROCCO_HIP_OK;
+}
+
+int rocco_hip_select_ranks_batch_f64(rocco_hip_solver *solver, size_t count, const double *const *vectors_dev, const size_t *n,
+                                     size_t n_ranks, const long long *ranks, int mode, const double *centers,
+                                     double *values_out_dev, long long *counts_out_dev, void *stream)
+{
+    if (solver == nullptr || n_ranks > (size_t)kSelectRanksMax || (mode != 0 && mode != 1) ||
+        (count > 0 && (vectors_dev == nullptr || n == nullptr || counts_out_dev == nullptr)) ||
+        (count > 0 && n_ranks > 0 && (ranks == nullptr || values_out_dev == nullptr)) || (count > 0 && mode == 1 && centers == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    for (size_t v = 0; v < count; ++v) {
+        if (n[v] >= ((size_t)1 << 31) || (n[v] > 0 && vectors_dev[v] == nullptr) || (n[v] == 0 && n_ranks > 0)) {
+            return ROCCO_HIP_EINVAL;
+        }
+        for (size_t r = 0; r < n_ranks; ++r) {
+            if (ranks[v * n_ranks + r] < 0 || ranks[v * n_ranks + r] >= (long long)n[v]) {
+                return ROCCO_HIP_EINVAL;
+            }
+        }
+    }
+    if (count == 0) {
+        return ROCCO_HIP_OK;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    const int rc = solver->dev_select.reserve(select_scratch_bytes(count));
+    if (rc != ROCCO_HIP_OK) return rc;
+    return launch_select_ranks_batch(vectors_dev, n, count, (int)n_ranks, ranks, mode, centers, values_out_dev, counts_out_dev,
+                                     solver->dev_select.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_bh_last_passing_rank_f64(rocco_hip_solver *solver, const double *sorted_dev, size_t m, double fdr,
+                                       long long *rank_out_dev, void *stream)
+{
+    if (solver == nullptr || rank_out_dev == nullptr || (m > 0 && sorted_dev == nullptr) || m >= ((size_t)1 << 31)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    return launch_bh_last_passing_rank(sorted_dev, m, fdr, rank_out_dev, (hipStream_t)stream);
+}
+
+int rocco_hip_threshold_mask_f64(rocco_hip_solver *solver, const double *x_dev, size_t n, double divisor, double threshold,
+                                 double floor_value, int use_floor, uint8_t *mask_out_dev, void *stream)
+{
+    if (solver == nullptr || (n > 0 && (x_dev == nullptr || mask_out_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    return launch_threshold_mask(x_dev, n, divisor, threshold, floor_value, use_floor, mask_out_dev, (hipStream_t)stream);
+}
+
+int rocco_hip_at_most_mask_f64(rocco_hip_solver *solver, const double *x_dev, size_t n, double cutoff, uint8_t *mask_out_dev,
+                               void *stream)
+{
+    if (solver == nullptr || (n > 0 && (x_dev == nullptr || mask_out_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    return launch_at_most_mask(x_dev, n, cutoff, mask_out_dev, (hipStream_t)stream);
+}
+
+int rocco_hip_divide_finite_f64(rocco_hip_solver *solver, const double *x_dev, size_t n, double divisor, double *out_dev,
+                                void *stream)
+{
+    if (solver == nullptr || (n > 0 && (x_dev == nullptr || out_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    return launch_divide_finite(x_dev, n, divisor, out_dev, (hipStream_t)stream);
 }
 
 int rocco_hip_autocovariance_sums_f64(rocco_hip_solver *solver, const double *x_dev, size_t n, double mean, int max_lag,

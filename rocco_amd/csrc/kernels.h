@@ -86,6 +86,22 @@ int launch_std(const void *matrix_dev, int dtype, size_t K, size_t n, size_t row
 int launch_trimmed_std(const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, int rank_lo, int rank_hi,
                        int take_root, double *scores_dev, hipStream_t stream);
 
+// ---- select.hip -----------------------------------------------------------------------------
+// order statistics of `count` vectors by a batched radix select, nothing n-long written (see the head of select.hip)
+constexpr int kSelectBatchMax = 48;  // vectors per series of launches (kernel-argument task table); more are served group by group
+constexpr int kSelectRanksMax = 16;  // ranks followed per vector
+size_t select_scratch_bytes(size_t count);
+// vectors_dev / n / centers: host arrays of `count` entries; ranks: host, [count][n_ranks], each below its n;
+// values_out_dev: [count][n_ranks]; counts_out_dev: [count][4].  Everything is queued on `stream`, nothing is waited for.
+int launch_select_ranks_batch(const double *const *vectors_dev, const size_t *n, size_t count, int n_ranks, const long long *ranks,
+                              int mode, const double *centers, double *values_out_dev, long long *counts_out_dev, void *scratch_dev,
+                              hipStream_t stream);
+int launch_bh_last_passing_rank(const double *sorted_dev, size_t m, double fdr, long long *rank_out_dev, hipStream_t stream);
+int launch_threshold_mask(const double *x_dev, size_t n, double divisor, double threshold, double floor_value, int use_floor,
+                          uint8_t *mask_out_dev, hipStream_t stream);
+int launch_at_most_mask(const double *x_dev, size_t n, double cutoff, uint8_t *mask_out_dev, hipStream_t stream);
+int launch_divide_finite(const double *x_dev, size_t n, double divisor, double *out_dev, hipStream_t stream);
+
 // ---- decode.hip -----------------------------------------------------------------------------
 // scratch: at least decode_scratch_bytes(n) bytes
 size_t decode_scratch_bytes(size_t n);

@@ -16,6 +16,7 @@
 
 #include <vector>
 #include "log2_cr.h"
+#include "radix_key.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -573,12 +574,6 @@ __global__ void wls_knots_kernel(const unsigned long long *__restrict__ ys_sorte
     }
 }
 
-__device__ __forceinline__ double key_to_double(unsigned long long k)
-{
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k;
-    return __longlong_as_double((long long)b);
-}
-
 // ---- np.median of every row without sorting it (round 3) ----------------------------------------------------------------
 // The median is one order statistic (two for an even length): a radix SELECT over the order-preserving keys finds the key
 // of rank (n - 1) / 2 of EVERY row in six passes over the matrix -- digits of 11, 11, 11, 11, 11 and 9 bits from the top,
@@ -595,36 +590,7 @@ struct RowSelect {  // per row, in device memory
     long long count_le;          // keys at or below the wanted one
 };
 
-__device__ __forceinline__ unsigned long long order_key(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-}
-
-// One count per active lane into an LDS histogram.  The keys of a row of counts, or the variances of one bin, crowd into a few
-// buckets: 64 lanes adding to ONE counter are serialised lane by lane.  So the two most common buckets of the wavefront are
-// counted by one lane each (a ballot of the lanes that share the leader's bucket), whoever is left adds for itself.
-__device__ __forceinline__ void lds_count(unsigned *__restrict__ local, unsigned bucket, bool active)
-{
-    unsigned long long todo = __ballot(active);
-    const int lane = (int)(threadIdx.x & 63);
-#pragma unroll
-    for (int round = 0; round < 2; ++round) {
-        if (todo == 0ULL) {
-            break;
-        }
-        const int leader = __ffsll((long long)todo) - 1;
-        const unsigned b0 = (unsigned)__shfl((int)bucket, leader);
-        const unsigned long long same = __ballot(active && bucket == b0) & todo;
-        if (lane == leader) {
-            atomicAdd(&local[b0], (unsigned)__popcll(same));
-        }
-        todo &= ~same;
-    }
-    if ((todo >> lane) & 1ULL) {
-        atomicAdd(&local[bucket], 1u);
-    }
-}
+// order_key, key_to_double and lds_count (the count of the lanes of a wavefront that crowd into a few buckets): radix_key.h
 
 // pass `p` looks at the `width` bits above bit `low`; hist[row][digit] += keys of the row matching its prefix.
 // SPAN (round 5, the passes behind the gathered-cell shortcut): also the smallest and the largest key that matches the

@@ -1032,3 +1032,279 @@ def compute_budget_null_draw_device(residual_template_t, wild_weights_t, lower_b
                                                            float(null_soft_scale), float(null_threshold), stats,
                                                            stream), "rocco_hip_budget_null_draw_stats_f64")
     return float(stats[0]), float(stats[1]), float(stats[2]), float(stats[3])
+
+
+# --------------------------------------------------------------------------------------------
+# summaries along the locus axis (rocco/inference.py:32-37, 382-443): order statistics by the batched radix select
+# (csrc/select.hip), one elementwise kernel behind them
+# --------------------------------------------------------------------------------------------
+
+_SELECT_RANKS_MAX = 16  # ranks one select call follows per vector (kSelectRanksMax)
+
+
+def select_ranks_batch_device(tensors, ranks, mode: int = 0, centers=None):
+    """Order statistics of several vectors by ONE `rocco_hip_select_ranks_batch_f64` call, nothing waited for.
+
+    `tensors`: contiguous one-dimensional float64 CUDA tensors on one device; `ranks`: one list of 0-based ascending
+    ranks per tensor, all of one length R <= 16 (any order, duplicates allowed).  mode 0 selects among the values,
+    mode 1 among |x - centers[v]| with every non-finite x sorted last as a NaN.  Returns (values [count, R] float64,
+    counts [count, 4] int64: NaNs, -inf, +inf, non-NaN values <= 0 of each vector itself), both on the device."""
+    import torch
+
+    count = len(tensors)
+    if count == 0:
+        raise ValueError("at least one vector is needed")
+    device = tensors[0].device
+    for t in tensors:
+        if t.dim() != 1 or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.device != device:
+            raise ValueError("every vector must be a contiguous one-dimensional float64 CUDA tensor on one device")
+    n_ranks = len(ranks[0]) if len(ranks) else 0
+    if len(ranks) != count or any(len(r) != n_ranks for r in ranks):
+        raise ValueError("one rank list of the same length per vector is needed")
+    if n_ranks > _SELECT_RANKS_MAX:
+        raise ValueError(f"at most {_SELECT_RANKS_MAX} ranks per call")
+    if mode == 1 and (centers is None or len(centers) != count):
+        raise ValueError("mode 1 needs one centre per vector")
+    pointers = (ctypes.c_void_p * count)(*[t.data_ptr() for t in tensors])
+    lengths = (ctypes.c_size_t * count)(*[int(t.shape[0]) for t in tensors])
+    flat = (ctypes.c_longlong * max(1, count * n_ranks))(*[int(k) for r in ranks for k in r])
+    mids = None if mode != 1 else (ctypes.c_double * count)(*[float(c) for c in centers])
+    values = torch.empty((count, n_ranks), dtype=torch.float64, device=device)
+    counts = torch.empty((count, 4), dtype=torch.int64, device=device)
+    solver = _native.solver_for(device.index)
+    _native.check(_native.load().rocco_hip_select_ranks_batch_f64(
+        solver.handle, count, pointers, lengths, n_ranks, flat, int(mode), mids, values.data_ptr(), counts.data_ptr(),
+        _dp._stream_ptr(tensors[0])), "rocco_hip_select_ranks_batch_f64")
+    return values, counts
+
+
+class _DeviceVector:
+    """What the functions below ask of a score vector in HBM; each answer that comes back as a Python number is one host
+    round trip.  (tests/test_locus_summaries_host.py runs the same functions over a NumPy stand-in.)"""
+
+    def __init__(self, t):
+        self.t = t
+        self.n = int(t.shape[0])
+        self._counts = None
+
+    def _lib(self):
+        return _native.load(), _native.solver_for(self.t.device.index), _dp._stream_ptr(self.t)
+
+    def counts(self):
+        if self._counts is None:  # (asked for once: every caller below shares the answer)
+            self._counts = tuple(int(c) for c in select_ranks_batch_device([self.t], [[]])[1][0].tolist())
+        return self._counts
+
+    def select(self, ranks, mode: int = 0, center: float = 0.0):
+        return [float(v) for v in select_ranks_batch_device([self.t], [list(ranks)], mode, [center])[0][0].tolist()]
+
+    def last_passing(self, fdr: float):
+        """(index i of the last element of the sorted copy that passes sorted[i] <= fdr * ((k + 1) / m), or -1; sorted[i]),
+        k the element's rank with every NaN last as np.argsort has them (the kernel steps over the sign-set NaNs that lead
+        the device sort's output)"""
+        import torch
+
+        from .budget import sort_device
+
+        lib, solver, stream = self._lib()
+        ordered = sort_device(self.t)
+        rank = torch.empty(1, dtype=torch.int64, device=self.t.device)
+        _native.check(lib.rocco_hip_bh_last_passing_rank_f64(solver.handle, ordered.data_ptr(), self.n, float(fdr), rank.data_ptr(),
+                                                             stream), "rocco_hip_bh_last_passing_rank_f64")
+        # the one number the mask needs: sorted[rank], picked on the device and fetched in one copy
+        picked = ordered[rank.clamp_min(0)]
+        k, cutoff = torch.stack((rank.to(torch.float64), picked)).flatten().tolist()
+        return int(k), float(cutoff)
+
+    def at_most(self, cutoff: float):
+        import torch
+
+        lib, solver, stream = self._lib()
+        mask = torch.empty(self.n, dtype=torch.uint8, device=self.t.device)
+        _native.check(lib.rocco_hip_at_most_mask_f64(solver.handle, self.t.data_ptr(), self.n, float(cutoff), mask.data_ptr(), stream),
+                      "rocco_hip_at_most_mask_f64")
+        return mask.view(torch.bool)
+
+    def threshold_mask(self, divisor: float, threshold: float, floor_value: float, use_floor: bool):
+        import torch
+
+        lib, solver, stream = self._lib()
+        mask = torch.empty(self.n, dtype=torch.uint8, device=self.t.device)
+        _native.check(lib.rocco_hip_threshold_mask_f64(solver.handle, self.t.data_ptr(), self.n, float(divisor), float(threshold),
+                                                       float(floor_value), int(bool(use_floor)), mask.data_ptr(), stream),
+                      "rocco_hip_threshold_mask_f64")
+        return mask.view(torch.bool)
+
+    def divide_finite(self, divisor: float):
+        import torch
+
+        lib, solver, stream = self._lib()
+        out = torch.empty_like(self.t)
+        _native.check(lib.rocco_hip_divide_finite_f64(solver.handle, self.t.data_ptr(), self.n, float(divisor), out.data_ptr(), stream),
+                      "rocco_hip_divide_finite_f64")
+        return out
+
+
+def _middle(values, odd: bool) -> float:
+    """np.median's last step: the middle value, or np.mean of the two middle values."""
+    a, b = np.float64(values[0]), np.float64(values[1])
+    with np.errstate(all="ignore"):
+        return float(a) if odd else float((a + b) / np.float64(2.0))
+
+
+def _robust_scale_of(vec, floor: float = 1.0e-6) -> float:
+    """`_robust_scale` of all of `vec` from two selects: its median (mode 0), then the median of |x - median| (mode 1)."""
+    n = vec.n
+    if n == 0:
+        return float(floor)
+    n_nan, _n_ninf, _n_pinf, _n_le0 = vec.counts()
+    ranks = ((n - 1) // 2, n // 2)
+    mad = float("nan")
+    if n_nan == 0:
+        centre = _middle(vec.select(ranks), n % 2 == 1)
+        if np.isfinite(centre):
+            # an infinite x is infinitely far from a finite median; the select sorts it last as a NaN
+            far = [float("inf") if np.isnan(v) else v for v in vec.select(ranks, 1, centre)]
+            mad = _middle(far, n % 2 == 1)
+        # (a median that is not finite leaves inf - inf among the deviations, and np.median answers NaN)
+    return float(max(np.float64(mad) * 1.4826, floor))
+
+
+def _null_scale_of(vec) -> float:
+    """`null_scale` of rocco/inference.py:409-418 without forming any of its vectors.
+
+    With m finite scores <= 0 the reference takes the MAD of concatenate((neg, -neg)): its median is exactly 0.0 and
+    the MAD is np.median(|neg|), the mean of the ascending |neg| ranks (m - 1) // 2 and m // 2 -- ascending ranks
+    lo + m - 1 - (m - 1) // 2 and lo + m - 1 - m // 2 of the whole vector, lo the number of -inf.  With none it is
+    `_robust_scale` of the finite scores, which occupy the ranks lo .. lo + finite - 1."""
+    n_nan, n_ninf, n_pinf, n_le0 = vec.counts()
+    finite = vec.n - n_nan - n_ninf - n_pinf
+    if finite <= 0:
+        raise ValueError("`z_scores` must contain at least one finite value")
+    lo, m = n_ninf, n_le0 - n_ninf
+    if m > 0:
+        a, b = vec.select((lo + m - 1 - (m - 1) // 2, lo + m - 1 - m // 2))
+        mad = np.float64(_middle((abs(a), abs(b)), False))
+    else:
+        odd = finite % 2 == 1
+        centre = _middle(vec.select((lo + (finite - 1) // 2, lo + finite // 2)), odd)
+        # mode 1 sorts the non-finite scores last: ranks 0 .. finite - 1 are the finite scores' deviations
+        mad = np.float64(_middle(vec.select(((finite - 1) // 2, finite // 2), 1, centre), odd))
+    return float(max(mad * 1.4826, 1.0e-6))
+
+
+def _bh_mask_of(vec, fdr: float):
+    """The mask of rocco/inference.py:392-399 as p <= sorted[cutoff]: when rank k passes and p_(k+1) == p_(k), rank k + 1
+    passes too, so the cutoff is never inside a run of ties and the reference's mask[order[:cutoff + 1]] is that set
+    whatever order its argsort gives the ties; NaNs of either sign rank last there and never pass.  None: nothing passes."""
+    cutoff_rank, cutoff = vec.last_passing(float(fdr))
+    return None if cutoff_rank < 0 else vec.at_most(cutoff)
+
+
+def _as_vector_tensor(values, name: str):
+    """float64 contiguous CUDA tensor of a one-dimensional input; (tensor, was a tensor)"""
+    import torch
+
+    if _dp._resident_tensor(values) is not None:
+        values = _dp._resident_tensor(values)
+    if _dp._is_tensor(values):
+        t = values
+        if t.dim() != 1:
+            raise ValueError(f"`{name}` must be one-dimensional")
+        if not t.is_cuda:
+            t = t.to(f"cuda:{_dp._device_index()}")
+        return t.to(torch.float64).contiguous()
+    arr = np.asarray(values, dtype=np.float64)
+    if arr.ndim != 1:
+        raise ValueError(f"`{name}` must be one-dimensional")
+    return torch.from_numpy(np.ascontiguousarray(arr)).to(f"cuda:{_dp._device_index()}")
+
+
+def _robust_scale_device(values_t, floor: float = 1.0e-6) -> float:
+    """`_robust_scale` of a CUDA tensor (any shape: NumPy's median flattens)."""
+    import torch
+
+    t = values_t.to(torch.float64).contiguous().reshape(-1)
+    if not t.is_cuda:
+        t = t.to(f"cuda:{_dp._device_index()}")
+    return _robust_scale_of(_DeviceVector(t), floor)
+
+
+def _robust_scale(values: np.ndarray, floor: float = 1.0e-6) -> float:
+    """rocco/inference.py:32-37: max(1.4826 * MAD, floor), the floor for an empty input."""
+    import torch
+
+    values_ = np.asarray(values, dtype=np.float64)
+    if values_.size == 0:
+        return float(floor)
+    return _robust_scale_device(torch.from_numpy(np.ascontiguousarray(values_).reshape(-1)).to(f"cuda:{_dp._device_index()}"), floor)
+
+
+def benjamini_hochberg_device(p_values_t, fdr: float = 0.01):
+    """`benjamini_hochberg` of a one-dimensional CUDA tensor: a bool tensor.  One sort (the predicate is not monotone in the
+    rank), the last passing rank, one fetched number, one mask kernel."""
+    import torch
+
+    t = _as_vector_tensor(p_values_t, "p_values")
+    if int(t.shape[0]) == 0:
+        return torch.zeros(0, dtype=torch.bool, device=t.device)
+    mask = _bh_mask_of(_DeviceVector(t), fdr)
+    return torch.zeros(int(t.shape[0]), dtype=torch.bool, device=t.device) if mask is None else mask
+
+
+def benjamini_hochberg(
+    p_values: np.ndarray,
+    fdr: float = 0.01,
+) -> np.ndarray:
+    """rocco/inference.py:382-400."""
+    p_values_ = np.asarray(p_values, dtype=np.float64)
+    if p_values_.ndim != 1:
+        raise ValueError("`p_values` must be one-dimensional")
+    if p_values_.shape[0] == 0:
+        return np.zeros(0, dtype=bool)
+    return benjamini_hochberg_device(_as_vector_tensor(p_values_, "p_values"), fdr).cpu().numpy()
+
+
+def _standardize_wls_z_scores_device(z_scores_t):
+    """`_standardize_wls_z_scores` of a one-dimensional CUDA tensor: (standardized tensor, null_scale)."""
+    t = _as_vector_tensor(z_scores_t, "z_scores")
+    vec = _DeviceVector(t)
+    null_scale = _null_scale_of(vec)
+    return vec.divide_finite(max(null_scale, 1.0e-6)), float(null_scale)
+
+
+def _standardize_wls_z_scores(
+    z_scores: np.ndarray,
+) -> tuple[np.ndarray, float]:
+    """rocco/inference.py:403-424."""
+    z_scores_ = np.asarray(z_scores, dtype=np.float64)
+    if z_scores_.ndim != 1:
+        raise ValueError("`z_scores` must be one-dimensional")
+    if not np.any(np.isfinite(z_scores_)):
+        raise ValueError("`z_scores` must contain at least one finite value")
+    standardized, null_scale = _standardize_wls_z_scores_device(_as_vector_tensor(z_scores_, "z_scores"))
+    return standardized.cpu().numpy(), null_scale
+
+
+def candidate_mask_from_wls_device(z_scores_t, tail_z: float = 2.0, min_signal: float = 0.0):
+    """`candidate_mask_from_wls` of a one-dimensional CUDA tensor: a bool tensor.  The standardized scores are not
+    written: the mask kernel divides and compares (a true division, as inference.py:423 rounds)."""
+    t = _as_vector_tensor(z_scores_t, "z_scores")
+    vec = _DeviceVector(t)
+    null_scale = _null_scale_of(vec)
+    return vec.threshold_mask(max(null_scale, 1.0e-6), float(tail_z), float(min_signal), min_signal > 0)
+
+
+def candidate_mask_from_wls(
+    z_scores: np.ndarray,
+    tail_z: float = 2.0,
+    min_signal: float = 0.0,
+) -> np.ndarray:
+    r"""Turn WLS z-scores into a one-sided exceedance mask (rocco/inference.py:427-443): a robust null width from the
+    non-positive side, the z-scores rescaled by it, and the loci with :math:`\tilde z_j > z_0` marked."""
+    z_scores_ = np.asarray(z_scores, dtype=np.float64)
+    if z_scores_.ndim != 1:
+        raise ValueError("`z_scores` must be one-dimensional")
+    if not np.any(np.isfinite(z_scores_)):
+        raise ValueError("`z_scores` must contain at least one finite value")
+    return candidate_mask_from_wls_device(_as_vector_tensor(z_scores_, "z_scores"), tail_z, min_signal).cpu().numpy()

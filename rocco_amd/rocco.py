@@ -3,6 +3,7 @@ reference's `rocco/rocco.py`:
 
     score_central_tendency_chrom   rocco/rocco.py:243-304  (median branch 264-265; call-site 983-991)
     score_dispersion_chrom         rocco/rocco.py:307-355  (tstd per column, see its docstring)
+    cscores_quantiles              rocco/rocco.py:358-395  (a batched radix select; logged per chromosome, 1071)
     chrom_solution_to_bed          rocco/rocco.py:139-191
     _merge_bed_records             rocco/rocco.py:74-95
     _write_bed_records             rocco/rocco.py:98-110
@@ -407,6 +408,81 @@ def score_dispersion_chrom(chrom_matrix, method="mad", rng=(25, 75), tprop=0.05,
                                                          int(out_t.shape[0]), _dp._stream_ptr(out_t)), "rocco_hip_power_f64")
         out = out_t.cpu().numpy()
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# score quantiles (rocco/rocco.py:358-395)
+# --------------------------------------------------------------------------------------------
+
+_DEFAULT_QUANTILES = (0.0, 0.01, 0.05, 0.25, 0.50, 0.75, 0.95, 0.975, 0.99, 1.0)  # rocco/rocco.py:373-386
+
+
+def _higher_quantile_rank(n: int, q) -> int:
+    """The 0-based ascending rank np.quantile(x, q, method="higher") picks from n values: ceil((n - 1) * q) in float64."""
+    return int(np.ceil((n - 1) * np.float64(q)))
+
+
+def _check_quantiles(n: int, quantiles) -> None:
+    """NumPy's own errors, in the reference's order (one np.quantile call per quantile): the ValueError for a quantile
+    outside [0, 1], the IndexError for an empty vector -- raised by NumPy itself on a stand-in of the same emptiness."""
+    stand_in = np.zeros(1 if n > 0 else 0, dtype=np.float64)
+    for q in quantiles:
+        np.quantile(stand_in, q=q, method="higher")
+
+
+def cscores_quantiles_batch_device(score_tensors, quantiles=None):
+    """np.quantile(scores, q, method="higher") for every q of `quantiles` and every vector of `score_tensors` (CUDA tensors
+    or arrays with a twin in HBM; flattened as NumPy flattens) by ONE batched radix select per 16 quantiles: a float64
+    tensor [count, Q] on the device, nothing waited for.  A vector that holds a NaN gets NaN for every quantile."""
+    import torch
+
+    from .inference import _SELECT_RANKS_MAX, _as_vector_tensor, select_ranks_batch_device
+
+    qs = list(_DEFAULT_QUANTILES if quantiles is None else quantiles)
+    tensors = []
+    for scores in score_tensors:
+        twin = _dp._resident_tensor(scores)
+        scores = twin if twin is not None else scores
+        tensors.append(_as_vector_tensor(scores.reshape(-1) if _dp._is_tensor(scores) else np.asarray(scores, dtype=np.float64).reshape(-1),
+                                         "chrom_scores"))
+    for emptiness in sorted({int(t.shape[0]) > 0 for t in tensors}, reverse=True):  # (the errors depend on nothing else)
+        _check_quantiles(int(emptiness), qs)
+    ranks = [[_higher_quantile_rank(int(t.shape[0]), q) for q in qs] for t in tensors]
+    parts, counts = [], None
+    for first in range(0, max(1, len(qs)), _SELECT_RANKS_MAX):
+        values, counts = select_ranks_batch_device(tensors, [r[first:first + _SELECT_RANKS_MAX] for r in ranks])
+        parts.append(values)
+    values = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+    return torch.where(counts[:, :1] > 0, torch.full_like(values, float("nan")), values)
+
+
+def _format_quantiles(quantiles, values, add_newlines=True) -> str:
+    """The reference's string (rocco/rocco.py:387-395) from the quantile values; duplicates collapse as dict keys do."""
+    from pprint import pformat
+
+    formatted_string = pformat({f"Quantile={q}": round(np.float64(v), 4) for q, v in zip(quantiles, values)})
+    if add_newlines:
+        return f"\n{formatted_string}\n"
+    return f"{formatted_string}"
+
+
+def cscores_quantiles(
+    chrom_scores: np.ndarray,
+    quantiles: np.ndarray = None,
+    add_newlines=True,
+) -> str:
+    """Return a formatted string of quantiles for a locus-score array (rocco/rocco.py:358-395): `pformat` of
+    {"Quantile=q": round(np.quantile(chrom_scores, q, method="higher"), 4)} in the order the quantiles are given.
+
+    The order statistics come from the device (`cscores_quantiles_batch_device`; a NumPy array is copied up, a CUDA
+    tensor or a cached score array is read where it is); the string is built on the host as the reference builds it.
+    Where -0.0 and +0.0 both sit at a selected rank the zero returned is -0.0's successor in key order, not whichever
+    NumPy's partition left there: the values compare equal, the printed sign may differ."""
+    if quantiles is None:
+        quantiles = np.array(_DEFAULT_QUANTILES)
+    qs = list(quantiles)
+    values = cscores_quantiles_batch_device([chrom_scores], qs)[0].tolist() if len(qs) else []
+    return _format_quantiles(qs, values, add_newlines)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1039,6 +1115,12 @@ def _build_chrom_cache(chroms_to_process: list, signal_inputs, args: dict) -> di
                                           return_details=True, **plan.wls, **shared)
             together = _estimates_side_by_side(ready, plan, one, side_streams)
         try:
+            # the score quantiles the reference logs per chromosome (rocco/rocco.py:1066-1071): all chromosomes whose scores
+            # exist (the batch: every chromosome unless memory or `low_memory` split them) by ONE batched select, queued here
+            # and fetched when the first line is written -- and only when somebody reads INFO
+            quantile_values = None
+            if logger.isEnabledFor(logging.INFO) and ready:
+                quantile_values = cscores_quantiles_batch_device([entry[2] for entry in ready])
             for i, (name, starts, scores, details, centred) in enumerate(ready):
                 start_ahead(i + 1 + depth)
                 extra = {} if plan.multipliers is None else {"multipliers": plan.multipliers}
@@ -1061,6 +1143,11 @@ def _build_chrom_cache(chroms_to_process: list, signal_inputs, args: dict) -> di
                     raise ValueError(f"{name} budget estimate is not finite")
                 n_loci = int(scores.shape[0])
                 total = float(np.clip(meta.get("effective_total_count", n_loci), 1.0, n_loci))
+                if quantile_values is not None:
+                    if _dp._is_tensor(quantile_values):
+                        quantile_values = quantile_values.tolist()
+                    logger.info("%s %s:%s", name, "direct input scores" if plan.bigwig else "WLS scores",
+                                _format_quantiles(_DEFAULT_QUANTILES, quantile_values[i]))
                 logger.info("%s raw budget estimate: %s", name, meta)
                 gamma, gamma_meta = _budget._resolve_chrom_gamma(name, args, scores, meta)
                 cache[name] = {
