@@ -627,6 +627,64 @@ int rocco_hip_bigwig_dense_fill_f64(rocco_hip_solver *solver, const int64_t *sta
                                     double *full_out_dev, size_t capacity, int64_t *first_start_out, int64_t *step_out,
                                     size_t *n_full_out, int *flags_out, void *stream);
 
+/* ---- decoded alignment records -> binned coverage ------------------
+ * What the reference does with a BAM record once htslib has decoded it, for records any decoder supplies as six
+ * arrays in file order (the order the index iterator yields them), 16 bytes per record: pos (core.pos), end
+ * (bam_endpos), isize (core.isize) as int32, flag (core.flag) as uint16, mapq (core.qual) and mate_same
+ * (core.mtid == core.tid) as uint8.  The records of K tracks are concatenated; rec_offsets_host has K + 1 entries.
+ * BAM decoding itself, the fragments (tabix) source, barcode filters, the count modes other than "coverage" and the
+ * whole-file probes (paired-end detection, read length, mapped-read count, fragment length) stay outside.
+ *
+ * rocco_hip_count_alignment_records_batch: ccounts_countRegion's alignment branch (rocco/native/ccounts_backend.c:
+ *   2400-2573) for K tracks in one launch series: per record the overlap test of the index iterator on the read as it
+ *   lies in the file (pos < end_of_region && max(end, pos + 1) > start_of_region; a shift or an extension never brings
+ *   in a read the iterator did not yield), the flag / mapping-quality filters, the paired-end or single-end fragment,
+ *   the clip to the region, and either the midpoint bin (one_read_per_bin) or +1 at index0 / -1 behind index1 with the
+ *   reference's clamp and skip; then the running sum over the bins.  out_dev + out_offsets_host[k] receives n_bins
+ *   float32 counts of track k (accumulate != 0: they are added to what is there, one float addition per bin, as the
+ *   reference adds into its countBuffer).  Integer atomics and an int32 prefix sum: the result does not depend on
+ *   scheduling and equals the reference's float arithmetic while every difference cell and every running value stays
+ *   within 2^24 in magnitude; max_magnitude_out_host[k] is the largest one seen for track k and the caller refuses a
+ *   result beyond 2^24 (there the reference's own result depends on record order).  With accumulate and
+ *   one_read_per_bin the reference adds 1.0f at a time into the used buffer: one addition per bin equals that only while
+ *   the buffer holds integers, so for such a track |buffer + count| counts towards max_magnitude_out_host[k] as well and
+ *   a buffer of non-integers is the caller's to avoid.  Records per track < 2^31.
+ * rocco_hip_count_alignment_shape: shape_out[0..3] = records a workgroup aggregates at a time, workgroups of one
+ *   launch at most, bins per scan tile, bins of the LDS window (the sizes at which the kernels change path).
+ * rocco_hip_alignment_chrom_range: ccounts_getChromRange for the alignment source (ccounts_backend.c:1666-1705):
+ *   *start_out = pos of the first record in file order that flag_exclude passes among those the query over
+ *   [0, chrom_len) yields; *end_out = end of the LAST such record in file order (not the maximum) among those the query
+ *   over [max(chrom_len - 2000000, 0), chrom_len) yields; 0 where no record qualifies (a start without an end happens).
+ * rocco_hip_alignment_count_tail_f64: rocco/readtracks.py:492-517 after the counting: vals = float64(counts) *
+ *   norm_scale, / step when scale_by_step, * const_scale when const_scale >= 0 (in that order); *first_out / *last_out
+ *   = first / last index with vals > 0 (-1: none); vals_out_dev = np.round(vals, round_digits) for every bin (the caller
+ *   slices first .. last).  Exact. */
+typedef struct rocco_hip_count_options {
+    int32_t flag_include, flag_exclude, min_mapq, read_length, extend_bp, paired_end_mode, min_template_length,
+        max_insert_size, shift_fwd, shift_rev, one_read_per_bin;
+} rocco_hip_count_options;
+typedef struct rocco_hip_count_region {
+    int32_t start, end, step, n_bins; /* n_bins: the reference's countBufferLength, ((end - start - 1) / step) + 1 */
+} rocco_hip_count_region;
+/* the four numbers of rocco_hip_count_alignment_shape; count.hip asserts that its kernels are built to them */
+#define ROCCO_COUNT_CHUNK_RECORDS 512
+#define ROCCO_COUNT_MAX_GRID 512
+#define ROCCO_COUNT_SCAN_TILE 2048
+#define ROCCO_COUNT_WINDOW_BINS 1024
+int rocco_hip_count_alignment_records_batch(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                            const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mapq_dev,
+                                            const uint8_t *mate_same_dev, const int64_t *rec_offsets_host, size_t K,
+                                            const rocco_hip_count_options *options_host,
+                                            const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host,
+                                            int accumulate, float *out_dev, int64_t *max_magnitude_out_host, void *stream);
+void rocco_hip_count_alignment_shape(int *shape_out);
+int rocco_hip_alignment_chrom_range(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                    const uint16_t *flag_dev, size_t n, int64_t chrom_len, int flag_exclude,
+                                    int64_t *start_out, int64_t *end_out, void *stream);
+int rocco_hip_alignment_count_tail_f64(rocco_hip_solver *solver, const float *counts_dev, size_t n, double norm_scale,
+                                       int scale_by_step, double step, double const_scale, int round_digits,
+                                       double *vals_out_dev, int64_t *first_out, int64_t *last_out, void *stream);
+
 /* ---- synthetic signal matrices (benchmark / test support, device-resident) -------------------
  * Fills a row-major [K][n] matrix with the counter-based synthetic tracks described in
  * DESIGN.md section 7 (5-decimal background + planted peaks with per-sample dropout); the same

@@ -33,6 +33,14 @@ from .inference import (  # noqa: F401  (rocco/inference.py:32-37, 382-443, and 
 )
 from .scores import EmpiricalNull, score_peak_counts  # noqa: F401  (rocco/scores.py:120-149, 560-625)
 from .readtracks import assemble_chrom_matrix, bigwig_dense_fill  # noqa: F401  (rocco/readtracks.py:141-186, 614-633)
+from .readtracks import (  # noqa: F401  (rocco/native/ccounts_backend.c:1666-1705, 2400-2573; rocco/readtracks.py:439-518)
+    AlignmentRecords,
+    alignment_chrom_range_from_records,
+    bam_chrom_reads_from_records,
+    bam_chrom_reads_from_records_batch,
+    count_alignment_records_batch_device,
+    count_alignment_region_from_records,
+)
 from .rocco import (  # noqa: F401
     chrom_solution_to_bed,
     combine_chrom_results,

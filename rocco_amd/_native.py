@@ -264,6 +264,21 @@ PROTOTYPES = [
     ("rocco_hip_bigwig_dense_fill_f64", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_int,
       ctypes.c_void_p, ctypes.c_size_t, c_ll_p, c_ll_p, c_size_p, c_int_p, ctypes.c_void_p]),
+    # row f5 (csrc/count.hip): ccounts_countRegion's alignment branch, rocco/native/ccounts_backend.c:2400-2573
+    ("rocco_hip_count_alignment_records_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      c_ll_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_int, ctypes.c_void_p, c_ll_p,
+      ctypes.c_void_p]),
+    # (no reference line: the sizes at which count.hip's kernels change path, for the tests)
+    ("rocco_hip_count_alignment_shape", None, [c_int_p]),
+    # ccounts_getChromRange, rocco/native/ccounts_backend.c:1666-1705
+    ("rocco_hip_alignment_chrom_range", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_int,
+      c_ll_p, c_ll_p, ctypes.c_void_p]),
+    # the tail of get_bam_chrom_reads, rocco/readtracks.py:492-517
+    ("rocco_hip_alignment_count_tail_f64", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+      ctypes.c_int, ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_void_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t,
       ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]),

@@ -1435,6 +1435,78 @@ int rocco_hip_bigwig_dense_fill_f64(rocco_hip_solver *solver, const int64_t *sta
                                     (hipStream_t)stream);
 }
 
+int rocco_hip_count_alignment_records_batch(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                            const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mapq_dev,
+                                            const uint8_t *mate_same_dev, const int64_t *rec_offsets_host, size_t K,
+                                            const rocco_hip_count_options *options_host,
+                                            const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host,
+                                            int accumulate, float *out_dev, int64_t *max_magnitude_out_host, void *stream)
+{
+    if (solver == nullptr || K == 0 || K >= (size_t)0x7fffffff || rec_offsets_host == nullptr || options_host == nullptr ||
+        regions_host == nullptr || out_offsets_host == nullptr || out_dev == nullptr || max_magnitude_out_host == nullptr) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (rec_offsets_host[K] > rec_offsets_host[0] &&
+        (pos_dev == nullptr || end_dev == nullptr || isize_dev == nullptr || flag_dev == nullptr || mapq_dev == nullptr ||
+         mate_same_dev == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    const size_t bytes = count_alignment_scratch_bytes(rec_offsets_host, K, options_host, regions_host, out_offsets_host);
+    if (bytes == 0) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    int rc;
+    if ((rc = solver->dev_misc.reserve(bytes)) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_count_alignment_records(pos_dev, end_dev, isize_dev, flag_dev, mapq_dev, mate_same_dev, rec_offsets_host, K,
+                                          options_host, regions_host, out_offsets_host, accumulate, out_dev,
+                                          max_magnitude_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+void rocco_hip_count_alignment_shape(int *shape_out)
+{
+    shape_out[0] = ROCCO_COUNT_CHUNK_RECORDS;
+    shape_out[1] = ROCCO_COUNT_MAX_GRID;
+    shape_out[2] = ROCCO_COUNT_SCAN_TILE;
+    shape_out[3] = ROCCO_COUNT_WINDOW_BINS;
+}
+
+int rocco_hip_alignment_chrom_range(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                    const uint16_t *flag_dev, size_t n, int64_t chrom_len, int flag_exclude,
+                                    int64_t *start_out, int64_t *end_out, void *stream)
+{
+    if (solver == nullptr || start_out == nullptr || end_out == nullptr || chrom_len < 0 ||
+        (n > 0 && (pos_dev == nullptr || end_dev == nullptr || flag_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    int rc;
+    if ((rc = solver->dev_misc.reserve(256)) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_alignment_chrom_range(pos_dev, end_dev, flag_dev, n, chrom_len, flag_exclude, start_out, end_out,
+                                        solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_alignment_count_tail_f64(rocco_hip_solver *solver, const float *counts_dev, size_t n, double norm_scale,
+                                       int scale_by_step, double step, double const_scale, int round_digits,
+                                       double *vals_out_dev, int64_t *first_out, int64_t *last_out, void *stream)
+{
+    if (solver == nullptr || first_out == nullptr || last_out == nullptr || round_digits > 22 || round_digits < -22 ||
+        (n > 0 && (counts_dev == nullptr || vals_out_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    int rc;
+    if ((rc = solver->dev_misc.reserve(256)) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_alignment_count_tail(counts_dev, n, norm_scale, scale_by_step, step, const_scale, round_digits, vals_out_dev,
+                                       first_out, last_out, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
 int rocco_hip_synth_matrix(rocco_hip_solver *solver, void *matrix_dev, int dtype, size_t K, size_t n,
                            size_t row_stride, uint64_t seed, void *stream)
 {

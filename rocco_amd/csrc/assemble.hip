@@ -9,6 +9,7 @@
 // two steps: every (track, locus) cell receives the largest source position that maps to it (atomicMax), then the
 // cells gather their value (or zero).  Integer work and copies only: results equal NumPy's exactly.
 #include "kernels.h"
+#include "round_np.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -197,14 +198,7 @@ __global__ __launch_bounds__(256) void scale_round_kernel(double *__restrict__ f
     if (apply_scale) {
         v = v * const_scale;
     }
-    if (digits > 0) {
-        v = rint(v * pow10) / pow10;
-    } else if (digits == 0) {
-        v = rint(v);
-    } else {
-        v = rint(v / pow10) * pow10;
-    }
-    full[i] = v;
+    full[i] = round_like_numpy(v, pow10, digits);
 }
 
 }  // namespace
@@ -241,10 +235,7 @@ int launch_bigwig_dense_fill(const int64_t *starts_dev, const int64_t *ends_dev,
     hipLaunchKernelGGL(bigwig_scatter_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream,
                        (const long long *)starts_dev, vals_dev, (long long)count, step, full_out_dev);
     const int digits = round_digits;
-    double pow10 = 1.0;
-    for (int d = 0; d < (digits < 0 ? -digits : digits); ++d) {
-        pow10 *= 10.0;  // 10**|d| as NumPy's integer power converted to float64 (exact up to 10**22)
-    }
+    const double pow10 = numpy_pow10(digits);
     hipLaunchKernelGGL(scale_round_kernel, dim3((unsigned)((n_full + 255) / 256)), dim3(256), 0, stream, full_out_dev,
                        (long long)n_full, const_scale, const_scale >= 0.0 ? 1 : 0, pow10, digits);
     ROCCO_HIP_TRY(hipGetLastError());

@@ -1,0 +1,697 @@
+// rocco_amd/csrc/count.hip -- decoded alignment records -> binned coverage, gfx950.
+//
+// Replaces what the reference does with a BAM record after htslib has decoded it:
+//   ccounts_countRegion   (rocco/native/ccounts_backend.c:2400-2573, the alignment branch): filter, fragment, clip, difference
+//                         array, running sum over the bins
+//   ccounts_getChromRange (rocco/native/ccounts_backend.c:1666-1705): first start / last end of a contig
+//   the tail of get_bam_chrom_reads (rocco/readtracks.py:492-517): scaling, positive support, np.round
+// A record is six integers (pos, end = bam_endpos, isize, flag, mapq, mate on the same contig), in file order.
+//
+// Counting is integer work: +1 / -1 into an int32 difference array with integer atomics (the result does not depend on
+// scheduling), an int32 prefix sum, one conversion to float32.  The reference adds +-1.0f into float cells and runs a
+// float sum: equal to the integers while every cell and every running value stays within +-2^24, which
+// launch_count_alignment_records reports per track (the largest magnitude of a cell or a running value).
+//
+// Shape: position-sorted records put the 64 lanes of a wavefront on a few neighbouring bins, so a workgroup first
+// aggregates its records in an LDS window of bins anchored at the lowest bin its records touch, and flushes the
+// non-zero cells with one global atomic each; indices past the window (the far end of a long fragment) go to global
+// memory directly.  The prefix sum is reduce-then-scan over tiles (three launches, no waiting between workgroups).
+#include "kernels.h"
+#include "round_np.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <climits>
+
+namespace rocco {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kRecsPerThread = 2;
+constexpr int kChunk = kThreads * kRecsPerThread;  // records one workgroup aggregates at a time
+constexpr int kWindow = 1024;                      // bins of the LDS window
+constexpr int kScanItems = 8;
+constexpr int kScanTile = kThreads * kScanItems;   // bins per scan tile
+
+#ifdef ROCCO_COUNT_TOOL_MAX_GRID  // (tests/tools/alignment_count_bench.py tries other caps in its stand-alone builds)
+constexpr int kMaxGrid = ROCCO_COUNT_TOOL_MAX_GRID;
+#else
+constexpr int kMaxGrid = ROCCO_COUNT_MAX_GRID;     // workgroups of one counting launch at most
+#endif
+
+static_assert(kChunk == ROCCO_COUNT_CHUNK_RECORDS && kScanTile == ROCCO_COUNT_SCAN_TILE && kWindow == ROCCO_COUNT_WINDOW_BINS &&
+                  kMaxGrid > 0,
+              "rocco_hip.h states the shape");
+
+enum : int { kPaired = 1, kProperPair = 2, kUnmapped = 4, kMateUnmapped = 8, kReverse = 16, kRead2 = 128 };
+
+// what a workgroup needs of its track
+struct CountTrack {
+    long long rec_begin, rec_end;  // its records in the concatenated arrays
+    long long out_offset;          // its counts in the output buffer (floats)
+    long long delta_offset;        // its difference array in the scratch (ints, n_bins + 1 cells)
+    long long read_length, extend_bp, min_template_length, max_insert_size, shift_fwd, shift_rev;
+    int start, end, step, n_bins;
+    int flag_include, flag_exclude, min_mapq, paired_end_mode, one_read_per_bin;
+    int pad_;
+};
+
+// largest k with first[k] <= item (first has K + 1 ascending entries, item < first[K]): tracks without work are skipped
+__device__ __forceinline__ int find_track(const int *__restrict__ first, int K, int item)
+{
+    int lo = 0, hi = K;  // answer in [lo, hi)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= item) {
+            lo = mid;
+        } else {
+            hi = mid;
+        }
+    }
+    return lo;
+}
+
+// One record through the reference's loop (ccounts_backend.c:2420-2560).  Returns false when the record adds nothing;
+// otherwise *i0 is the cell that gains one and *i1 the cell that loses one (-1: none, the one-read-per-bin form).
+__device__ __forceinline__ bool record_cells(const CountTrack &t, long long pos, long long end, long long isize, int flag,
+                                             int mapq, int mate_same, int *i0, int *i1)
+{
+    const long long start64 = t.start, end64 = t.end, step64 = t.step;
+    // the index iterator yields only records that overlap the region as they lie in the file (before any shift or
+    // extension): sam_itr_queryi(start, end) at :2400
+    const long long it_end = end > pos + 1 ? end : pos + 1;
+    if (!(pos < end64 && it_end > start64)) {
+        return false;
+    }
+    if (t.flag_include > 0 && (flag & t.flag_include) != t.flag_include) {  // :2422
+        return false;
+    }
+    if ((flag & t.flag_exclude) != 0) {  // :2427
+        return false;
+    }
+    if (mapq < t.min_mapq) {  // :2431
+        return false;
+    }
+    const long long read_start = pos, read_end = end;
+    long long adj_start, adj_end;
+    if (t.paired_end_mode > 0) {  // :2439-2487
+        if ((flag & kProperPair) == 0 || (flag & kRead2) != 0 || (flag & kMateUnmapped) != 0 || !mate_same) {
+            return false;
+        }
+        const long long min_template = t.min_template_length >= 0 ? t.min_template_length : t.read_length;  // :2416
+        const long long abs_template = isize >= 0 ? isize : -isize;
+        if (abs_template == 0 || abs_template < min_template) {
+            return false;
+        }
+        if (t.max_insert_size > 0 && abs_template > t.max_insert_size) {
+            return false;
+        }
+        if (isize >= 0) {
+            adj_start = read_start;
+            adj_end = read_start + abs_template;
+        } else {
+            adj_end = read_end;
+            adj_start = adj_end - abs_template;
+        }
+        const long long shift = (flag & kReverse) == 0 ? t.shift_fwd : -t.shift_rev;
+        adj_start += shift;
+        adj_end += shift;
+    } else if ((flag & kReverse) == 0) {  // :2490-2503
+        if (t.extend_bp > 0) {
+            adj_start = read_start + t.shift_fwd;
+            adj_end = adj_start + t.extend_bp;
+        } else {
+            adj_start = read_start + t.shift_fwd;
+            adj_end = read_end + t.shift_fwd;
+        }
+    } else {  // :2504-2517
+        if (t.extend_bp > 0) {
+            adj_end = (read_end - 1) - t.shift_rev + 1;
+            adj_start = adj_end - t.extend_bp;
+        } else {
+            adj_start = read_start - t.shift_rev;
+            adj_end = read_end - t.shift_rev;
+        }
+    }
+    if (adj_end <= start64 || adj_start >= end64) {  // :2520
+        return false;
+    }
+    if (adj_start < start64) {
+        adj_start = start64;
+    }
+    if (adj_end > end64) {
+        adj_end = end64;
+    }
+    const unsigned long long length = (unsigned long long)t.n_bins;
+    if (t.one_read_per_bin) {  // :2533-2542
+        const long long mid = (adj_start + adj_end) / 2;
+        const unsigned long long index = (unsigned long long)((mid - start64) / step64);
+        if (index >= length) {
+            return false;
+        }
+        *i0 = (int)index;
+        *i1 = -1;
+        return true;
+    }
+    // (size_t) of a signed quotient, as the reference computes it (:2544-2557)
+    const unsigned long long index0 = (unsigned long long)((adj_start - start64) / step64);
+    unsigned long long index1 = (unsigned long long)(((adj_end - 1) - start64) / step64);
+    if (index0 >= length) {
+        return false;
+    }
+    if (index1 >= length) {
+        index1 = length - 1;
+    }
+    if (index0 > index1) {
+        return false;
+    }
+    *i0 = (int)index0;
+    *i1 = (int)(index1 + 1);  // <= n_bins: the difference array has n_bins + 1 cells
+    return true;
+}
+
+__device__ __forceinline__ int wave_min(int v)
+{
+    for (int off = warpSize / 2; off > 0; off >>= 1) {
+        const int o = __shfl_xor(v, off);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+// chunk_first[k]: the first chunk of track k among all chunks (K + 1 entries).  A workgroup takes chunks blockIdx.x,
+// blockIdx.x + gridDim.x, ...
+__global__ __launch_bounds__(kThreads) void count_records_kernel(
+    const int *__restrict__ pos, const int *__restrict__ end, const int *__restrict__ isize,
+    const unsigned short *__restrict__ flag, const unsigned char *__restrict__ mapq,
+    const unsigned char *__restrict__ mate_same, const CountTrack *__restrict__ tracks, int K,
+    const int *__restrict__ chunk_first, int total_chunks, int *__restrict__ delta)
+{
+    __shared__ int window[kWindow];
+    __shared__ int s_anchor;
+    for (int c = threadIdx.x; c < kWindow; c += kThreads) {
+        window[c] = 0;
+    }
+    for (int chunk = blockIdx.x; chunk < total_chunks; chunk += gridDim.x) {
+        const int k = find_track(chunk_first, K, chunk);
+        const CountTrack t = tracks[k];
+        const long long base = t.rec_begin + (long long)(chunk - chunk_first[k]) * kChunk;
+        int *__restrict__ track_delta = delta + t.delta_offset;
+        if (threadIdx.x == 0) {
+            s_anchor = INT_MAX;
+        }
+        __syncthreads();  // window zeroed (first pass or the last flush), anchor reset
+        int i0[kRecsPerThread], i1[kRecsPerThread];
+        int lowest = INT_MAX;
+#pragma unroll
+        for (int j = 0; j < kRecsPerThread; ++j) {
+            const long long r = base + (long long)j * kThreads + threadIdx.x;
+            i0[j] = -1;
+            i1[j] = -1;
+            if (r < t.rec_end) {
+                int a = -1, b = -1;
+                if (record_cells(t, pos[r], end[r], isize[r], flag[r], mapq[r], mate_same[r], &a, &b)) {
+                    i0[j] = a;
+                    i1[j] = b;
+                    lowest = a < lowest ? a : lowest;  // (i1 > i0 always)
+                }
+            }
+        }
+#ifndef ROCCO_COUNT_NO_LDS_AGGREGATION
+        lowest = wave_min(lowest);
+        if ((threadIdx.x & (warpSize - 1)) == 0 && lowest != INT_MAX) {
+            atomicMin(&s_anchor, lowest);
+        }
+        __syncthreads();
+        const int anchor = s_anchor;
+#pragma unroll
+        for (int j = 0; j < kRecsPerThread; ++j) {
+            if (i0[j] >= 0) {
+                const unsigned off = (unsigned)(i0[j] - anchor);
+                if (off < (unsigned)kWindow) {
+                    atomicAdd(&window[off], 1);
+                } else {
+                    atomicAdd(&track_delta[i0[j]], 1);
+                }
+            }
+            if (i1[j] >= 0) {
+                const unsigned off = (unsigned)(i1[j] - anchor);
+                if (off < (unsigned)kWindow) {
+                    atomicSub(&window[off], 1);
+                } else {
+                    atomicSub(&track_delta[i1[j]], 1);
+                }
+            }
+        }
+        __syncthreads();
+        for (int c = threadIdx.x; c < kWindow; c += kThreads) {
+            const int v = window[c];
+            if (v != 0) {  // (only cells some record of this chunk wrote: anchor + c <= n_bins)
+                atomicAdd(&track_delta[(long long)anchor + c], v);
+                window[c] = 0;
+            }
+        }
+#else
+#pragma unroll
+        for (int j = 0; j < kRecsPerThread; ++j) {
+            if (i0[j] >= 0) {
+                atomicAdd(&track_delta[i0[j]], 1);
+            }
+            if (i1[j] >= 0) {
+                atomicSub(&track_delta[i1[j]], 1);
+            }
+        }
+#endif
+    }
+}
+
+// ---- prefix sum over the bins: tile sums, their exclusive scan per track, scan + convert ---------------------------
+__global__ __launch_bounds__(kThreads) void tile_sum_kernel(const CountTrack *__restrict__ tracks, int K,
+                                                           const int *__restrict__ tile_first, const int *__restrict__ delta,
+                                                           int *__restrict__ tile_sums)
+{
+    using Reduce = hipcub::BlockReduce<int, kThreads>;
+    __shared__ typename Reduce::TempStorage temp;
+    const int tile = blockIdx.x;
+    const int k = find_track(tile_first, K, tile);
+    const long long base = (long long)(tile - tile_first[k]) * kScanTile;
+    const int n_bins = tracks[k].n_bins;
+    int sum = 0;
+    if (!tracks[k].one_read_per_bin) {  // (those cells are the counts themselves: nothing runs across them)
+        const int *__restrict__ cells = delta + tracks[k].delta_offset + base;
+        for (int i = threadIdx.x; i < kScanTile && base + i < n_bins; i += kThreads) {
+            sum += cells[i];
+        }
+    }
+    sum = Reduce(temp).Sum(sum);
+    if (threadIdx.x == 0) {
+        tile_sums[tile] = sum;
+    }
+}
+
+// one workgroup per track: tile_sums[first .. last) becomes its exclusive prefix sum
+__global__ __launch_bounds__(kThreads) void tile_offsets_kernel(const int *__restrict__ tile_first, int *__restrict__ tile_sums)
+{
+    using Scan = hipcub::BlockScan<int, kThreads>;
+    __shared__ typename Scan::TempStorage temp;
+    const int first = tile_first[blockIdx.x], last = tile_first[blockIdx.x + 1];
+    int carry = 0;
+    for (int base = first; base < last; base += kThreads) {
+        const int i = base + threadIdx.x;
+        const int v = i < last ? tile_sums[i] : 0;
+        int exclusive, total;
+        Scan(temp).ExclusiveSum(v, exclusive, total);
+        if (i < last) {
+            tile_sums[i] = carry + exclusive;
+        }
+        carry += total;
+        __syncthreads();  // temp is used again
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void scan_write_kernel(const CountTrack *__restrict__ tracks, int K,
+                                                             const int *__restrict__ tile_first, const int *__restrict__ delta,
+                                                             const int *__restrict__ tile_offsets, int accumulate,
+                                                             float *__restrict__ out, int *__restrict__ max_magnitude)
+{
+    using Load = hipcub::BlockLoad<int, kThreads, kScanItems, hipcub::BLOCK_LOAD_WARP_TRANSPOSE>;
+    using LoadF = hipcub::BlockLoad<float, kThreads, kScanItems, hipcub::BLOCK_LOAD_WARP_TRANSPOSE>;
+    using Store = hipcub::BlockStore<float, kThreads, kScanItems, hipcub::BLOCK_STORE_WARP_TRANSPOSE>;
+    using Scan = hipcub::BlockScan<int, kThreads>;
+    using Reduce = hipcub::BlockReduce<int, kThreads>;
+    __shared__ union {
+        typename Load::TempStorage load;
+        typename LoadF::TempStorage load_f;
+        typename Store::TempStorage store;
+        typename Scan::TempStorage scan;
+        typename Reduce::TempStorage reduce;
+    } temp;
+    const int tile = blockIdx.x;
+    const int k = find_track(tile_first, K, tile);
+    const long long base = (long long)(tile - tile_first[k]) * kScanTile;
+    const int n_bins = tracks[k].n_bins;
+    const int valid = (int)(n_bins - base < kScanTile ? n_bins - base : kScanTile);
+    const int *__restrict__ cells = delta + tracks[k].delta_offset + base;
+    float *__restrict__ track_out = out + tracks[k].out_offset + base;
+    int v[kScanItems], run[kScanItems];
+    Load(temp.load).Load(cells, v, valid, 0);
+    __syncthreads();
+    int biggest = 0;
+    if (tracks[k].one_read_per_bin) {
+#pragma unroll
+        for (int i = 0; i < kScanItems; ++i) {
+            run[i] = v[i];
+        }
+    } else {
+        Scan(temp.scan).InclusiveSum(v, run);
+        __syncthreads();
+        const int offset = tile_offsets[tile];
+#pragma unroll
+        for (int i = 0; i < kScanItems; ++i) {
+            run[i] += offset;
+        }
+        if (threadIdx.x == 0 && base + kScanTile >= n_bins) {
+            const int past = cells[valid];  // the cell behind the last bin takes the -1 of every fragment that reaches it
+            biggest = past < 0 ? -past : past;
+        }
+    }
+    float f[kScanItems];
+#pragma unroll
+    for (int i = 0; i < kScanItems; ++i) {
+        const int a = v[i] < 0 ? -v[i] : v[i], b = run[i] < 0 ? -run[i] : run[i];
+        biggest = a > biggest ? a : biggest;
+        biggest = b > biggest ? b : biggest;
+        f[i] = (float)run[i];
+    }
+    if (accumulate) {  // countBuffer[i] += deltaValue (:2567): one float addition per bin
+        float before[kScanItems];
+        LoadF(temp.load_f).Load(track_out, before, valid, 0.0f);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < kScanItems; ++i) {
+            f[i] = before[i] + f[i];
+        }
+        if (tracks[k].one_read_per_bin) {
+            // the reference adds 1.0f at a time into the used buffer (:2540): one addition gives the same float only while
+            // the buffer holds integers and the sum stays within 2^24, so the sum counts towards the reported magnitude
+#pragma unroll
+            for (int i = 0; i < kScanItems; ++i) {
+                const float m = fabsf(f[i]);
+                const int mi = m < 2147483520.0f ? (int)m : INT_MAX;  // (NaN and infinity: INT_MAX)
+                biggest = mi > biggest ? mi : biggest;
+            }
+        }
+    }
+    Store(temp.store).Store(track_out, f, valid);
+    __syncthreads();
+    biggest = Reduce(temp.reduce).Reduce(biggest, hipcub::Max());
+    if (threadIdx.x == 0 && biggest > 0) {
+        atomicMax(&max_magnitude[k], biggest);
+    }
+}
+
+// ---- ccounts_getChromRange ------------------------------------------------------------------------------------------
+// result[0]: lowest index of a record the first query yields and flag_exclude passes; result[1]: highest index + 1 of
+// one the tail query yields and flag_exclude passes (0: none)
+__global__ __launch_bounds__(kThreads) void chrom_range_kernel(const int *__restrict__ pos, const int *__restrict__ end,
+                                                              const unsigned short *__restrict__ flag, long long n,
+                                                              long long chrom_len, long long tail_start, int flag_exclude,
+                                                              unsigned long long *__restrict__ result)
+{
+    unsigned long long first = ~0ULL, last = 0;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+        if ((flag[i] & flag_exclude) != 0) {
+            continue;
+        }
+        const long long p = pos[i], e = end[i] > p + 1 ? end[i] : p + 1;
+        if (p < chrom_len && e > 0) {  // sam_itr_queryi(0, chromLength), :1666
+            first = (unsigned long long)i < first ? (unsigned long long)i : first;
+        }
+        if (p < chrom_len && e > tail_start) {  // sam_itr_queryi(tailStart, chromLength), :1686
+            last = (unsigned long long)i + 1 > last ? (unsigned long long)i + 1 : last;
+        }
+    }
+    for (int off = warpSize / 2; off > 0; off >>= 1) {
+        const unsigned long long f = __shfl_xor(first, off), l = __shfl_xor(last, off);
+        first = f < first ? f : first;
+        last = l > last ? l : last;
+    }
+    if ((threadIdx.x & (warpSize - 1)) == 0) {
+        if (first != ~0ULL) {
+            atomicMin(&result[0], first);
+        }
+        if (last != 0) {
+            atomicMax(&result[1], last);
+        }
+    }
+}
+
+__global__ void chrom_range_fetch_kernel(const int *__restrict__ pos, const int *__restrict__ end,
+                                         const unsigned long long *__restrict__ result, long long *__restrict__ range)
+{
+    range[0] = result[0] != ~0ULL ? (long long)pos[result[0]] : 0;  // *startOut = record->core.pos (:1677)
+    range[1] = result[1] != 0 ? (long long)end[result[1] - 1] : 0;  // *endOut = bam_endpos(record), the last one (:1701)
+}
+
+// ---- the tail of get_bam_chrom_reads (rocco/readtracks.py:492-517) ----------------------------------------------------
+// vals = counts.astype(float64) * norm_scale; / float(step) if asked; * const_scale if const_scale >= 0; support[0] / [1]:
+// first / last index + 1 with vals > 0 (before rounding); out = np.round(vals, digits)
+__global__ __launch_bounds__(kThreads) void count_tail_kernel(const float *__restrict__ counts, long long n, double norm_scale,
+                                                             int scale_by_step, double step, double const_scale, int apply_const,
+                                                             double pow10, int digits, double *__restrict__ out,
+                                                             unsigned long long *__restrict__ support)
+{
+    unsigned long long first = ~0ULL, last = 0;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+        double v = (double)counts[i];
+        v = v * norm_scale;
+        if (scale_by_step) {
+            v = v / step;
+        }
+        if (apply_const) {
+            v = v * const_scale;
+        }
+        if (v > 0.0) {
+            first = (unsigned long long)i < first ? (unsigned long long)i : first;
+            last = (unsigned long long)i + 1;
+        }
+        out[i] = round_like_numpy(v, pow10, digits);
+    }
+    for (int off = warpSize / 2; off > 0; off >>= 1) {
+        const unsigned long long f = __shfl_xor(first, off), l = __shfl_xor(last, off);
+        first = f < first ? f : first;
+        last = l > last ? l : last;
+    }
+    if ((threadIdx.x & (warpSize - 1)) == 0) {
+        if (first != ~0ULL) {
+            atomicMin(&support[0], first);
+        }
+        if (last != 0) {
+            atomicMax(&support[1], last);
+        }
+    }
+}
+
+size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+
+struct CountPlan {
+    std::vector<CountTrack> tracks;
+    std::vector<int> chunk_first, tile_first;
+    size_t delta_cells = 0;
+    size_t off_tracks = 0, off_chunk_first = 0, off_tile_first = 0, off_max = 0, off_tile_sums = 0, off_delta = 0, bytes = 0;
+};
+
+int make_plan(const int64_t *rec_offsets, size_t K, const rocco_hip_count_options *options,
+              const rocco_hip_count_region *regions, const int64_t *out_offsets, CountPlan &plan)
+{
+    plan.tracks.resize(K);
+    plan.chunk_first.assign(K + 1, 0);
+    plan.tile_first.assign(K + 1, 0);
+    long long chunks = 0, tiles = 0;
+    size_t cells = 0;
+    for (size_t k = 0; k < K; ++k) {
+        const rocco_hip_count_options &o = options[k];
+        const rocco_hip_count_region &r = regions[k];
+        const long long n = rec_offsets[k + 1] - rec_offsets[k];
+        if (n < 0 || n >= (1LL << 31) || rec_offsets[k] < 0 || r.step <= 0 || r.start < 0 || r.end <= r.start || r.n_bins <= 0 ||
+            out_offsets[k] < 0) {
+            set_last_error("count_alignment_records: a track's record range, region or output offset is invalid");
+            return ROCCO_HIP_EINVAL;
+        }
+        CountTrack &t = plan.tracks[k];
+        t.rec_begin = rec_offsets[k];
+        t.rec_end = rec_offsets[k + 1];
+        t.out_offset = out_offsets[k];
+        t.delta_offset = (long long)cells;
+        t.read_length = o.read_length;
+        t.extend_bp = o.extend_bp;
+        t.min_template_length = o.min_template_length;
+        t.max_insert_size = o.max_insert_size;
+        t.shift_fwd = o.shift_fwd;
+        t.shift_rev = o.shift_rev;
+        t.start = r.start;
+        t.end = r.end;
+        t.step = r.step;
+        t.n_bins = r.n_bins;
+        t.flag_include = o.flag_include > 0 ? (o.flag_include & 0xffff) : 0;  // uint16 in ccounts_countOptions
+        t.flag_exclude = o.flag_exclude > 0 ? (o.flag_exclude & 0xffff) : 0;
+        t.min_mapq = o.min_mapq;
+        t.paired_end_mode = o.paired_end_mode;
+        t.one_read_per_bin = o.one_read_per_bin != 0;
+        t.pad_ = 0;
+        plan.chunk_first[k] = (int)chunks;
+        plan.tile_first[k] = (int)tiles;
+        chunks += (n + kChunk - 1) / kChunk;
+        tiles += ((long long)r.n_bins + kScanTile - 1) / kScanTile;
+        cells += ((size_t)r.n_bins + 1 + 3) / 4 * 4;
+        if (chunks >= INT_MAX || tiles >= INT_MAX) {
+            set_last_error("count_alignment_records: too many records or bins for one call");
+            return ROCCO_HIP_EINVAL;
+        }
+    }
+    plan.chunk_first[K] = (int)chunks;
+    plan.tile_first[K] = (int)tiles;
+    plan.delta_cells = cells;
+    size_t at = 0;
+    plan.off_tracks = at;
+    at += align256(K * sizeof(CountTrack));
+    plan.off_chunk_first = at;
+    at += align256((K + 1) * sizeof(int));
+    plan.off_tile_first = at;
+    at += align256((K + 1) * sizeof(int));
+    plan.off_max = at;
+    at += align256(K * sizeof(int));
+    plan.off_tile_sums = at;
+    at += align256((size_t)tiles * sizeof(int));
+    plan.off_delta = at;
+    at += align256(cells * sizeof(int));
+    plan.bytes = at;
+    return ROCCO_HIP_OK;
+}
+
+}  // namespace
+
+size_t count_alignment_scratch_bytes(const int64_t *rec_offsets_host, size_t K, const rocco_hip_count_options *options_host,
+                                     const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host)
+{
+    CountPlan plan;
+    if (make_plan(rec_offsets_host, K, options_host, regions_host, out_offsets_host, plan) != ROCCO_HIP_OK) {
+        return 0;
+    }
+    return plan.bytes;
+}
+
+int launch_count_alignment_records(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
+                                   const uint16_t *flag_dev, const uint8_t *mapq_dev, const uint8_t *mate_same_dev,
+                                   const int64_t *rec_offsets_host, size_t K, const rocco_hip_count_options *options_host,
+                                   const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host,
+                                   int accumulate, float *out_dev, int64_t *max_magnitude_out_host, void *scratch_dev,
+                                   hipStream_t stream)
+{
+    CountPlan plan;
+    const int rc = make_plan(rec_offsets_host, K, options_host, regions_host, out_offsets_host, plan);
+    if (rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    std::vector<int> maxima(K, 0);
+    // the copies below read this call's host vectors: no return before the stream has taken them
+    const int queued = [&]() -> int {
+        char *sc = (char *)scratch_dev;
+        CountTrack *tracks = (CountTrack *)(sc + plan.off_tracks);
+        int *chunk_first = (int *)(sc + plan.off_chunk_first), *tile_first = (int *)(sc + plan.off_tile_first);
+        int *max_dev = (int *)(sc + plan.off_max), *tile_sums = (int *)(sc + plan.off_tile_sums), *delta = (int *)(sc + plan.off_delta);
+        ROCCO_HIP_TRY(hipMemcpyAsync(tracks, plan.tracks.data(), K * sizeof(CountTrack), hipMemcpyHostToDevice, stream));
+        ROCCO_HIP_TRY(hipMemcpyAsync(chunk_first, plan.chunk_first.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+        ROCCO_HIP_TRY(hipMemcpyAsync(tile_first, plan.tile_first.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+        // the difference arrays and, in front of them, the per-track maxima and the tile sums
+        ROCCO_HIP_TRY(hipMemsetAsync(max_dev, 0, plan.bytes - plan.off_max, stream));
+        const int chunks = plan.chunk_first[K], tiles = plan.tile_first[K];
+        if (chunks > 0) {
+            const int grid = chunks < kMaxGrid ? chunks : kMaxGrid;
+            hipLaunchKernelGGL(count_records_kernel, dim3((unsigned)grid), dim3(kThreads), 0, stream, (const int *)pos_dev,
+                               (const int *)end_dev, (const int *)isize_dev, (const unsigned short *)flag_dev,
+                               (const unsigned char *)mapq_dev, (const unsigned char *)mate_same_dev, tracks, (int)K, chunk_first,
+                               chunks, delta);
+        }
+        hipLaunchKernelGGL(tile_sum_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, stream, tracks, (int)K, tile_first, delta,
+                           tile_sums);
+        hipLaunchKernelGGL(tile_offsets_kernel, dim3((unsigned)K), dim3(kThreads), 0, stream, tile_first, tile_sums);
+        hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, stream, tracks, (int)K, tile_first, delta,
+                           tile_sums, accumulate, out_dev, max_dev);
+        ROCCO_HIP_TRY(hipGetLastError());
+        ROCCO_HIP_TRY(hipMemcpyAsync(maxima.data(), max_dev, K * sizeof(int), hipMemcpyDeviceToHost, stream));
+        ROCCO_HIP_TRY(hipStreamSynchronize(stream));  // the scratch buffer is the solver's; the maxima are the caller's guard
+        return ROCCO_HIP_OK;
+    }();
+    if (queued != ROCCO_HIP_OK) {
+        (void)hipStreamSynchronize(stream);  // (copies of plan's vectors or into `maxima` may be pending)
+        (void)hipGetLastError();
+        return queued;
+    }
+    for (size_t k = 0; k < K; ++k) {
+        max_magnitude_out_host[k] = maxima[k];
+    }
+    return ROCCO_HIP_OK;
+}
+
+int launch_alignment_chrom_range(const int32_t *pos_dev, const int32_t *end_dev, const uint16_t *flag_dev, size_t n,
+                                 int64_t chrom_len, int flag_exclude, int64_t *start_out, int64_t *end_out, void *scratch_dev,
+                                 hipStream_t stream)
+{
+    *start_out = 0;
+    *end_out = 0;
+    if (n == 0) {
+        return ROCCO_HIP_OK;
+    }
+    unsigned long long *result = (unsigned long long *)scratch_dev;
+    long long *range = (long long *)(result + 2);
+    const unsigned long long init[2] = {~0ULL, 0ULL};
+    ROCCO_HIP_TRY(hipMemcpyAsync(result, init, sizeof(init), hipMemcpyHostToDevice, stream));
+    const long long tail_start = chrom_len > 2000000LL ? chrom_len - 2000000LL : 0;  // tailCushion (:1684)
+    const size_t blocks = (n + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(chrom_range_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kThreads), 0, stream,
+                       (const int *)pos_dev, (const int *)end_dev, (const unsigned short *)flag_dev, (long long)n,
+                       (long long)chrom_len, tail_start, flag_exclude, result);
+    hipLaunchKernelGGL(chrom_range_fetch_kernel, dim3(1), dim3(1), 0, stream, (const int *)pos_dev, (const int *)end_dev, result,
+                       range);
+    ROCCO_HIP_TRY(hipGetLastError());
+    long long host[2] = {0, 0};
+    ROCCO_HIP_TRY(hipMemcpyAsync(host, range, sizeof(host), hipMemcpyDeviceToHost, stream));
+    ROCCO_HIP_TRY(hipStreamSynchronize(stream));
+    *start_out = host[0];
+    *end_out = host[1];
+    return ROCCO_HIP_OK;
+}
+
+int launch_alignment_count_tail(const float *counts_dev, size_t n, double norm_scale, int scale_by_step, double step,
+                                double const_scale, int round_digits, double *vals_out_dev, int64_t *first_out,
+                                int64_t *last_out, void *scratch_dev, hipStream_t stream)
+{
+    *first_out = -1;
+    *last_out = -1;
+    if (n == 0) {
+        return ROCCO_HIP_OK;
+    }
+    unsigned long long *support = (unsigned long long *)scratch_dev;
+    const unsigned long long init[2] = {~0ULL, 0ULL};
+    ROCCO_HIP_TRY(hipMemcpyAsync(support, init, sizeof(init), hipMemcpyHostToDevice, stream));
+    const size_t blocks = (n + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(count_tail_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kThreads), 0, stream, counts_dev,
+                       (long long)n, norm_scale, scale_by_step, step, const_scale, const_scale >= 0.0 ? 1 : 0,
+                       numpy_pow10(round_digits), round_digits, vals_out_dev, support);
+    ROCCO_HIP_TRY(hipGetLastError());
+    unsigned long long host[2] = {~0ULL, 0ULL};
+    ROCCO_HIP_TRY(hipMemcpyAsync(host, support, sizeof(host), hipMemcpyDeviceToHost, stream));
+    ROCCO_HIP_TRY(hipStreamSynchronize(stream));
+    if (host[1] != 0) {
+        *first_out = (int64_t)host[0];
+        *last_out = (int64_t)host[1] - 1;
+    }
+    return ROCCO_HIP_OK;
+}
+
+}  // namespace rocco
+
+#ifdef ROCCO_COUNT_STANDALONE
+// tests/tools/alignment_count_bench.py builds this file alone (once as it is, once with -DROCCO_COUNT_NO_LDS_AGGREGATION)
+// to time the counting with and without the LDS window; the library itself never defines ROCCO_COUNT_STANDALONE.
+namespace rocco {
+void set_last_error(const std::string &msg) { fprintf(stderr, "count.hip: %s\n", msg.c_str()); }
+}  // namespace rocco
+
+extern "C" size_t rocco_count_standalone_scratch_bytes(const int64_t *rec_offsets, size_t K, const rocco_hip_count_options *options,
+                                                       const rocco_hip_count_region *regions, const int64_t *out_offsets)
+{
+    return rocco::count_alignment_scratch_bytes(rec_offsets, K, options, regions, out_offsets);
+}
+
+extern "C" int rocco_count_standalone(const int32_t *pos, const int32_t *end, const int32_t *isize, const uint16_t *flag,
+                                      const uint8_t *mapq, const uint8_t *mate_same, const int64_t *rec_offsets, size_t K,
+                                      const rocco_hip_count_options *options, const rocco_hip_count_region *regions,
+                                      const int64_t *out_offsets, float *out, int64_t *maxima, void *scratch, void *stream)
+{
+    return rocco::launch_count_alignment_records(pos, end, isize, flag, mapq, mate_same, rec_offsets, K, options, regions,
+                                                 out_offsets, 0, out, maxima, scratch, (hipStream_t)stream);
+}
+#endif

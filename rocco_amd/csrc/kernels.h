@@ -313,6 +313,24 @@ int launch_ecdf_survival(const double *stat_dev, const int *bin_dev, const doubl
 size_t bh_scratch_bytes(size_t m);
 int launch_bh_adjust(const double *pvals_dev, size_t m, double *qvals_out_dev, void *scratch_dev, hipStream_t stream);
 
+// ---- count.hip ------------------------------------------------------------------------------
+size_t count_alignment_scratch_bytes(const int64_t *rec_offsets_host, size_t K, const rocco_hip_count_options *options_host,
+                                     const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host);
+// max_magnitude_out_host[k]: the largest |difference cell| or |running value| of track k (the caller's 2^24 guard)
+int launch_count_alignment_records(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
+                                   const uint16_t *flag_dev, const uint8_t *mapq_dev, const uint8_t *mate_same_dev,
+                                   const int64_t *rec_offsets_host, size_t K, const rocco_hip_count_options *options_host,
+                                   const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host,
+                                   int accumulate, float *out_dev, int64_t *max_magnitude_out_host, void *scratch_dev,
+                                   hipStream_t stream);
+// scratch_dev: 64 bytes
+int launch_alignment_chrom_range(const int32_t *pos_dev, const int32_t *end_dev, const uint16_t *flag_dev, size_t n,
+                                 int64_t chrom_len, int flag_exclude, int64_t *start_out, int64_t *end_out, void *scratch_dev,
+                                 hipStream_t stream);
+int launch_alignment_count_tail(const float *counts_dev, size_t n, double norm_scale, int scale_by_step, double step,
+                                double const_scale, int round_digits, double *vals_out_dev, int64_t *first_out,
+                                int64_t *last_out, void *scratch_dev, hipStream_t stream);
+
 // ---- synth.hip ------------------------------------------------------------------------------
 int launch_synth(void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, uint64_t seed,
                  hipStream_t stream);

@@ -142,6 +142,359 @@ def bigwig_dense_fill(starts, ends, vals, const_scale: float = 1.0, round_digits
 
 
 # --------------------------------------------------------------------------------------------
+# decoded alignment records -> binned coverage (csrc/count.hip)
+# --------------------------------------------------------------------------------------------
+
+POSITION_LIMIT = 1 << 31          # the BAM format's own limit on a position
+EXACT_COUNT_LIMIT = 1 << 24       # float32 holds every integer up to here: the reference's float sums are exact below it
+_RECORD_FIELDS = (("pos", np.int32), ("end", np.int32), ("isize", np.int32), ("flag", np.uint16), ("mapq", np.uint8),
+                  ("mate_same", np.uint8))
+
+
+class CountOptions(ctypes.Structure):
+    """`rocco_hip_count_options` of include/rocco_hip.h."""
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        "flag_include", "flag_exclude", "min_mapq", "read_length", "extend_bp", "paired_end_mode", "min_template_length",
+        "max_insert_size", "shift_fwd", "shift_rev", "one_read_per_bin")]
+
+
+class CountRegion(ctypes.Structure):
+    """`rocco_hip_count_region` of include/rocco_hip.h."""
+    _fields_ = [(name, ctypes.c_int32) for name in ("start", "end", "step", "n_bins")]
+
+
+class AlignmentRecords:
+    """The decoded records of one file on one chromosome, in file order (the order the index iterator yields them): six
+    arrays of one length, 16 bytes per record -- ``pos`` (core.pos), ``end`` (bam_endpos), ``isize`` (core.isize) as
+    int32, ``flag`` (core.flag) as uint16, ``mapq`` (core.qual) and ``mate_same`` (core.mtid == core.tid) as uint8.
+    Any decoder can fill it (pysam, htslib, an integrator's own); CIGAR strings are not needed.  NumPy arrays are checked
+    (integer dtypes, one length, values inside their fields, positions below 2**31) and converted; CUDA tensors must
+    already have the dtypes above."""
+
+    __slots__ = tuple(name for name, _ in _RECORD_FIELDS)
+
+    def __init__(self, pos, end, isize, flag, mapq, mate_same):
+        given = dict(pos=pos, end=end, isize=isize, flag=flag, mapq=mapq, mate_same=mate_same)
+        length = None
+        for name, dtype in _RECORD_FIELDS:
+            a = given[name]
+            if _dp._is_tensor(a):
+                kind = str(a.dtype).replace("torch.", "")
+                if (kind != np.dtype(dtype).name and not (name == "flag" and kind == "int16")) or a.dim() != 1:
+                    raise TypeError(f"AlignmentRecords: `{name}` must be a one-dimensional {np.dtype(dtype).name} tensor")
+                a = a.contiguous()
+                if kind == "uint16":
+                    import torch
+
+                    a = a.view(torch.int16)  # (the bit pattern: torch has few operators for uint16)
+                if name in ("pos", "end") and a.numel() and int(a.min()) < 0:
+                    raise ValueError(f"AlignmentRecords: `{name}` holds a negative position")
+            else:
+                a = np.asarray(a)
+                if a.ndim != 1:
+                    raise ValueError(f"AlignmentRecords: `{name}` must be one-dimensional")
+                if a.dtype.kind == "b" and name == "mate_same":
+                    a = a.astype(np.uint8)
+                if a.dtype.kind not in "iu":
+                    raise TypeError(f"AlignmentRecords: `{name}` must hold integers, not {a.dtype}")
+                if a.size:
+                    low, high = int(a.min()), int(a.max())
+                    if name in ("pos", "end") and (low < 0 or high >= POSITION_LIMIT):
+                        raise ValueError(f"AlignmentRecords: `{name}` must lie in [0, 2**31), the BAM format's limit on a "
+                                         f"position (found {low if low < 0 else high})")
+                    info = np.iinfo(dtype)
+                    if low < info.min or high > info.max:
+                        raise ValueError(f"AlignmentRecords: `{name}` does not fit {np.dtype(dtype).name}")
+                a = np.ascontiguousarray(a, dtype=dtype)
+            n = int(a.shape[0])
+            if length is None:
+                length = n
+            elif n != length:
+                raise ValueError(f"AlignmentRecords: `{name}` has {n} entries, `pos` has {length}")
+            setattr(self, name, a)
+
+    @classmethod
+    def from_numpy(cls, pos, end, isize, flag, mapq, mate_same) -> "AlignmentRecords":
+        return cls(pos, end, isize, flag, mapq, mate_same)
+
+    def __len__(self) -> int:
+        return int(self.pos.shape[0])
+
+    def to(self, device) -> "AlignmentRecords":
+        """The same records with every array on ``device``."""
+        import torch
+
+        out = object.__new__(AlignmentRecords)
+        for name, _ in _RECORD_FIELDS:
+            a = getattr(self, name)
+            if not _dp._is_tensor(a):
+                a = torch.from_numpy(a.view(np.int16) if name == "flag" else a)
+            setattr(out, name, a.to(device))
+        return out
+
+
+def _compute_native_scale_factor(norm_method: str, effective_genome_size: float, step: int, mapped_reads: int,
+                                 norm_read_length: int, scale_factor: float = 1.0) -> float:
+    """rocco/readtracks.py:210-239: the ``norm_scale`` of a file from its whole-file facts (host arithmetic)."""
+    method = "" if norm_method is None else norm_method.lower().replace(" ", "").upper()
+    mapped = max(int(mapped_reads), 1)
+    tile_len_kb = float(step) / 1000.0
+    scale = float(scale_factor)
+    if method == "RPGC":
+        if effective_genome_size is None or float(effective_genome_size) <= 0:
+            raise ValueError("Effective genome size must be positive for RPGC normalization.")
+        current_coverage = (float(mapped) * float(max(int(norm_read_length), 1))) / float(effective_genome_size)
+        return float(scale * (1.0 / max(current_coverage, 1.0e-12)))
+    if method == "RPKM":
+        return float(scale * (1.0 / max((float(mapped) / 1.0e6) * tile_len_kb, 1.0e-12)))
+    if method in {"CPM", "BPM"}:
+        return float(scale * (1.0 / max(float(mapped) / 1.0e6, 1.0e-12)))
+    raise ValueError(f"Normalization method must be one of `RPGC`, `RPKM`, `CPM`, or `BPM`, not `{norm_method}`.")
+
+
+def _check_exact_counts(max_magnitudes: Sequence[int]) -> None:
+    """The counts equal the reference's float32 arithmetic only while every difference cell and every running value stays
+    within 2**24; beyond it the reference's own result depends on the order of its records, and there is no CPU fallback."""
+    for k, magnitude in enumerate(max_magnitudes):
+        if int(magnitude) > EXACT_COUNT_LIMIT:
+            raise RuntimeError(f"alignment counts of track {k} reach {int(magnitude)}, beyond 2**24 = {EXACT_COUNT_LIMIT}: float32 "
+                               "coverage is no longer exact there (the reference's own sums depend on record order)")
+
+
+def _count_options(read_length: int, one_read_per_bin=0, flag_include=0, flag_exclude=0, shift_forward_strand53=0,
+                   shift_reverse_strand53=0, extend_bp=0, max_insert_size=1000, paired_end_mode=0, min_mapping_quality=0,
+                   min_template_length=-1, count_mode="coverage") -> CountOptions:
+    """Keyword names and defaults of the reference's ``count_alignment_region`` (rocco/_hts_counts.c:420-463)."""
+    if count_mode != "coverage":
+        raise ValueError(f"count mode `{count_mode}` is not built: only `coverage` (with or without one_read_per_bin)")
+    return CountOptions(flag_include=int(flag_include), flag_exclude=int(flag_exclude), min_mapq=int(min_mapping_quality),
+                        read_length=int(read_length), extend_bp=int(extend_bp), paired_end_mode=int(paired_end_mode),
+                        min_template_length=int(min_template_length), max_insert_size=int(max_insert_size),
+                        shift_fwd=int(shift_forward_strand53), shift_rev=int(shift_reverse_strand53),
+                        one_read_per_bin=1 if one_read_per_bin else 0)
+
+
+def _records_on_device(records_list: Sequence[AlignmentRecords], dev) -> Tuple[AlignmentRecords, list]:
+    """The records of K tracks as the C ABI takes them: one `AlignmentRecords` on ``dev`` holding all of them back to back
+    and the K + 1 offsets.  Every host array is uploaded once, straight to its place in the concatenated array (a device
+    tensor is copied there); a single track is used where it lies."""
+    import torch
+
+    offsets = [0]
+    for records in records_list:
+        offsets.append(offsets[-1] + len(records))
+    if len(records_list) == 1:
+        return records_list[0].to(dev), offsets
+    out = object.__new__(AlignmentRecords)
+    for name, dtype in _RECORD_FIELDS:
+        buf = torch.empty(offsets[-1], dtype=torch.int16 if name == "flag" else getattr(torch, np.dtype(dtype).name), device=dev)
+        for k, records in enumerate(records_list):
+            a = getattr(records, name)
+            if not _dp._is_tensor(a):
+                a = torch.from_numpy(a.view(np.int16) if name == "flag" else a)
+            buf[offsets[k]: offsets[k + 1]].copy_(a)
+        setattr(out, name, buf)
+    return out, offsets
+
+
+def _records_slice(records: AlignmentRecords, lo: int, hi: int) -> AlignmentRecords:
+    out = object.__new__(AlignmentRecords)
+    for name, _ in _RECORD_FIELDS:
+        setattr(out, name, getattr(records, name)[lo:hi])
+    return out
+
+
+def _count_concatenated(cat: AlignmentRecords, offsets: Sequence[int], regions: Sequence, options_list: Sequence,
+                        lengths: Optional[Sequence[int]] = None, into=None) -> Tuple[list, list]:
+    """`rocco_hip_count_alignment_records_batch` over device records already concatenated.  Returns (one float32 view per
+    track, the largest magnitude the kernels saw per track: `max_magnitude_out_host`); the caller applies the 2**24 guard."""
+    import torch
+
+    lib = _native.load()
+    K = len(offsets) - 1
+    if K <= 0 or len(regions) != K or len(options_list) != K:
+        raise ValueError("one region and one set of options per track are required")
+    dev = cat.pos.device
+    opts = (CountOptions * K)()
+    regs = (CountRegion * K)()
+    rec_offsets = (ctypes.c_longlong * (K + 1))(*[int(o) for o in offsets])
+    out_offsets = (ctypes.c_longlong * K)()
+    total_bins = 0
+    for k, (region, options) in enumerate(zip(regions, options_list)):
+        start, end, step = (int(v) for v in region)
+        if step <= 0 or end <= start:
+            raise ValueError("invalid interval size or genomic segment")  # (the reference's wording, rocco/_hts_counts.c:500-506)
+        if start < 0 or end >= POSITION_LIMIT:
+            raise ValueError("a region must lie in [0, 2**31)")
+        bins = ((end - start - 1) // step) + 1 if lengths is None or lengths[k] is None else int(lengths[k])
+        if bins <= 0:
+            raise ValueError("a track needs at least one bin")
+        opts[k] = options if isinstance(options, CountOptions) else _count_options(**options)
+        regs[k] = CountRegion(start, end, step, bins)
+        out_offsets[k] = total_bins
+        total_bins += (bins + 3) // 4 * 4
+    out = torch.zeros(total_bins, dtype=torch.float32, device=dev)
+    views = [out[out_offsets[k]: out_offsets[k] + regs[k].n_bins] for k in range(K)]
+    if into is not None:
+        for view, before in zip(views, into):
+            view.copy_(before)
+    maxima = (ctypes.c_longlong * K)()
+    solver, stream = _native.solver_for(dev.index), _dp._stream_ptr(out)
+    _native.check(lib.rocco_hip_count_alignment_records_batch(
+        solver.handle, cat.pos.data_ptr(), cat.end.data_ptr(), cat.isize.data_ptr(), cat.flag.data_ptr(),
+        cat.mapq.data_ptr(), cat.mate_same.data_ptr(), rec_offsets, K, ctypes.cast(opts, ctypes.c_void_p),
+        ctypes.cast(regs, ctypes.c_void_p), out_offsets, 0 if into is None else 1, out.data_ptr(), maxima, stream),
+        "rocco_hip_count_alignment_records_batch")
+    return views, [int(m) for m in maxima]
+
+
+def count_alignment_records_batch_device(records_list: Sequence[AlignmentRecords], regions: Sequence, options_list: Sequence,
+                                         device=None, lengths: Optional[Sequence[int]] = None, into=None) -> list:
+    """``ccounts_countRegion`` (rocco/native/ccounts_backend.c:2400-2573) for K tracks in one launch series.
+    ``regions[k]``: (start, end, step); ``options_list[k]``: a `CountOptions` or a dict of `count_alignment_region`'s
+    keywords plus ``read_length``.  Returns one float32 CUDA tensor per track with ((end - start - 1) // step) + 1 bins
+    (``lengths[k]`` bins where given: the reference's countBufferLength).  ``into``: float32 CUDA tensors that stand for
+    the reference's used count buffer: the returned tensors hold their values plus the counts (one float addition per
+    bin); the tensors given are read, not changed.  Raises RuntimeError beyond 2**24."""
+    import torch
+
+    K = len(records_list)
+    if K == 0 or len(regions) != K or len(options_list) != K:
+        raise ValueError("one region and one set of options per track are required")
+    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
+    cat, offsets = _records_on_device(records_list, dev)
+    views, maxima = _count_concatenated(cat, offsets, regions, options_list, lengths, into)
+    _check_exact_counts(maxima)
+    return views
+
+
+def count_alignment_region_from_records(records: AlignmentRecords, start: int, end: int, step: int, read_length: int,
+                                        **kw) -> np.ndarray:
+    """The reference's ``count_alignment_region`` (rocco/_hts_counts.c:420-569) for records already decoded: same keyword
+    names and defaults (``one_read_per_bin``, ``flag_include``, ``flag_exclude``, ``shift_forward_strand53``,
+    ``shift_reverse_strand53``, ``extend_bp``, ``max_insert_size=1000``, ``paired_end_mode``, ``min_mapping_quality``,
+    ``min_template_length=-1``, ``count_mode="coverage"``).  Returns the float32 counts as a NumPy array."""
+    kw.pop("thread_count", None)
+    kw.pop("infer_fragment_length", None)
+    (counts,) = count_alignment_records_batch_device([records], [(start, end, step)], [_count_options(read_length, **kw)])
+    return counts.cpu().numpy()
+
+
+def alignment_chrom_range_from_records(records: AlignmentRecords, chrom_size: int, flag_exclude: int = 0) -> Tuple[int, int]:
+    """``ccounts_getChromRange`` (rocco/native/ccounts_backend.c:1666-1705): (pos of the first record ``flag_exclude``
+    passes, end of the LAST one in file order among the records reaching into the contig's last 2 Mb); 0 where none."""
+    import torch
+
+    lib = _native.load()
+    if _dp._is_tensor(records.pos):
+        dev = records.pos.device
+    else:
+        dev = torch.device(f"cuda:{_dp._device_index()}")
+    r = records.to(dev)
+    start, end = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _native.check(lib.rocco_hip_alignment_chrom_range(
+        _native.solver_for(dev.index).handle, r.pos.data_ptr(), r.end.data_ptr(), r.flag.data_ptr(), len(r), int(chrom_size),
+        max(0, int(flag_exclude)) & 0xFFFF, ctypes.byref(start), ctypes.byref(end), _dp._stream_ptr(r.pos)),
+        "rocco_hip_alignment_chrom_range")
+    return int(start.value), int(end.value)
+
+
+def _count_window(chrom_start: int, chrom_end: int, chrom_size: int, step: int) -> Tuple[int, int]:
+    """rocco/readtracks.py:467-473."""
+    count_start = max(0, (chrom_start // step) * step)
+    count_end = min(chrom_size, int(np.ceil(max(chrom_end, count_start + 1) / float(step)) * step))
+    if count_end <= count_start:
+        count_end = min(chrom_size, count_start + step)
+    return count_start, count_end
+
+
+def _bam_tail(counts_t, count_start: int, step: int, norm_scale: float, scale_by_step: bool, const_scale: float,
+              round_digits: int, bam_file: str, chromosome: str):
+    """rocco/readtracks.py:492-518 on the device: scaling in float64, the positive support, np.round."""
+    import torch
+
+    lib = _native.load()
+    n = int(counts_t.shape[0])
+    vals_t = torch.empty(n, dtype=torch.float64, device=counts_t.device)
+    first, last = ctypes.c_longlong(-1), ctypes.c_longlong(-1)
+    if scale_by_step:
+        logger.info(f"Dividing `vals` by step size (bp): {step}")
+    if const_scale >= 0 and const_scale == 0:
+        logger.warning("You are scaling the values by 0.")
+    _native.check(lib.rocco_hip_alignment_count_tail_f64(
+        _native.solver_for(counts_t.device.index).handle, counts_t.data_ptr(), n, float(norm_scale), 1 if scale_by_step else 0,
+        float(step), float(const_scale), int(round_digits), vals_t.data_ptr(), ctypes.byref(first), ctypes.byref(last),
+        _dp._stream_ptr(counts_t)), "rocco_hip_alignment_count_tail_f64")
+    if first.value < 0:
+        logger.warning("No non-zero values found in BAM file: %s for chromosome: %s. Returning (None,None).", bam_file, chromosome)
+        return None, None
+    first_idx, last_idx = int(first.value), int(last.value) + 1
+    intervals = count_start + (np.arange(first_idx, last_idx, dtype=np.int64) * int(step))
+    return intervals.astype(int), vals_t[first_idx:last_idx].cpu().numpy()
+
+
+def bam_chrom_reads_from_records_batch(records_list: Sequence[AlignmentRecords], chrom_size: int, step: int,
+                                       metadata_list: Sequence[dict], min_mapping_score: int = 10, flag_include=None,
+                                       flag_exclude: int = 3844, center_reads: bool = False, const_scale: float = 1.0,
+                                       round_digits: int = 5, scale_by_step: bool = False, bam_files: Optional[Sequence[str]] = None,
+                                       chromosome: str = ""):
+    """K files of one chromosome in one call: everything ``get_bam_chrom_reads`` does after its metadata lookup
+    (rocco/readtracks.py:439-518), the counting of all files in one launch series.  Returns (interval_matrix,
+    vals_matrix), the two lists `assemble_chrom_matrix` takes; a file without data has ``None`` in both (the reference's
+    two ``(None, None)`` returns, with its warnings), which ``generate_chrom_matrix`` leaves out."""
+    K = len(records_list)
+    if len(metadata_list) != K:
+        raise ValueError("one metadata dict per file is required")
+    names = list(bam_files) if bam_files is not None else [""] * K
+    chrom_size, step = int(chrom_size), int(step)
+    intervals_out, vals_out = [None] * K, [None] * K
+    if K == 0:
+        return intervals_out, vals_out
+    import torch
+
+    given = next((r.pos.device for r in records_list if _dp._is_tensor(r.pos)), None)
+    cat, offsets = _records_on_device(records_list, given if given is not None else torch.device(f"cuda:{_dp._device_index()}"))
+    live, regions, options = [], [], []
+    for k, metadata in enumerate(metadata_list):
+        chrom_start, chrom_end = alignment_chrom_range_from_records(_records_slice(cat, offsets[k], offsets[k + 1]), chrom_size,
+                                                                    max(0, int(flag_exclude)))
+        if chrom_end <= chrom_start:
+            logger.warning("No mapped reads found in BAM file: %s for chromosome: %s. Returning (None,None).", names[k], chromosome)
+            regions.append((0, 1, 1))  # (its place in the concatenated records stays; one bin nobody reads)
+            options.append(_count_options(0))
+            continue
+        live.append(k)
+        regions.append(_count_window(chrom_start, chrom_end, chrom_size, step) + (step,))
+        options.append(_count_options(int(metadata["read_length"]), one_read_per_bin=1 if center_reads else 0,
+                                      flag_include=max(0, int(flag_include or 0)), flag_exclude=max(0, int(flag_exclude)),
+                                      extend_bp=max(0, int(metadata["resolved_extend_bp"])),
+                                      paired_end_mode=1 if bool(metadata["paired_end_mode"]) else 0,
+                                      min_mapping_quality=max(0, int(min_mapping_score))))
+    if live:
+        counts, maxima = _count_concatenated(cat, offsets, regions, options)
+        _check_exact_counts([m if k in live else 0 for k, m in enumerate(maxima)])
+        for k in live:
+            intervals_out[k], vals_out[k] = _bam_tail(counts[k], regions[k][0], step, float(metadata_list[k]["norm_scale"]), scale_by_step,
+                                                      const_scale, round_digits, names[k], chromosome)
+    return intervals_out, vals_out
+
+
+def bam_chrom_reads_from_records(records: AlignmentRecords, chrom_size: int, step: int, metadata: dict, min_mapping_score: int = 10,
+                                 flag_include=None, flag_exclude: int = 3844, center_reads: bool = False, const_scale: float = 1.0,
+                                 round_digits: int = 5, scale_by_step: bool = False, bam_file: str = "", chromosome: str = ""):
+    """What ``get_bam_chrom_reads`` returns for one file (rocco/readtracks.py:439-518), from its decoded records and the
+    dict of ``_get_bam_count_metadata`` (``read_length``, ``resolved_extend_bp``, ``paired_end_mode``, ``norm_scale``:
+    whole-file facts the reader supplies; `_compute_native_scale_factor` makes ``norm_scale``): the count window, the
+    counting, the scaling and the trimming on the device.  ``(None, None)`` with the reference's warnings for an empty
+    range or no positive value; otherwise ``intervals.astype(int)`` and the rounded float64 values.  This is the function
+    to bind behind `get_bam_chrom_reads`."""
+    intervals, vals = bam_chrom_reads_from_records_batch([records], chrom_size, step, [metadata], min_mapping_score, flag_include,
+                                                         flag_exclude, center_reads, const_scale, round_digits, scale_by_step,
+                                                         [bam_file], chromosome)
+    return intervals[0], vals[0]
+
+
+# --------------------------------------------------------------------------------------------
 # the reference's two entry points around the kernels above (same names, arguments, return values and errors)
 # --------------------------------------------------------------------------------------------
 
@@ -181,7 +534,8 @@ def get_bam_chrom_reads(bam_file, *_args, **_kwargs):
     is out of this package's scope.  ``generate_chrom_matrix`` looks this name up in the
     module when it is called, so an integrator puts the reference's reader (or any ``(starts, values)`` source) here."""
     raise RuntimeError("rocco_amd does not decode BAM files: replace rocco_amd.readtracks.get_bam_chrom_reads with the "
-                       f"reference's reader (asked for {bam_file})")
+                       f"reference's reader (asked for {bam_file}); a reader that decodes the records itself binds "
+                       "rocco_amd.readtracks.bam_chrom_reads_from_records behind it, which does the rest on the device")
 
 
 def get_bigwig_chrom_scores(bigwig_file: str, chromosome: str, chrom_sizes_file: str, const_scale: float = 1.0,
