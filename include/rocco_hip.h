@@ -685,6 +685,36 @@ int rocco_hip_alignment_count_tail_f64(rocco_hip_solver *solver, const float *co
                                        int scale_by_step, double step, double const_scale, int round_digits,
                                        double *vals_out_dev, int64_t *first_out, int64_t *last_out, void *stream);
 
+/* ---- decoded alignment records -> one count per (interval, file) ------------------
+ * The counting half of the reference's post-hoc scoring for records already decoded (the six arrays above).
+ *
+ * rocco_hip_count_alignment_intervals_batch: count_alignment_intervals (rocco/_hts_counts.c:571-836) for F files in one
+ *   launch series -- per interval one ccounts_countRegion call (rocco/native/ccounts_backend.c:2400-2573) with region =
+ *   [start, end), intervalSizeBP = end - start and a buffer of one float, as raw_count_matrix (rocco/scores.py:250-341)
+ *   uses it; at flag_exclude = 4, min_mapq = 10, one_read_per_bin = 1 it is also the pysam count of get_ecdf
+ *   (rocco/scores.py:697-713; argued from the shared index iterator and filters, not run: pysam is not a dependency).
+ *   F files x C contigs are T = F * C tracks, track f * C + c, concatenated; rec_offsets_host has T + 1 entries; a track
+ *   may be empty.  Every track's pos must ascend (file order of an indexed BAM).  The P intervals are device arrays
+ *   (contig id in [0, C), start, end; end > start; any order, overlapping, nested or repeated); one option set for the call.
+ *   out_dev is int32 [P][F], row-major: exact integer counts, independent of scheduling.  (The reference adds 1.0f into
+ *   one float per interval: its result is min(count, 2^24), a clamp the caller applies where it wants floats; derived
+ *   from float32 arithmetic, not recorded at that depth.)  track_facts_out_host receives 2 T ints: [2 t] the largest
+ *   max(end, pos + 1) - pos of track t (the width of the candidate window, so one very long record costs time on its
+ *   track, never correctness), [2 t + 1] non-zero when the track's pos does not ascend -- its counts are then undefined
+ *   and the caller refuses them.  One synchronisation, at the end.  P * F < 2^31 - 1.
+ * rocco_hip_count_intervals_shape: shape_out[0..2] = candidate records of one work unit, workgroups of the counting
+ *   launch at most, wavefronts per workgroup (a wavefront takes one unit at a time, in a grid stride). */
+#define ROCCO_COUNT_INTERVALS_UNIT 256
+#define ROCCO_COUNT_INTERVALS_MAX_GRID 1024
+#define ROCCO_COUNT_INTERVALS_WAVES_PER_GROUP 4
+int rocco_hip_count_alignment_intervals_batch(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                              const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mapq_dev,
+                                              const uint8_t *mate_same_dev, const int64_t *rec_offsets_host, size_t F, size_t C,
+                                              const rocco_hip_count_options *options_host, const int32_t *contig_id_dev,
+                                              const int32_t *start_dev, const int32_t *end_region_dev, size_t P, int32_t *out_dev,
+                                              int32_t *track_facts_out_host, void *stream);
+void rocco_hip_count_intervals_shape(int *shape_out);
+
 /* ---- synthetic signal matrices (benchmark / test support, device-resident) -------------------
  * Fills a row-major [K][n] matrix with the counter-based synthetic tracks described in
  * DESIGN.md section 7 (5-decimal background + planted peaks with per-sample dropout); the same

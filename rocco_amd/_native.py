@@ -279,6 +279,12 @@ PROTOTYPES = [
     ("rocco_hip_alignment_count_tail_f64", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double,
       ctypes.c_int, ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_void_p]),
+    # count_alignment_intervals, rocco/_hts_counts.c:571-836 (raw_count_matrix and the null counts of rocco/scores.py)
+    ("rocco_hip_count_alignment_intervals_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      c_ll_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_void_p, c_int_p, ctypes.c_void_p]),
+    ("rocco_hip_count_intervals_shape", None, [c_int_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t,
       ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]),

@@ -1507,6 +1507,44 @@ int rocco_hip_alignment_count_tail_f64(rocco_hip_solver *solver, const float *co
                                        first_out, last_out, solver->dev_misc.ptr, (hipStream_t)stream);
 }
 
+int rocco_hip_count_alignment_intervals_batch(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                              const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mapq_dev,
+                                              const uint8_t *mate_same_dev, const int64_t *rec_offsets_host, size_t F, size_t C,
+                                              const rocco_hip_count_options *options_host, const int32_t *contig_id_dev,
+                                              const int32_t *start_dev, const int32_t *end_region_dev, size_t P, int32_t *out_dev,
+                                              int32_t *track_facts_out_host, void *stream)
+{
+    if (solver == nullptr || F == 0 || C == 0 || P == 0 || rec_offsets_host == nullptr || options_host == nullptr ||
+        contig_id_dev == nullptr || start_dev == nullptr || end_region_dev == nullptr || out_dev == nullptr ||
+        track_facts_out_host == nullptr) {
+        return ROCCO_HIP_EINVAL;
+    }
+    const size_t bytes = count_intervals_scratch_bytes(rec_offsets_host, F, C, P);
+    if (bytes == 0) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (rec_offsets_host[F * C] > rec_offsets_host[0] &&
+        (pos_dev == nullptr || end_dev == nullptr || isize_dev == nullptr || flag_dev == nullptr || mapq_dev == nullptr ||
+         mate_same_dev == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    int rc;
+    if ((rc = solver->dev_misc.reserve(bytes)) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_count_alignment_intervals(pos_dev, end_dev, isize_dev, flag_dev, mapq_dev, mate_same_dev, rec_offsets_host, F, C,
+                                            options_host, contig_id_dev, start_dev, end_region_dev, P, out_dev,
+                                            track_facts_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+void rocco_hip_count_intervals_shape(int *shape_out)
+{
+    shape_out[0] = ROCCO_COUNT_INTERVALS_UNIT;
+    shape_out[1] = ROCCO_COUNT_INTERVALS_MAX_GRID;
+    shape_out[2] = ROCCO_COUNT_INTERVALS_WAVES_PER_GROUP;
+}
+
 int rocco_hip_synth_matrix(rocco_hip_solver *solver, void *matrix_dev, int dtype, size_t K, size_t n,
                            size_t row_stride, uint64_t seed, void *stream)
 {

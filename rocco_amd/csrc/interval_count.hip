@@ -1,0 +1,353 @@
+// rocco_amd/csrc/interval_count.hip -- decoded alignment records -> one count per (interval, file) (DESIGN.md section 0
+// row f6), gfx950.
+//
+// Replaces the counting half of the reference's post-hoc scoring:
+//   count_alignment_intervals (rocco/_hts_counts.c:571-836): one ccounts_countRegion call per interval with
+//                             region = [start, end), intervalSizeBP = end - start and a count buffer of one float
+//   its callers raw_count_matrix (rocco/scores.py:250-341) and, at the null's options, the pysam count of get_ecdf
+//   (rocco/scores.py:697-713)
+// The per-record rule is record_cells of record_cells.h (the copy count.hip uses) with step = end - start, n_bins = 1 and
+// the region taken per interval.
+//
+// F files x C contigs are T = F * C tracks of position-sorted records (track f * C + c), concatenated.  Three steps on
+// the stream, no host synchronisation in between:
+//   interval_track_facts_kernel  per track: the largest span L = max(max(end, pos + 1) - pos) and whether pos ascends
+//   interval_bounds_kernel       per (interval, file): two bisections in the track's pos give the candidates [lo, hi) --
+//                                first pos > start - L, first pos >= end -- and ceil((hi - lo) / UNIT) work units;
+//                                hipcub's exclusive scan turns the unit counts into unit offsets (the total stays on the device)
+//   interval_count_kernel        a fixed grid; a wavefront takes units in a grid stride, finds its pair by bisecting the unit
+//                                offsets, its 64 lanes read consecutive records, record_cells, wave reduction, one integer
+//                                atomicAdd (a plain store where the pair has one unit)
+// Integer counts: the result does not depend on scheduling.  A long record widens L for its whole track: more candidates
+// are read and filtered (time), never a wrong count.
+#include "kernels.h"
+#include "record_cells.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <cstring>
+
+namespace rocco {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWave = 64;
+constexpr int kWavesPerGroup = kThreads / kWave;
+constexpr int kUnit = 256;                       // candidate records of one work unit
+constexpr int kRecsPerLane = kUnit / kWave;
+constexpr int kMaxGrid = ROCCO_COUNT_INTERVALS_MAX_GRID;  // workgroups of the counting launch
+
+static_assert(kUnit == ROCCO_COUNT_INTERVALS_UNIT && kWavesPerGroup == ROCCO_COUNT_INTERVALS_WAVES_PER_GROUP && kMaxGrid > 0 &&
+                  kUnit % kWave == 0,
+              "rocco_hip.h states the shape");
+
+// largest t in [0, T) with offsets[t] <= item (offsets ascends, item < offsets[T]): entries without work are skipped
+__device__ __forceinline__ int find_slot(const long long *__restrict__ offsets, int T, long long item)
+{
+    int lo = 0, hi = T;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= item) {
+            lo = mid;
+        } else {
+            hi = mid;
+        }
+    }
+    return lo;
+}
+
+// facts[2 t]: L of track t; facts[2 t + 1]: 1 when some pos is smaller than the one before it
+__global__ __launch_bounds__(kThreads) void interval_track_facts_kernel(const int *__restrict__ pos, const int *__restrict__ end,
+                                                                       const long long *__restrict__ rec_offsets, int T,
+                                                                       int *__restrict__ facts)
+{
+    const long long first = rec_offsets[0], total = rec_offsets[T];
+    for (long long base = first + (long long)blockIdx.x * kThreads; base < total; base += (long long)gridDim.x * kThreads) {
+        const long long i = base + threadIdx.x;
+        int t = -1, span = 0, unsorted = 0;
+        if (i < total) {
+            t = find_slot(rec_offsets, T, i);
+            const long long p = pos[i], e = end[i];
+            span = (int)((e > p + 1 ? e : p + 1) - p);
+            unsorted = (i > rec_offsets[t] && (long long)pos[i - 1] > p) ? 1 : 0;
+        }
+        const int t0 = __shfl(t, 0);
+        if (__all(t == t0)) {  // (the usual case: a wavefront inside one track)
+            for (int off = kWave / 2; off > 0; off >>= 1) {
+                const int s = __shfl_xor(span, off), u = __shfl_xor(unsorted, off);
+                span = s > span ? s : span;
+                unsorted |= u;
+            }
+            if ((threadIdx.x & (kWave - 1)) == 0 && t0 >= 0) {
+                atomicMax(&facts[2 * t0], span);
+                if (unsorted) {
+                    atomicOr(&facts[2 * t0 + 1], 1);
+                }
+            }
+        } else if (t >= 0) {
+            atomicMax(&facts[2 * t], span);
+            if (unsorted) {
+                atomicOr(&facts[2 * t + 1], 1);
+            }
+        }
+    }
+}
+
+// first index in [lo, hi) with pos[index] >= key (hi where none)
+__device__ __forceinline__ long long lower_bound_pos(const int *__restrict__ pos, long long lo, long long hi, long long key)
+{
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if ((long long)pos[mid] < key) {
+            lo = mid + 1;
+        } else {
+            hi = mid;
+        }
+    }
+    return lo;
+}
+
+// one thread per (interval p, file f), pair = p * F + f: cand_lo / cand_n = its candidates, units = its work units.
+// units has pairs + 1 entries (the last one 0) so that the exclusive scan's last entry is the total.
+__global__ __launch_bounds__(kThreads) void interval_bounds_kernel(const int *__restrict__ pos, const long long *__restrict__ rec_offsets,
+                                                                  const int *__restrict__ facts, int F, int C,
+                                                                  const int *__restrict__ contig_id, const int *__restrict__ start,
+                                                                  const int *__restrict__ end, long long pairs,
+                                                                  long long *__restrict__ cand_lo, int *__restrict__ cand_n,
+                                                                  long long *__restrict__ units)
+{
+    const long long pair = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (pair > pairs) {
+        return;
+    }
+    if (pair == pairs) {
+        units[pair] = 0;
+        return;
+    }
+    const long long p = pair / F;
+    const int f = (int)(pair - p * F);
+    const int c = contig_id[p];
+    const long long s = start[p], e = end[p];
+    long long lo = 0, n = 0;
+    if (c >= 0 && c < C && s >= 0 && e > s) {
+        const int t = f * C + c;
+        const long long b = rec_offsets[t], last = rec_offsets[t + 1];
+        const long long L = facts[2 * t];
+        lo = lower_bound_pos(pos, b, last, s - L + 1);  // first pos > start - L
+        const long long hi = lower_bound_pos(pos, lo, last, e);  // first pos >= end (at or behind lo: start - L < end)
+        n = hi - lo;
+    }
+    cand_lo[pair] = lo;
+    cand_n[pair] = (int)n;
+    units[pair] = (n + kUnit - 1) / kUnit;
+}
+
+__device__ __forceinline__ long long uniform64(long long v)
+{
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)v);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// unit_first: the exclusive scan of units (pairs + 1 entries; unit_first[pairs] is the number of units).  `options` holds
+// the call's option set; its region fields are filled per interval.  out is zeroed before the launch.
+__global__ __launch_bounds__(kThreads) void interval_count_kernel(
+    const int *__restrict__ pos, const int *__restrict__ end, const int *__restrict__ isize,
+    const unsigned short *__restrict__ flag, const unsigned char *__restrict__ mapq,
+    const unsigned char *__restrict__ mate_same, CountTrack options, int F, const int *__restrict__ start,
+    const int *__restrict__ stop, int pairs, const long long *__restrict__ cand_lo, const int *__restrict__ cand_n,
+    const long long *__restrict__ unit_first, int *__restrict__ out)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const long long total_units = unit_first[pairs];
+    const long long stride = (long long)gridDim.x * kWavesPerGroup;
+    for (long long unit = uniform64((long long)blockIdx.x * kWavesPerGroup + (threadIdx.x / kWave)); unit < total_units; unit += stride) {
+        const int pair = find_slot(unit_first, pairs, unit);
+        const int p = pair / F;
+        const long long first_unit = unit_first[pair];
+        const long long lo = cand_lo[pair];
+        const int n = cand_n[pair];
+        CountTrack t = options;
+        t.start = start[p];
+        t.end = stop[p];
+        t.step = t.end - t.start;  // intervalSizeBP = end - start (_hts_counts.c:571-836): one bin
+        t.n_bins = 1;
+        const long long base = lo + (unit - first_unit) * kUnit;
+        const long long limit = lo + n;
+        int count = 0;
+#pragma unroll
+        for (int j = 0; j < kRecsPerLane; ++j) {
+            const long long r = base + j * kWave + lane;
+            if (r < limit) {
+                int i0 = -1, i1 = -1;
+                if (record_cells(t, pos[r], end[r], isize[r], flag[r], mapq[r], mate_same[r], &i0, &i1)) {
+                    count += 1;  // (one bin: i0 == 0)
+                }
+            }
+        }
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+            count += __shfl_xor(count, off);
+        }
+        if (lane == 0 && count != 0) {
+            if (n <= kUnit) {
+                out[pair] = count;  // the pair's only unit
+            } else {
+                atomicAdd(&out[pair], count);
+            }
+        }
+    }
+}
+
+size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+
+struct IntervalPlan {
+    size_t off_rec_offsets = 0, off_facts = 0, off_lo = 0, off_n = 0, off_units = 0, off_unit_first = 0, off_scan = 0;
+    size_t scan_bytes = 0, bytes = 0;
+};
+
+int make_interval_plan(size_t T, size_t pairs, IntervalPlan &plan)
+{
+    size_t scan_bytes = 0;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const long long *)nullptr, (long long *)nullptr, (int)(pairs + 1)) !=
+        hipSuccess) {
+        (void)hipGetLastError();
+        set_last_error("count_alignment_intervals: cannot size the scan");
+        return ROCCO_HIP_EHIP;
+    }
+    size_t at = 0;
+    plan.off_rec_offsets = at;
+    at += align256((T + 1) * sizeof(long long));
+    plan.off_facts = at;
+    at += align256(2 * T * sizeof(int));
+    plan.off_lo = at;
+    at += align256(pairs * sizeof(long long));
+    plan.off_n = at;
+    at += align256(pairs * sizeof(int));
+    plan.off_units = at;
+    at += align256((pairs + 1) * sizeof(long long));
+    plan.off_unit_first = at;
+    at += align256((pairs + 1) * sizeof(long long));
+    plan.off_scan = at;
+    at += align256(scan_bytes > 0 ? scan_bytes : 1);
+    plan.scan_bytes = scan_bytes;
+    plan.bytes = at;
+    return ROCCO_HIP_OK;
+}
+
+int check_interval_shape(const int64_t *rec_offsets_host, size_t F, size_t C, size_t P)
+{
+    if (F == 0 || C == 0 || P == 0 || F >= (1u << 20) || C >= (1u << 20) || F * C >= (size_t)0x7fffffff ||
+        P >= (size_t)0x7fffffff || P * F >= (size_t)0x7ffffffe) {
+        set_last_error("count_alignment_intervals: files x contigs or intervals x files is out of range");
+        return ROCCO_HIP_EINVAL;
+    }
+    const size_t T = F * C;
+    if (rec_offsets_host[0] < 0) {
+        set_last_error("count_alignment_intervals: a track's record range is invalid");
+        return ROCCO_HIP_EINVAL;
+    }
+    for (size_t t = 0; t < T; ++t) {
+        const long long n = rec_offsets_host[t + 1] - rec_offsets_host[t];
+        if (n < 0 || n >= (1LL << 31)) {
+            set_last_error("count_alignment_intervals: a track's record range is invalid");
+            return ROCCO_HIP_EINVAL;
+        }
+    }
+    return ROCCO_HIP_OK;
+}
+
+}  // namespace
+
+size_t count_intervals_scratch_bytes(const int64_t *rec_offsets_host, size_t F, size_t C, size_t P)
+{
+    IntervalPlan plan;
+    if (check_interval_shape(rec_offsets_host, F, C, P) != ROCCO_HIP_OK || make_interval_plan(F * C, P * F, plan) != ROCCO_HIP_OK) {
+        return 0;
+    }
+    return plan.bytes;
+}
+
+int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
+                                     const uint16_t *flag_dev, const uint8_t *mapq_dev, const uint8_t *mate_same_dev,
+                                     const int64_t *rec_offsets_host, size_t F, size_t C, const rocco_hip_count_options *options_host,
+                                     const int32_t *contig_id_dev, const int32_t *start_dev, const int32_t *end_region_dev, size_t P,
+                                     int32_t *out_dev, int32_t *track_facts_out_host, void *scratch_dev, hipStream_t stream)
+{
+    int rc = check_interval_shape(rec_offsets_host, F, C, P);
+    if (rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    const size_t T = F * C, pairs = P * F;
+    IntervalPlan plan;
+    if ((rc = make_interval_plan(T, pairs, plan)) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    const rocco_hip_count_options &o = *options_host;
+    CountTrack options;
+    memset(&options, 0, sizeof(options));
+    options.read_length = o.read_length;
+    options.extend_bp = o.extend_bp;
+    options.min_template_length = o.min_template_length;
+    options.max_insert_size = o.max_insert_size;
+    options.shift_fwd = o.shift_fwd;
+    options.shift_rev = o.shift_rev;
+    options.flag_include = o.flag_include > 0 ? (o.flag_include & 0xffff) : 0;  // uint16 in ccounts_countOptions
+    options.flag_exclude = o.flag_exclude > 0 ? (o.flag_exclude & 0xffff) : 0;
+    options.min_mapq = o.min_mapq;
+    options.paired_end_mode = o.paired_end_mode;
+    options.one_read_per_bin = o.one_read_per_bin != 0;
+    std::vector<long long> offsets(rec_offsets_host, rec_offsets_host + T + 1);
+    std::vector<int> facts(2 * T, 0);
+    const long long records = offsets[T] - offsets[0];
+    // the copies below read this call's host vectors: no return before the stream has taken them
+    const int queued = [&]() -> int {
+        char *sc = (char *)scratch_dev;
+        long long *rec_offsets = (long long *)(sc + plan.off_rec_offsets), *cand_lo = (long long *)(sc + plan.off_lo);
+        long long *units = (long long *)(sc + plan.off_units), *unit_first = (long long *)(sc + plan.off_unit_first);
+        int *facts_dev = (int *)(sc + plan.off_facts), *cand_n = (int *)(sc + plan.off_n);
+        ROCCO_HIP_TRY(hipMemcpyAsync(rec_offsets, offsets.data(), (T + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+        ROCCO_HIP_TRY(hipMemsetAsync(facts_dev, 0, 2 * T * sizeof(int), stream));
+        ROCCO_HIP_TRY(hipMemsetAsync(out_dev, 0, pairs * sizeof(int), stream));
+        if (records > 0) {
+            const long long blocks = (records + kThreads - 1) / kThreads;
+            hipLaunchKernelGGL(interval_track_facts_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kThreads), 0, stream,
+                               (const int *)pos_dev, (const int *)end_dev, rec_offsets, (int)T, facts_dev);
+        }
+        hipLaunchKernelGGL(interval_bounds_kernel, dim3((unsigned)((pairs + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
+                           (const int *)pos_dev, rec_offsets, facts_dev, (int)F, (int)C, (const int *)contig_id_dev,
+                           (const int *)start_dev, (const int *)end_region_dev, (long long)pairs, cand_lo, cand_n, units);
+        ROCCO_HIP_TRY(hipGetLastError());
+        size_t scan_bytes = plan.scan_bytes;
+        ROCCO_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc + plan.off_scan, scan_bytes, (const long long *)units, unit_first,
+                                                       (int)(pairs + 1), stream));
+        if (records > 0) {
+            // at least one wavefront per pair is the most the launch can use when every pair has one unit; pairs with many
+            // units are reached by the grid stride
+            const size_t wanted = (pairs + kWavesPerGroup - 1) / kWavesPerGroup;
+            const size_t by_records = (size_t)((records + kUnit - 1) / kUnit + kWavesPerGroup - 1) / kWavesPerGroup;
+            size_t grid = wanted > by_records ? wanted : by_records;
+            grid = grid < (size_t)kMaxGrid ? grid : (size_t)kMaxGrid;
+            hipLaunchKernelGGL(interval_count_kernel, dim3((unsigned)grid), dim3(kThreads), 0, stream, (const int *)pos_dev,
+                               (const int *)end_dev, (const int *)isize_dev, (const unsigned short *)flag_dev,
+                               (const unsigned char *)mapq_dev, (const unsigned char *)mate_same_dev, options, (int)F,
+                               (const int *)start_dev, (const int *)end_region_dev, (int)pairs, cand_lo, cand_n, unit_first,
+                               (int *)out_dev);
+            ROCCO_HIP_TRY(hipGetLastError());
+        }
+        ROCCO_HIP_TRY(hipMemcpyAsync(facts.data(), facts_dev, 2 * T * sizeof(int), hipMemcpyDeviceToHost, stream));
+        ROCCO_HIP_TRY(hipStreamSynchronize(stream));  // the scratch buffer is the solver's; the facts are the caller's guard
+        return ROCCO_HIP_OK;
+    }();
+    if (queued != ROCCO_HIP_OK) {
+        (void)hipStreamSynchronize(stream);  // (copies of this call's vectors may be pending)
+        (void)hipGetLastError();
+        return queued;
+    }
+    for (size_t i = 0; i < 2 * T; ++i) {
+        track_facts_out_host[i] = facts[i];
+    }
+    return ROCCO_HIP_OK;
+}
+
+}  // namespace rocco

@@ -331,6 +331,16 @@ int launch_alignment_count_tail(const float *counts_dev, size_t n, double norm_s
                                 double const_scale, int round_digits, double *vals_out_dev, int64_t *first_out,
                                 int64_t *last_out, void *scratch_dev, hipStream_t stream);
 
+// ---- interval_count.hip -----------------------------------------------------------------------
+// 0: the shape is out of range
+size_t count_intervals_scratch_bytes(const int64_t *rec_offsets_host, size_t F, size_t C, size_t P);
+// out_dev: int32 [P][F]; track_facts_out_host: 2 * F * C ints (largest span, pos does not ascend)
+int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
+                                     const uint16_t *flag_dev, const uint8_t *mapq_dev, const uint8_t *mate_same_dev,
+                                     const int64_t *rec_offsets_host, size_t F, size_t C, const rocco_hip_count_options *options_host,
+                                     const int32_t *contig_id_dev, const int32_t *start_dev, const int32_t *end_region_dev, size_t P,
+                                     int32_t *out_dev, int32_t *track_facts_out_host, void *scratch_dev, hipStream_t stream);
+
 // ---- synth.hip ------------------------------------------------------------------------------
 int launch_synth(void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, uint64_t seed,
                  hipStream_t stream);

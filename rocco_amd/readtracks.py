@@ -495,6 +495,93 @@ def bam_chrom_reads_from_records(records: AlignmentRecords, chrom_size: int, ste
 
 
 # --------------------------------------------------------------------------------------------
+# decoded alignment records -> one count per (interval, file) (csrc/interval_count.hip)
+# --------------------------------------------------------------------------------------------
+
+def count_intervals_shape() -> dict:
+    """`rocco_hip_count_intervals_shape`: the sizes at which the interval kernels change path."""
+    shape = (ctypes.c_int * 3)()
+    _native.load().rocco_hip_count_intervals_shape(shape)
+    return {"unit_records": int(shape[0]), "max_grid": int(shape[1]), "waves_per_group": int(shape[2])}
+
+
+def _check_intervals(chromosomes, starts, ends) -> Tuple[list, np.ndarray, np.ndarray]:
+    """The argument checks of the reference's ``count_alignment_intervals`` (rocco/_hts_counts.c:571-836), its words where
+    it has them."""
+    chroms = [str(c) for c in chromosomes]
+    starts_h, ends_h = np.asarray(starts), np.asarray(ends)
+    if starts_h.ndim != 1 or ends_h.ndim != 1 or len(chroms) != starts_h.shape[0] or len(chroms) != ends_h.shape[0]:
+        raise ValueError("`chromosomes`, `starts`, and `ends` must have the same length")
+    if len(chroms) == 0:
+        return chroms, np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+    if starts_h.dtype.kind not in "iu" or ends_h.dtype.kind not in "iu":
+        raise TypeError("starts and ends must hold integers")
+    starts_h, ends_h = starts_h.astype(np.int64), ends_h.astype(np.int64)
+    if np.any(ends_h <= starts_h):
+        raise ValueError("each interval must satisfy end > start")
+    if int(starts_h.min()) < 0 or int(ends_h.max()) >= POSITION_LIMIT:
+        raise ValueError("interval positions must lie in [0, 2**31)")
+    return chroms, starts_h.astype(np.int32), ends_h.astype(np.int32)
+
+
+def count_alignment_intervals_batch_device(records_by_file: Sequence[dict], chroms, starts, ends, device=None, **options):
+    """``count_alignment_intervals`` (rocco/_hts_counts.c:571-836: one ``ccounts_countRegion`` per interval, region =
+    [start, end), one bin) for F files in one launch series.  ``records_by_file[f]``: ``{contig: AlignmentRecords}`` of file
+    f, every track in coordinate order (the file order of an indexed BAM); ``chroms`` / ``starts`` / ``ends``: the P
+    intervals, in any order.  ``options``: `count_alignment_region`'s keywords (``read_length`` defaults to 0; only the
+    paired-end template floor reads it).  Returns the exact counts, an int32 CUDA tensor [P, F]; the reference's float is
+    ``min(count, 2**24)`` (`count_alignment_intervals_from_records`)."""
+    import torch
+
+    F = len(records_by_file)
+    if F == 0:
+        raise ValueError("no files")
+    chrom_list, starts_h, ends_h = _check_intervals(chroms, starts, ends)
+    opts = _count_options(int(options.pop("read_length", 0)), **options)
+    P = len(chrom_list)
+    contigs = list(dict.fromkeys(chrom_list))
+    for records in records_by_file:
+        for contig in contigs:
+            if contig not in records:
+                raise ValueError("chromosome not found in alignment header")
+    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
+    if P == 0:
+        return torch.zeros((0, F), dtype=torch.int32, device=dev)
+    C = len(contigs)
+    index = {contig: c for c, contig in enumerate(contigs)}
+    ids_h = np.fromiter((index[c] for c in chrom_list), dtype=np.int32, count=P)
+    tracks = [records_by_file[f][contig] for f in range(F) for contig in contigs]
+    cat, offsets = _records_on_device(tracks, dev)
+    lib = _native.load()
+    ids_t, starts_t, ends_t = (torch.from_numpy(a).to(dev) for a in (ids_h, starts_h, ends_h))
+    out = torch.empty((P, F), dtype=torch.int32, device=dev)
+    rec_offsets = (ctypes.c_longlong * (F * C + 1))(*[int(o) for o in offsets])
+    facts = (ctypes.c_int * (2 * F * C))()
+    solver, stream = _native.solver_for(dev.index), _dp._stream_ptr(out)
+    _native.check(lib.rocco_hip_count_alignment_intervals_batch(
+        solver.handle, cat.pos.data_ptr(), cat.end.data_ptr(), cat.isize.data_ptr(), cat.flag.data_ptr(), cat.mapq.data_ptr(),
+        cat.mate_same.data_ptr(), rec_offsets, F, C, ctypes.byref(opts), ids_t.data_ptr(), starts_t.data_ptr(), ends_t.data_ptr(),
+        P, out.data_ptr(), facts, stream), "rocco_hip_count_alignment_intervals_batch")
+    for t in range(F * C):
+        if facts[2 * t + 1]:
+            raise ValueError(f"the records of file {t // C} on {contigs[t % C]} are not in coordinate order: the interval "
+                             "counter needs the file order of an indexed BAM")
+    return out
+
+
+def count_alignment_intervals_from_records(records_by_chrom: dict, chromosomes, starts, ends, **kw) -> np.ndarray:
+    """The reference's ``count_alignment_intervals`` (rocco/_hts_counts.c:571-836) for one file's decoded records
+    (``{contig: AlignmentRecords}``): same keyword names and defaults as `count_alignment_region_from_records`
+    (``thread_count`` and ``infer_fragment_length`` are accepted and ignored).  Returns float32 counts, one per interval,
+    clamped at 2**24: the reference adds 1.0f into one float, and float32(2**24) + 1 rounds back to 2**24 (derived from
+    float32 arithmetic, not recorded from the reference at that depth)."""
+    kw.pop("thread_count", None)
+    kw.pop("infer_fragment_length", None)
+    counts = count_alignment_intervals_batch_device([records_by_chrom], chromosomes, starts, ends, **kw)
+    return np.minimum(counts[:, 0].cpu().numpy(), EXACT_COUNT_LIMIT).astype(np.float32)
+
+
+# --------------------------------------------------------------------------------------------
 # the reference's two entry points around the kernels above (same names, arguments, return values and errors)
 # --------------------------------------------------------------------------------------------
 
