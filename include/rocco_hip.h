@@ -563,11 +563,15 @@ int rocco_hip_soft_counts_f64(rocco_hip_solver *solver, const double *scores_dev
 /* ---- post-hoc peak scoring: the per-peak arithmetic (rocco/scores.py:180-194, 128-141, 560-583) ----
  * rocco_hip_peak_signal_stat_f64: counts_dev is [n_peaks][n_samples] (scaled counts, row-major), lengths_dev the peak
  *   lengths; stat_out[p] = np.percentile(log2(max(counts[p] * row_scale / max(int(length), 1) + pc, pc)), percentile)
- *   (`_peak_signal_stat`; the logarithm correctly rounded, see rocco_hip_log_scale_f64; NaN in a row gives NaN).
+ *   (`_peak_signal_stat`; the logarithm correctly rounded, see rocco_hip_log_scale_f64; np.percentile's method "linear":
+ *   virtual index (n_samples - 1) * (percentile / 100); max is np.maximum: a NaN count gives a NaN statistic, and so does
+ *   an interpolation between two equal infinities, as in NumPy).
  * rocco_hip_ecdf_survival_f64: bin_dev[p] selects the sorted null values null_values_dev[null_offsets_dev[b] ..
- *   null_offsets_dev[b + 1]); pvals_out[p] = (size - searchsorted_left(null, stat[p]) + 1) / (size + 1) (`EmpiricalNull.survival`).
+ *   null_offsets_dev[b + 1]); pvals_out[p] = (size - searchsorted_left(null, stat[p]) + 1) / (size + 1) (`EmpiricalNull.survival`;
+ *   NumPy's order: a NaN statistic lies after every number, NaN null values are sorted last).
  * rocco_hip_bh_adjust_f64: Benjamini-Hochberg adjusted p-values as scipy.stats.false_discovery_control(ps, method="bh")
- *   computes them for m > 1 (p * (m / rank), running minimum from the largest rank down, clip to [0, 1]). */
+ *   computes them for m > 1 (p * (m / rank), running minimum from the largest rank down, clip to [0, 1]).  The caller
+ *   guarantees 0 <= p <= 1 (SciPy raises otherwise; rocco_amd.scores checks it); -0.0 counts as 0. */
 int rocco_hip_peak_signal_stat_f64(rocco_hip_solver *solver, const double *counts_dev, const double *lengths_dev, size_t n_peaks,
                                    size_t n_samples, double row_scale, double pc, double percentile, double *stat_out_dev, void *stream);
 int rocco_hip_ecdf_survival_f64(rocco_hip_solver *solver, const double *stat_dev, const int *bin_dev, const double *null_values_dev,

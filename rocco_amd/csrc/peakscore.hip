@@ -1,13 +1,16 @@
 // rocco_amd/csrc/peakscore.hip -- the per-peak arithmetic of the post-hoc peak scoring (SURVEY.md section 8 (f) item 4;
 // rocco/scores.py:180-194, 128-141, 560-583), gfx950.  Counting reads over peaks and over the random background regions
 // of the empirical nulls is BAM work and stays with the reference's readers; what follows it is here:
-//   * signal value of a peak: the 75th percentile (np.percentile's linear interpolation) over the samples of
-//     log2(max(count * row_scale / length + pc, pc)) -- one lane per peak, the two order statistics by rank counting
-//     (K samples: tens), the logarithm correctly rounded (log2_cr.h);
+//   * signal value of a peak: a percentile (np.percentile's method "linear": virtual index (K - 1) q, _lerp) over the
+//     samples of log2(np.maximum(count * row_scale / length + pc, pc)) -- one lane per peak, the two order statistics by
+//     rank counting (K samples: tens), the logarithm correctly rounded (log2_cr.h);
 //   * p-value: finite-sample right-tail survival against the sorted null of the peak's length bin,
-//     (size - lower_bound + 1) / (size + 1);
+//     (size - lower_bound + 1) / (size + 1), lower_bound as np.searchsorted(..., "left");
 //   * q-values: Benjamini-Hochberg as scipy.stats.false_discovery_control applies it -- sort, p * (m / rank),
 //     running minimum from the largest rank down, back to the input order, clip to [0, 1].
+// Non-finite values follow NumPy / SciPy: a NaN count goes through the maximum and makes the peak's statistic NaN, as
+// does an interpolation between two equal infinities (inf - inf in _lerp); a NaN statistic sorts after every null value
+// (lower_bound = size); -0.0 is a zero among the p-values.  (The host refuses p-values that are NaN or outside [0, 1].)
 #include "kernels.h"
 #include "log2_cr.h"
 
@@ -29,12 +32,13 @@ __global__ __launch_bounds__(256) void peak_transform_kernel(const double *__res
     const long long p = i / K;
     const long long len_i = (long long)lengths[p];
     const double factor = row_scale / (double)((len_i > 1) ? len_i : 1);  // float(row_scale) / float(max(int(length), 1))
-    const double t = fmax(counts[i] * factor + pc, pc);
+    const double v = counts[i] * factor + pc;
+    const double t = (v != v) ? v : fmax(v, pc);  // np.maximum: a NaN goes through (fmax would drop it)
     transformed[i] = (t > 0.0 && t < INFINITY) ? log2_correctly_rounded(t) : log2(t);
 }
 
 // np.percentile(row, q), method "linear", of every row of a [P][K] matrix: one lane per row, the two order statistics by
-// rank counting
+// rank counting; a row that holds a NaN answers NaN
 __global__ __launch_bounds__(256) void row_percentile_kernel(const double *__restrict__ x, long long P, int K, double percentile,
                                                             double *__restrict__ out)
 {
@@ -43,9 +47,12 @@ __global__ __launch_bounds__(256) void row_percentile_kernel(const double *__res
         return;
     }
     const double *__restrict__ row = x + p * K;
-    // virtual index n q + (1 - q) - 1 in NumPy's own expression (alpha = beta = 1)
+    // NumPy's _quantile for method "linear": virtual index (n - 1) * q -- not the algebraically equal
+    // n q + (1 - q) - 1 of the other methods' general form, which rounds differently --, previous = floor, next =
+    // previous + 1, gamma = virtual index - previous; at n - 1 both indexes are the last one (the difference is then
+    // zero, or an infinity minus itself -- NaN --, whatever gamma is)
     const double q = percentile / 100.0;
-    const double vi = (double)K * q + (1.0 + q * (1.0 - 1.0 - 1.0)) - 1.0;
+    const double vi = (double)(K - 1) * q;
     int prev = (int)floor(vi);
     const double gamma = vi - (double)prev;
     int next = prev + 1;
@@ -93,7 +100,8 @@ __global__ __launch_bounds__(256) void survival_kernel(const double *__restrict_
     long long lo = lo0, hi = hi0;  // np.searchsorted(values, x, side="left")
     while (lo < hi) {
         const long long mid = lo + (hi - lo) / 2;
-        if (null_values[mid] < x) {
+        const double v = null_values[mid];
+        if (v < x || (x != x && v == v)) {  // NumPy's order: a NaN sorts after every number (and NaN nulls sort last)
             lo = mid + 1;
         } else {
             hi = mid;
@@ -110,7 +118,9 @@ __global__ __launch_bounds__(256) void bh_keys_kernel(const double *__restrict__
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < m) {
-        key[i] = (u64)__double_as_longlong(p[i]);  // p >= 0: the bit patterns order like the numbers
+        // 0 <= p <= 1 (the host refuses anything else): the bit patterns order like the numbers, once -0.0 is the zero it is
+        const double v = p[i];
+        key[i] = (v == 0.0) ? (u64)0 : (u64)__double_as_longlong(v);
         idx[i] = (unsigned)i;
     }
 }

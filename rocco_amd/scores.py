@@ -78,10 +78,13 @@ def _peak_signal_stat(vals, length, row_scale: float = 1000.0, pc: float = 1.0, 
 
 
 def benjamini_hochberg_device(pvals_t):
-    """scipy.stats.false_discovery_control(ps, method="bh") (rocco/scores.py:583) on a float64 CUDA tensor."""
+    """scipy.stats.false_discovery_control(ps, method="bh") (rocco/scores.py:583) on a float64 CUDA tensor.  As SciPy, a
+    NaN or a value outside [0, 1] is refused (one reduction on the device, read back before the kernels are queued)."""
     import torch
 
     m = int(pvals_t.shape[0])
+    if m > 0 and not bool(((pvals_t >= 0.0) & (pvals_t <= 1.0)).all()):  # (a NaN fails both comparisons)
+        raise ValueError("`ps` must include only numbers between 0 and 1.")
     if m <= 1:
         return pvals_t.clone()
     out = torch.empty_like(pvals_t)
