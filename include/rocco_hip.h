@@ -164,7 +164,11 @@ int rocco_hip_solve_penalized_chain_f64(rocco_hip_solver *solver, const double *
  * seeds are formed as the reference does (rocco/dp.py:110-111: lower = min(s) - sum(c) - 1,
  * upper = max(s) + sum(c) + 1): min / max are computed on the device (exact), `sum_costs` must be
  * supplied by the caller as NumPy's pairwise np.sum(switch_costs) gives it, because its last bits
- * fix the midpoint sequence. */
+ * fix the midpoint sequence.
+ * `max_iter` is per task and may be any count from 0 (the bracket's upper end is the answer: 2 evaluations) upwards;
+ * every task of a batch may carry its own.  A NEGATIVE `max_iter` in any task makes the whole call return
+ * ROCCO_HIP_EINVAL with nothing launched and `results` untouched.  (The reference's `for _ in range(max_iter)`,
+ * rocco/dp.py:141, takes no step for a negative count; rocco_amd/dp.py gives its callers that behaviour by passing 0.) */
 typedef struct {
     const double *scores_dev;       /* n doubles                                        */
     const double *switch_costs_dev; /* n-1 doubles or NULL (use gamma)                  */
@@ -172,7 +176,7 @@ typedef struct {
     size_t n;
     long long target_count;         /* int(floor(n * budget)), rocco/dp.py:197          */
     double sum_costs;               /* np.sum(switch_costs), rocco/dp.py:110-111        */
-    int max_iter;                   /* 60 in the reference (rocco/dp.py:93)             */
+    int max_iter;                   /* >= 0; the reference's default is 60 (dp.py:93)   */
     uint8_t *solution_dev;          /* n bytes out                                      */
 } rocco_hip_budget_task;
 

@@ -276,8 +276,22 @@ def calibrate_selection_penalty_device(scores_t, switch_costs, target_count: int
     return calibrate_batch_device([scores_t], [switch_costs], [target_count], max_iter=max_iter)[0]
 
 
-def calibrate_batch_device(scores_list, switch_costs_list, target_counts, max_iter: int = 60, score_stats=None):
+def _max_iters(max_iter, k: int):
+    """One step count per problem from an int or a sequence of k ints.  A negative count is 0 steps, as the
+    reference's `for _ in range(max_iter)` makes it (rocco/dp.py:141); the C ABI itself refuses one."""
+    if np.ndim(max_iter) == 0:
+        return [max(0, int(max_iter))] * k
+    steps = [max(0, int(m)) for m in max_iter]
+    if len(steps) != k:
+        raise ValueError("`max_iter` must be an int or hold one int per problem")
+    return steps
+
+
+def calibrate_batch_device(scores_list, switch_costs_list, target_counts, max_iter=60, score_stats=None):
     """One device launch sequence for several chromosomes (rocco_hip_solve_budget_batch_f64).
+
+    `max_iter`: the bisection steps of rocco/dp.py:93,141, one int for the batch or one per problem (the task struct
+    carries its own).
 
     `score_stats`: optional [k, 3] float64 HOST array (NumPy, or a CPU tensor whose copy from the device has
     completed) of np.min, np.max and sum |.| of every score array as score_central_tendency_chrom_batch_device
@@ -292,6 +306,7 @@ def calibrate_batch_device(scores_list, switch_costs_list, target_counts, max_it
     results = (_native.BudgetResult * k)()
     keep = []
     sols = []
+    steps = _max_iters(max_iter, k)
     for i, (s_t, costs, target) in enumerate(zip(scores_list, switch_costs_list, target_counts)):
         n = int(s_t.shape[0])
         if n == 0:
@@ -306,7 +321,7 @@ def calibrate_batch_device(scores_list, switch_costs_list, target_counts, max_it
         tasks[i].n = n
         tasks[i].target_count = int(target)
         tasks[i].sum_costs = _sum_costs(n, costs_t, gamma)
-        tasks[i].max_iter = int(max_iter)
+        tasks[i].max_iter = steps[i]
         tasks[i].solution_dev = sol_t.data_ptr()
     solver = _native.solver_for(device.index)
     if score_stats is not None:
@@ -332,7 +347,7 @@ def calibrate_batch_device(scores_list, switch_costs_list, target_counts, max_it
 def calibrate_selection_penalty(scores, switch_costs, target_count: int,
                                 max_iter: int = 60) -> Tuple[float, np.ndarray, float, int]:
     r"""Find a selection penalty whose solution selects at most `target_count` loci, by the
-    reference's bracket + 60-step bisection (rocco/dp.py:89-164).  Returns
+    reference's bracket + `max_iter`-step bisection (rocco/dp.py:89-164; a negative `max_iter` is no step).  Returns
     ``(upper, best_solution, best_value, best_count)``."""
     _native.load()
     if not _is_tensor(scores) and np.asarray(scores).shape[0] == 0:

@@ -343,3 +343,96 @@ def test_envelope_fixed_penalties(oracle, n):
                 assert np.array_equal(sol, o_sol) and cnt == o_cnt, (rung, kind, n, lam, info)
                 assert ec.values_agree(val, o_val, o_cnt, s, lam, info["path"] == 2, sequential=True), (
                     rung, kind, n, lam, val, o_val, info)
+
+
+# ---- off the reference's default of 60 bisection steps (inputs: tests/bisection_steps_cases.py; the same step counts
+# run on the GPU in tests/test_gpu_calibration_steps.py, so a failure there can be placed: search.cpp here, the
+# directors' replays and the chains there) ----
+
+def _off_sixty_agree(oracle, kind, n, max_iter, where, depths=(1, 2, 3), exact=(False, True)):
+    import bisection_steps_cases as bs
+    import envelope_cases as ec
+
+    s, gamma, target = bs.host_logic_problem(kind, n, 0)
+    ref = bs.reference(oracle, ("host", kind, n), s, gamma, target, max_iter)
+    assert ref[4] == max_iter + 2, (where, ref[4])
+    for force_exact in exact:
+        for depth in (depths[:1] if force_exact else depths):  # (the exact evaluator's trees have a depth of their own)
+            pen, sol, val, cnt, info = hl.calibrate(s, gamma, target, max_iter=max_iter, spec_depth=depth, force_exact=force_exact)
+            at = (where, kind, n, gamma, target, max_iter, depth, force_exact, info)
+            assert pen == ref[0], (at, pen, ref[0])
+            assert cnt == ref[3], (at, cnt, ref[3])
+            assert np.array_equal(sol, ref[1]), at
+            assert ec.values_agree(val, ref[2], ref[3], s, ref[0], info["path"] == 2, sequential=True), (at, val, ref[2])
+            assert info["evaluations"] == max_iter + 2, at
+            if force_exact:
+                assert info["path"] == 2, at
+
+
+def _step_counts():
+    import bisection_steps_cases as bs
+
+    return bs.STEP_COUNTS
+
+
+@pytest.mark.parametrize("max_iter", _step_counts())
+def test_calibration_off_sixty_steps(oracle, max_iter):
+    """`max_iter` of rocco/dp.py:93 from 0 (the bracket's upper end is the answer) over a bisection cut in the middle of an
+    open bracket to 200 (140 steps after the bracket stopped moving): four kinds of scores, four lengths, speculative
+    depths 1 to 3, with and without the exact evaluator forced; penalty, count and solution are the reference's bit for
+    bit and the evaluations are the reference's max_iter + 2."""
+    for kind in ("round5", "int", "normal", "offset"):
+        for n in (33, 1000, 8193, 30000):
+            _off_sixty_agree(oracle, kind, n, max_iter, "plain")
+
+
+@pytest.mark.parametrize("max_iter", [2, 26, 61, 120])
+@pytest.mark.parametrize("behaviour", range(len(_DEVICE_SIDE_BEHAVIOURS)))
+def test_off_sixty_steps_do_not_depend_on_what_the_device_side_does(oracle, monkeypatch, behaviour, max_iter):
+    """The same check under every imitated device-side behaviour of
+    test_search_does_not_depend_on_what_the_device_side_does."""
+    import bisection_steps_cases as bs
+
+    assert max_iter in bs.DEVICE_SIDE_STEP_COUNTS
+    for key, value in _DEVICE_SIDE_BEHAVIOURS[behaviour].items():
+        monkeypatch.setenv("ROCCO_HOSTLOGIC_" + key, value)
+    for kind in ("round5", "int", "normal", "offset"):
+        for n in (33, 1000, 8193, 30000):
+            _off_sixty_agree(oracle, kind, n, max_iter, ("behaviour", behaviour))
+
+
+def test_step_counts_span_every_regime(oracle):
+    """The GPU tests lean on regimes that exist: on these tracks the ORACLE's own answers are far above every score
+    (count 0) up to 17 steps, cut in the middle of an open bracket (a count that is not the one of 60 steps) below 60 and,
+    on the integers, still at 59 and 61, differ from the penalty of 60 steps at 75 and 120, and have stopped moving by 75.
+    The search itself is held to the same answers."""
+    import bisection_steps_cases as bs
+    import envelope_cases as ec
+
+    seen = set()
+    table = {}
+    for kind, n, target, gamma in bs.REGIME_TRACKS:
+        s = ec.track(kind, n)
+        refs = {m: bs.reference(oracle, ("regime", kind, n, gamma), s, gamma, target, m) for m in bs.STEP_COUNTS + (60,)}
+        table[kind] = (refs, bs.regimes(refs, target))
+        for m, names in table[kind][1].items():
+            seen |= {name for name in names if name != "past_sixty" or m > 60}
+    assert seen == {"far", "cut_open", "past_sixty", "converged"}, seen
+    refs, reg = table["normal"]
+    assert all("far" in reg[m] for m in (0, 1, 2, 7, 17)), reg
+    assert refs[0][0] > 262144.0 and refs[17][0] > 4.0, (refs[0][0], refs[17][0])  # max + sum(costs) + 1 halved 17 times
+    assert all("past_sixty" in reg[m] for m in (75, 120, 200)) and "converged" in reg[75] and "converged" in reg[120], reg
+    refs, reg = table["peaks"]
+    assert all("cut_open" in reg[m] for m in (1, 2, 7, 17)) and not any("far" in reg[m] for m in (1, 2, 7, 17)), reg
+    assert refs[7][3] < refs[17][3] < refs[26][3] == refs[60][3], [refs[m][3] for m in (7, 17, 26, 60)]
+    assert all("past_sixty" in reg[m] for m in (75, 120, 200)) and "converged" in reg[75] and "converged" in reg[120], reg
+    refs, reg = table["integers"]  # a count that still moves at 60
+    assert "cut_open" in reg[59] and "cut_open" in reg[61] and refs[59][3] < refs[60][3] < refs[61][3], reg
+    assert all("converged" in reg[m] for m in (61, 64, 65, 75, 120)), reg
+    for kind, n, target, gamma in bs.REGIME_TRACKS:
+        s = ec.track(kind, n)
+        for m in (17, 61, 120):
+            ref = table[kind][0][m]
+            pen, sol, val, cnt, info = hl.calibrate(s, gamma, target, max_iter=m)
+            assert pen == ref[0] and cnt == ref[3] and np.array_equal(sol, ref[1]), (kind, m, info)
+            assert info["evaluations"] == m + 2 == ref[4], (kind, m, info)
