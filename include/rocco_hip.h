@@ -640,8 +640,8 @@ int rocco_hip_bigwig_dense_fill_f64(rocco_hip_solver *solver, const int64_t *sta
  * arrays in file order (the order the index iterator yields them), 16 bytes per record: pos (core.pos), end
  * (bam_endpos), isize (core.isize) as int32, flag (core.flag) as uint16, mapq (core.qual) and mate_same
  * (core.mtid == core.tid) as uint8.  The records of K tracks are concatenated; rec_offsets_host has K + 1 entries.
- * BAM decoding itself, the fragments (tabix) source, barcode filters, the count modes other than "coverage" and the
- * whole-file probes (paired-end detection, read length, mapped-read count, fragment length) stay outside.
+ * BAM decoding itself, the fragments (tabix) source, barcode filters and the count modes other than "coverage" stay
+ * outside; the whole-file probes (paired-end detection, read length, mapped-read count, fragment length) are row f7 below.
  *
  * rocco_hip_count_alignment_records_batch: ccounts_countRegion's alignment branch (rocco/native/ccounts_backend.c:
  *   2400-2573) for K tracks in one launch series: per record the overlap test of the index iterator on the read as it
@@ -722,6 +722,68 @@ int rocco_hip_count_alignment_intervals_batch(rocco_hip_solver *solver, const in
                                               const int32_t *start_dev, const int32_t *end_region_dev, size_t P, int32_t *out_dev,
                                               int32_t *track_facts_out_host, void *stream);
 void rocco_hip_count_intervals_shape(int *shape_out);
+
+/* ---- decoded alignment records of whole files -> the facts behind the count metadata ------
+ * The record passes of the reference's whole-file probes, for records already decoded: the six arrays above (the
+ * query length, a seventh, is read on the host side only).  Tracks are concatenated, rec_offsets_host has T + 1 entries, a
+ * track may be empty; F files x their contigs are one launch series.  Parameters arrive clamped as
+ * rocco/native/ccounts_backend.c:944-967 clamps them (max_iterations >= 1, max_insert_size >= 1, block_size >= 64,
+ * rolling_chunk_size >= 1, lag_step >= 1); smaller values are ROCCO_HIP_EINVAL.  Each call synchronises once, at its end.
+ *
+ * rocco_hip_record_flag_facts: mapped_out_host[t] = records of track t with flag & 4 == 0 -- what hts_idx_get_stat
+ *   reports as mapped for a contig, all ccounts_getMappedReadCount (ccounts_backend.c:1712-1888, the loop at 1859-1874)
+ *   needs; unsorted_out_host[t] != 0 when the track's pos does not ascend.  Integer reductions.
+ * rocco_hip_fragment_block_centers: ccounts_backend.c:1217-1339 per track (a contig of one file): the chunk density
+ *   (records passing flag_exclude and not unmapped, counted at pos / rolling_chunk_size into ceil(contig_len / chunk)
+ *   int32 cells, aggregated in an LDS window of ROCCO_FRAGMENT_DENSITY_WINDOW cells per
+ *   ROCCO_FRAGMENT_DENSITY_RECORDS records), the clamped window sums (winSize = block_size / chunk, at least 1, made
+ *   odd; the reference's start / end rules at both contig ends), the ranking by value descending then index ascending
+ *   (a stable descending radix sort) and the greedy pick of at most min(max_iterations, numChunks) centres, which stops
+ *   at the first non-positive value (host code over a downloaded prefix of the ranking, extended while it runs out).
+ *   The reference holds these counts in doubles; they are integers below 2^31, so int32 cells hold the same values.
+ *   centers_out_host is [T][max_iterations], center_count_out_host[t] says how many are set; a contig shorter than
+ *   block_size has none (1212-1215).  Optional: density_out_dev / rank_out_dev (device, int32) receive the window sums
+ *   and the ranking of track t at chunk_offsets_host[t] (T + 1 entries, the chunk counts accumulated; 0 chunks for a
+ *   skipped contig).
+ * rocco_hip_strand_xcorr_blocks: ccounts_backend.c:1361-1469 for n_blocks blocks, one workgroup each: block b covers
+ *   [block_start_host[b], + block_size) of track block_track_host[b] (the caller applies the formula and the clamp of
+ *   1344-1359).  Its records are found by bisecting pos (which must ascend: rocco_hip_record_flag_facts tells) and are
+ *   pos in [start, end), end <= block end, end > pos, flag_exclude passed, not unmapped -- what the index iterator and
+ *   the two containment tests leave.  Forward 5' ends at pos - start and reverse 5' ends at end - 1 - start are counted
+ *   in LDS (int32); fwd_sum / rev_sum are their totals; with either below 10, or no lag in range, best_lag is -1 and
+ *   best_score 0.0.  Otherwise one lane per lag = min_lag_host[track], + lag_step, ... <= min(max_insert_size,
+ *   block_size - 1) runs score += ((double)fwd[i] - fwdMean) * ((double)rev[i + lag] - revMean) for i = 0 ..
+ *   block_size - lag - 1 in that order, multiply and add apart, so that every score has the reference's bits; best_lag
+ *   is the lag of the largest score, the smallest such lag where scores compare equal (the reference's strict >),
+ *   best_score its score.  A block yields a candidate iff best_lag > 0 && best_score != 0.0.  block_size is at most
+ *   ROCCO_FRAGMENT_MAX_BLOCK_SIZE (two int32 arrays of a block in one workgroup's LDS); beyond it ROCCO_HIP_EINVAL.
+ * rocco_hip_template_lengths: ccounts_backend.c:1115-1144: lengths_out_dev + rec_offsets_host[t] receives, in file order,
+ *   |isize| of the records of track t that pass flag_exclude, are proper pairs, not read 2, have a mapped mate on the
+ *   same contig and min_insert_host[t] <= |isize| <= max_insert_size; count_out_host[t] says how many.  lengths_tmp_dev
+ *   and lengths_out_dev are device arrays of as many int32 as there are records.  A predicate and a stable compaction.
+ * rocco_hip_fragment_length_shape: shape_out[0..3] = the four numbers below. */
+#define ROCCO_FRAGMENT_THREADS 256
+#define ROCCO_FRAGMENT_DENSITY_RECORDS 2048
+#define ROCCO_FRAGMENT_DENSITY_WINDOW 2048
+#define ROCCO_FRAGMENT_MAX_BLOCK_SIZE 20224
+int rocco_hip_record_flag_facts(rocco_hip_solver *solver, const int32_t *pos_dev, const uint16_t *flag_dev,
+                                const int64_t *rec_offsets_host, size_t T, int64_t *mapped_out_host, int32_t *unsorted_out_host,
+                                void *stream);
+int rocco_hip_fragment_block_centers(rocco_hip_solver *solver, const int32_t *pos_dev, const uint16_t *flag_dev,
+                                     const int64_t *rec_offsets_host, size_t T, const int64_t *contig_len_host, int flag_exclude,
+                                     int max_iterations, int block_size, int rolling_chunk_size, int32_t *centers_out_host,
+                                     int32_t *center_count_out_host, const int64_t *chunk_offsets_host, int32_t *density_out_dev,
+                                     int32_t *rank_out_dev, void *stream);
+int rocco_hip_strand_xcorr_blocks(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev, const uint16_t *flag_dev,
+                                  const int64_t *rec_offsets_host, size_t T, const int32_t *block_track_host,
+                                  const int64_t *block_start_host, size_t n_blocks, const int32_t *min_lag_host, int flag_exclude,
+                                  int block_size, int max_insert_size, int lag_step, int32_t *best_lag_out_host,
+                                  double *best_score_out_host, int32_t *fwd_sum_out_host, int32_t *rev_sum_out_host, void *stream);
+int rocco_hip_template_lengths(rocco_hip_solver *solver, const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mate_same_dev,
+                               const int64_t *rec_offsets_host, size_t T, const int32_t *min_insert_host, int flag_exclude,
+                               int max_insert_size, int32_t *lengths_tmp_dev, int32_t *lengths_out_dev, int64_t *count_out_host,
+                               void *stream);
+void rocco_hip_fragment_length_shape(int *shape_out);
 
 /* ---- synthetic signal matrices (benchmark / test support, device-resident) -------------------
  * Fills a row-major [K][n] matrix with the counter-based synthetic tracks described in

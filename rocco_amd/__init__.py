@@ -41,6 +41,16 @@ from .readtracks import (  # noqa: F401  (rocco/native/ccounts_backend.c:1666-17
     count_alignment_records_batch_device,
     count_alignment_region_from_records,
 )
+from .readtracks import (  # noqa: F401  (rocco/native/ccounts_backend.c:598-1524, 1712-1888; rocco/readtracks.py:242-353)
+    AlignmentFileRecords,
+    alignment_fragment_length_from_records,
+    alignment_fragment_length_from_records_batch,
+    alignment_mapped_read_count_from_records,
+    alignment_read_length_from_records,
+    bam_count_metadata_from_records,
+    bam_count_metadata_from_records_batch,
+    is_alignment_paired_end_from_records,
+)
 from .rocco import (  # noqa: F401
     chrom_solution_to_bed,
     combine_chrom_results,

@@ -285,6 +285,22 @@ PROTOTYPES = [
       c_ll_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_size_t, ctypes.c_void_p, c_int_p, ctypes.c_void_p]),
     ("rocco_hip_count_intervals_shape", None, [c_int_p]),
+    # row f7 (csrc/fragment_length.hip): ccounts_getMappedReadCount, rocco/native/ccounts_backend.c:1712-1888
+    ("rocco_hip_record_flag_facts", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_size_t, c_ll_p, c_int_p, ctypes.c_void_p]),
+    # ccounts_getFragmentLength, rocco/native/ccounts_backend.c:861-1524: density, ranking and pick of block centres (1217-1339)
+    ("rocco_hip_fragment_block_centers", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_size_t, c_ll_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+      ctypes.c_int, c_int_p, c_int_p, c_ll_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # the strand cross-correlation of its blocks (1341-1469)
+    ("rocco_hip_strand_xcorr_blocks", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_size_t, c_int_p, c_ll_p, ctypes.c_size_t,
+      c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, c_double_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    # the template lengths of its paired branch (1084-1180)
+    ("rocco_hip_template_lengths", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_size_t, c_int_p, ctypes.c_int, ctypes.c_int,
+      ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_fragment_length_shape", None, [c_int_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t,
       ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]),

@@ -1545,6 +1545,103 @@ void rocco_hip_count_intervals_shape(int *shape_out)
     shape_out[2] = ROCCO_COUNT_INTERVALS_WAVES_PER_GROUP;
 }
 
+int rocco_hip_record_flag_facts(rocco_hip_solver *solver, const int32_t *pos_dev, const uint16_t *flag_dev,
+                                const int64_t *rec_offsets_host, size_t T, int64_t *mapped_out_host, int32_t *unsorted_out_host,
+                                void *stream)
+{
+    if (solver == nullptr || T == 0 || T >= (size_t)0x7fffffff || rec_offsets_host == nullptr || mapped_out_host == nullptr ||
+        unsorted_out_host == nullptr || (rec_offsets_host[T] > rec_offsets_host[0] && (pos_dev == nullptr || flag_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    int rc;
+    if ((rc = solver->dev_misc.reserve(record_flag_facts_scratch_bytes(T))) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_record_flag_facts(pos_dev, flag_dev, rec_offsets_host, T, mapped_out_host, unsorted_out_host, solver->dev_misc.ptr,
+                                    (hipStream_t)stream);
+}
+
+int rocco_hip_fragment_block_centers(rocco_hip_solver *solver, const int32_t *pos_dev, const uint16_t *flag_dev,
+                                     const int64_t *rec_offsets_host, size_t T, const int64_t *contig_len_host, int flag_exclude,
+                                     int max_iterations, int block_size, int rolling_chunk_size, int32_t *centers_out_host,
+                                     int32_t *center_count_out_host, const int64_t *chunk_offsets_host, int32_t *density_out_dev,
+                                     int32_t *rank_out_dev, void *stream)
+{
+    if (solver == nullptr || T == 0 || T >= (size_t)0x7fffffff || rec_offsets_host == nullptr || contig_len_host == nullptr ||
+        centers_out_host == nullptr || center_count_out_host == nullptr ||
+        (rec_offsets_host[T] > rec_offsets_host[0] && (pos_dev == nullptr || flag_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    const size_t bytes = fragment_block_centers_scratch_bytes(rec_offsets_host, T, contig_len_host, block_size, rolling_chunk_size);
+    if (bytes == 0) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    int rc;
+    if ((rc = solver->dev_misc.reserve(bytes)) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_fragment_block_centers(pos_dev, flag_dev, rec_offsets_host, T, contig_len_host, flag_exclude, max_iterations, block_size,
+                                         rolling_chunk_size, centers_out_host, center_count_out_host, chunk_offsets_host,
+                                         density_out_dev, rank_out_dev, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_strand_xcorr_blocks(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev, const uint16_t *flag_dev,
+                                  const int64_t *rec_offsets_host, size_t T, const int32_t *block_track_host,
+                                  const int64_t *block_start_host, size_t n_blocks, const int32_t *min_lag_host, int flag_exclude,
+                                  int block_size, int max_insert_size, int lag_step, int32_t *best_lag_out_host,
+                                  double *best_score_out_host, int32_t *fwd_sum_out_host, int32_t *rev_sum_out_host, void *stream)
+{
+    if (solver == nullptr || T == 0 || T >= (size_t)0x7fffffff || n_blocks == 0 || n_blocks >= (size_t)0x7fffffff ||
+        rec_offsets_host == nullptr || block_track_host == nullptr || block_start_host == nullptr || min_lag_host == nullptr ||
+        best_lag_out_host == nullptr || best_score_out_host == nullptr || fwd_sum_out_host == nullptr || rev_sum_out_host == nullptr ||
+        (rec_offsets_host[T] > rec_offsets_host[0] && (pos_dev == nullptr || end_dev == nullptr || flag_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    int rc;
+    if ((rc = solver->dev_misc.reserve(strand_xcorr_scratch_bytes(T, n_blocks))) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_strand_xcorr_blocks(pos_dev, end_dev, flag_dev, rec_offsets_host, T, block_track_host, block_start_host, n_blocks,
+                                      min_lag_host, flag_exclude, block_size, max_insert_size, lag_step, best_lag_out_host,
+                                      best_score_out_host, fwd_sum_out_host, rev_sum_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_template_lengths(rocco_hip_solver *solver, const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mate_same_dev,
+                               const int64_t *rec_offsets_host, size_t T, const int32_t *min_insert_host, int flag_exclude,
+                               int max_insert_size, int32_t *lengths_tmp_dev, int32_t *lengths_out_dev, int64_t *count_out_host,
+                               void *stream)
+{
+    if (solver == nullptr || T == 0 || T >= (size_t)0x7fffffff || rec_offsets_host == nullptr || min_insert_host == nullptr ||
+        count_out_host == nullptr ||
+        (rec_offsets_host[T] > rec_offsets_host[0] && (isize_dev == nullptr || flag_dev == nullptr || mate_same_dev == nullptr ||
+                                                       lengths_tmp_dev == nullptr || lengths_out_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    const size_t bytes = template_lengths_scratch_bytes(rec_offsets_host, T);
+    if (bytes == 0) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
+    int rc;
+    if ((rc = solver->dev_misc.reserve(bytes)) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_template_lengths(isize_dev, flag_dev, mate_same_dev, rec_offsets_host, T, min_insert_host, flag_exclude,
+                                   max_insert_size, lengths_tmp_dev, lengths_out_dev, count_out_host, solver->dev_misc.ptr,
+                                   (hipStream_t)stream);
+}
+
+void rocco_hip_fragment_length_shape(int *shape_out)
+{
+    shape_out[0] = ROCCO_FRAGMENT_THREADS;
+    shape_out[1] = ROCCO_FRAGMENT_DENSITY_RECORDS;
+    shape_out[2] = ROCCO_FRAGMENT_DENSITY_WINDOW;
+    shape_out[3] = ROCCO_FRAGMENT_MAX_BLOCK_SIZE;
+}
+
 int rocco_hip_synth_matrix(rocco_hip_solver *solver, void *matrix_dev, int dtype, size_t K, size_t n,
                            size_t row_stride, uint64_t seed, void *stream)
 {

@@ -341,6 +341,30 @@ int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_
                                      const int32_t *contig_id_dev, const int32_t *start_dev, const int32_t *end_region_dev, size_t P,
                                      int32_t *out_dev, int32_t *track_facts_out_host, void *scratch_dev, hipStream_t stream);
 
+// ---- fragment_length.hip ----------------------------------------------------------------------
+size_t record_flag_facts_scratch_bytes(size_t T);
+int launch_record_flag_facts(const int32_t *pos_dev, const uint16_t *flag_dev, const int64_t *rec_offsets_host, size_t T,
+                             int64_t *mapped_out_host, int32_t *unsorted_out_host, void *scratch_dev, hipStream_t stream);
+// 0: the shape is out of range
+size_t fragment_block_centers_scratch_bytes(const int64_t *rec_offsets_host, size_t T, const int64_t *contig_len_host, int block_size,
+                                            int rolling_chunk_size);
+int launch_fragment_block_centers(const int32_t *pos_dev, const uint16_t *flag_dev, const int64_t *rec_offsets_host, size_t T,
+                                  const int64_t *contig_len_host, int flag_exclude, int max_iterations, int block_size,
+                                  int rolling_chunk_size, int32_t *centers_out_host, int32_t *center_count_out_host,
+                                  const int64_t *chunk_offsets_host, int32_t *density_out_dev, int32_t *rank_out_dev, void *scratch_dev,
+                                  hipStream_t stream);
+size_t strand_xcorr_scratch_bytes(size_t T, size_t n_blocks);
+int launch_strand_xcorr_blocks(const int32_t *pos_dev, const int32_t *end_dev, const uint16_t *flag_dev, const int64_t *rec_offsets_host,
+                               size_t T, const int32_t *block_track_host, const int64_t *block_start_host, size_t n_blocks,
+                               const int32_t *min_lag_host, int flag_exclude, int block_size, int max_insert_size, int lag_step,
+                               int32_t *best_lag_out_host, double *best_score_out_host, int32_t *fwd_sum_out_host,
+                               int32_t *rev_sum_out_host, void *scratch_dev, hipStream_t stream);
+size_t template_lengths_scratch_bytes(const int64_t *rec_offsets_host, size_t T);
+int launch_template_lengths(const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mate_same_dev,
+                            const int64_t *rec_offsets_host, size_t T, const int32_t *min_insert_host, int flag_exclude,
+                            int max_insert_size, int32_t *lengths_tmp_dev, int32_t *lengths_out_dev, int64_t *count_out_host,
+                            void *scratch_dev, hipStream_t stream);
+
 // ---- synth.hip ------------------------------------------------------------------------------
 int launch_synth(void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, uint64_t seed,
                  hipStream_t stream);

@@ -169,11 +169,16 @@ class AlignmentRecords:
     int32, ``flag`` (core.flag) as uint16, ``mapq`` (core.qual) and ``mate_same`` (core.mtid == core.tid) as uint8.
     Any decoder can fill it (pysam, htslib, an integrator's own); CIGAR strings are not needed.  NumPy arrays are checked
     (integer dtypes, one length, values inside their fields, positions below 2**31) and converted; CUDA tensors must
-    already have the dtypes above."""
+    already have the dtypes above.
 
-    __slots__ = tuple(name for name, _ in _RECORD_FIELDS)
+    ``qlen`` (optional, keyword or `with_query_length`): a seventh array, int32, the query length of every record --
+    ``core.l_qseq``, or the CIGAR's query length (``bam_cigar2qlen``) when ``l_qseq <= 0``, the value the reference reads at
+    rocco/native/ccounts_backend.c:812-816 and 1046-1050.  Only the whole-file probes (DESIGN.md section 0 row f7) read it;
+    it is ``None`` unless given."""
 
-    def __init__(self, pos, end, isize, flag, mapq, mate_same):
+    __slots__ = tuple(name for name, _ in _RECORD_FIELDS) + ("qlen",)
+
+    def __init__(self, pos, end, isize, flag, mapq, mate_same, *, qlen=None):
         given = dict(pos=pos, end=end, isize=isize, flag=flag, mapq=mapq, mate_same=mate_same)
         length = None
         for name, dtype in _RECORD_FIELDS:
@@ -212,10 +217,33 @@ class AlignmentRecords:
             elif n != length:
                 raise ValueError(f"AlignmentRecords: `{name}` has {n} entries, `pos` has {length}")
             setattr(self, name, a)
+        self.qlen = None
+        if qlen is not None:
+            if _dp._is_tensor(qlen):
+                if str(qlen.dtype) != "torch.int32" or qlen.dim() != 1:
+                    raise TypeError("AlignmentRecords: `qlen` must be a one-dimensional int32 tensor")
+                qlen = qlen.contiguous()
+            else:
+                qlen = np.asarray(qlen)
+                if qlen.ndim != 1:
+                    raise ValueError("AlignmentRecords: `qlen` must be one-dimensional")
+                if qlen.dtype.kind not in "iu":
+                    raise TypeError(f"AlignmentRecords: `qlen` must hold integers, not {qlen.dtype}")
+                if qlen.size and (int(qlen.min()) < np.iinfo(np.int32).min or int(qlen.max()) > np.iinfo(np.int32).max):
+                    raise ValueError("AlignmentRecords: `qlen` does not fit int32")
+                qlen = np.ascontiguousarray(qlen, dtype=np.int32)
+            if int(qlen.shape[0]) != length:
+                raise ValueError(f"AlignmentRecords: `qlen` has {int(qlen.shape[0])} entries, `pos` has {length}")
+            self.qlen = qlen
 
     @classmethod
     def from_numpy(cls, pos, end, isize, flag, mapq, mate_same) -> "AlignmentRecords":
         return cls(pos, end, isize, flag, mapq, mate_same)
+
+    @classmethod
+    def with_query_length(cls, pos, end, isize, flag, mapq, mate_same, qlen) -> "AlignmentRecords":
+        """The six arrays plus ``qlen`` (see the class): what the whole-file probes need."""
+        return cls(pos, end, isize, flag, mapq, mate_same, qlen=qlen)
 
     def __len__(self) -> int:
         return int(self.pos.shape[0])
@@ -230,6 +258,9 @@ class AlignmentRecords:
             if not _dp._is_tensor(a):
                 a = torch.from_numpy(a.view(np.int16) if name == "flag" else a)
             setattr(out, name, a.to(device))
+        out.qlen = None
+        if self.qlen is not None:
+            out.qlen = (self.qlen if _dp._is_tensor(self.qlen) else torch.from_numpy(self.qlen)).to(device)
         return out
 
 
@@ -294,6 +325,7 @@ def _records_on_device(records_list: Sequence[AlignmentRecords], dev) -> Tuple[A
                 a = torch.from_numpy(a.view(np.int16) if name == "flag" else a)
             buf[offsets[k]: offsets[k + 1]].copy_(a)
         setattr(out, name, buf)
+    out.qlen = None
     return out, offsets
 
 
@@ -301,6 +333,7 @@ def _records_slice(records: AlignmentRecords, lo: int, hi: int) -> AlignmentReco
     out = object.__new__(AlignmentRecords)
     for name, _ in _RECORD_FIELDS:
         setattr(out, name, getattr(records, name)[lo:hi])
+    out.qlen = None if records.qlen is None else records.qlen[lo:hi]
     return out
 
 
@@ -484,7 +517,8 @@ def bam_chrom_reads_from_records(records: AlignmentRecords, chrom_size: int, ste
                                  round_digits: int = 5, scale_by_step: bool = False, bam_file: str = "", chromosome: str = ""):
     """What ``get_bam_chrom_reads`` returns for one file (rocco/readtracks.py:439-518), from its decoded records and the
     dict of ``_get_bam_count_metadata`` (``read_length``, ``resolved_extend_bp``, ``paired_end_mode``, ``norm_scale``:
-    whole-file facts the reader supplies; `_compute_native_scale_factor` makes ``norm_scale``): the count window, the
+    whole-file facts; `bam_count_metadata_from_records` returns this dict from the file's decoded records, and a reader
+    may as well supply it): the count window, the
     counting, the scaling and the trimming on the device.  ``(None, None)`` with the reference's warnings for an empty
     range or no positive value; otherwise ``intervals.astype(int)`` and the rounded float64 values.  This is the function
     to bind behind `get_bam_chrom_reads`."""
@@ -579,6 +613,478 @@ def count_alignment_intervals_from_records(records_by_chrom: dict, chromosomes, 
     kw.pop("infer_fragment_length", None)
     counts = count_alignment_intervals_batch_device([records_by_chrom], chromosomes, starts, ends, **kw)
     return np.minimum(counts[:, 0].cpu().numpy(), EXACT_COUNT_LIMIT).astype(np.float32)
+
+
+# --------------------------------------------------------------------------------------------
+# decoded records of a whole file -> the count metadata (csrc/fragment_length.hip)
+# --------------------------------------------------------------------------------------------
+
+class AlignmentFileRecords:
+    """The decoded records of one whole file: ``contigs``, the header's ``(name, length)`` pairs IN HEADER ORDER, and
+    ``records``, a mapping from contig name to `AlignmentRecords` in file order (absent or empty contigs allowed).
+    Concatenating the contigs in header order is the file order of a coordinate-sorted, indexed BAM, which the probes
+    that read "the first N records of the file" rely on.  Records without a contig (tid -1) are not part of it; they lie
+    at the end of such a file, so a result can differ from the reference's only for a file with fewer placed records than a
+    probe looks at (4 096 at the defaults).  ``name`` is the file's name in messages.  A ``(contigs, records)`` pair is
+    accepted wherever one of these is."""
+
+    __slots__ = ("contigs", "records", "name")
+
+    def __init__(self, contigs, records, name: str = ""):
+        self.contigs = [(str(n), int(length)) for n, length in contigs]
+        if len({n for n, _ in self.contigs}) != len(self.contigs):
+            raise ValueError("AlignmentFileRecords: a contig is named twice")
+        known = {n for n, _ in self.contigs}
+        for contig in records:
+            if contig not in known:
+                raise ValueError(f"AlignmentFileRecords: records for `{contig}`, which the header does not name")
+        self.records = dict(records)
+        self.name = str(name)
+
+    def tracks(self, names=None) -> list:
+        """(contig, records) in header order (or for ``names`` in their order), contigs without records left out."""
+        order = [n for n, _ in self.contigs] if names is None else list(names)
+        return [(n, self.records[n]) for n in order if n in self.records and len(self.records[n]) > 0]
+
+
+def _as_file(file) -> AlignmentFileRecords:
+    if isinstance(file, AlignmentFileRecords):
+        return file
+    contigs, records = file
+    return AlignmentFileRecords(contigs, records)
+
+
+def _need_qlen(file: AlignmentFileRecords, tracks, what: str) -> None:
+    for contig, records in tracks:
+        if records.qlen is None:
+            raise ValueError(f"{what}: the records of {file.name or 'the file'} on {contig} carry no `qlen` (query length); build "
+                             "them with AlignmentRecords.with_query_length")
+
+
+def _host(a) -> np.ndarray:
+    if _dp._is_tensor(a):
+        a = a.cpu().numpy()
+        return a.view(np.uint16) if a.dtype == np.int16 else a
+    return a
+
+
+def _head_chunks(tracks, fields, first: int = 4096):
+    """The records of ``tracks`` in order, as host arrays of ``fields``, a head slice at a time (doubling): the probes that
+    look at the head of a file download what they look at, not whole arrays."""
+    size = max(int(first), 1)
+    for _, records in tracks:
+        n, at = len(records), 0
+        while at < n:
+            hi = min(n, at + size)
+            yield {f: _host(getattr(records, f)[at:hi]) for f in fields}
+            at, size = hi, size * 2
+
+
+def _uint_median(values: np.ndarray) -> int:
+    """The integer median of the reference's probes (e.g. rocco/native/ccounts_backend.c:830-845): sort, the middle one, or
+    (a + b) / 2 in unsigned arithmetic."""
+    v = np.sort(np.asarray(values, dtype=np.int64))
+    mid = v.size // 2
+    return int((v[mid - 1] + v[mid]) // 2) if v.size % 2 == 0 else int(v[mid])
+
+
+def is_alignment_paired_end_from_records(file, max_reads: int = 1000) -> bool:
+    """``ccounts_isPairedEnd`` (rocco/native/ccounts_backend.c:598-652) for a file's decoded records: whether one of the
+    first ``max_reads`` records in file order is paired (every record for ``max_reads <= 0``).  Host arithmetic on a
+    downloaded head."""
+    file = _as_file(file)
+    left = int(max_reads)
+    for chunk in _head_chunks(file.tracks(), ("flag",), first=left if left > 0 else 1 << 16):
+        flags = chunk["flag"] if left <= 0 else chunk["flag"][:left]
+        if np.any(flags & 1):
+            return True
+        if left > 0:
+            left -= flags.size
+            if left <= 0:
+                return False
+    return False
+
+
+def alignment_read_length_from_records(file, min_reads: int = 32, max_iterations: int = 4096, flag_exclude: int = 0) -> int:
+    """``ccounts_getReadLength`` (rocco/native/ccounts_backend.c:654-856, the alignment branch) for a file's decoded
+    records: of the first ``max_iterations`` records in file order, the first ``min_reads`` with ``qlen > 0`` that pass
+    ``flag_exclude``; their integer median.  RuntimeError with the reference's message when none qualifies.  Host arithmetic
+    on a downloaded head."""
+    file = _as_file(file)
+    tracks = file.tracks()
+    _need_qlen(file, tracks, "alignment_read_length_from_records")
+    min_reads = max(int(min_reads), 1)
+    left = max(int(max_iterations), min_reads)
+    exclude = int(flag_exclude) & 0xFFFF
+    taken, have = [], 0
+    for chunk in _head_chunks(tracks, ("flag", "qlen"), first=left):
+        flags, qlen = chunk["flag"][:left], chunk["qlen"][:left]
+        good = qlen[((flags & exclude) == 0) & (qlen > 0)][: min_reads - have]
+        taken.append(good)
+        have += good.size
+        left -= flags.size
+        if have >= min_reads or left <= 0:
+            break
+    if have == 0:
+        raise RuntimeError("failed to estimate read length")
+    return _uint_median(np.concatenate(taken))
+
+
+def _device_for(tracks):
+    import torch
+
+    given = next((r.pos.device for r in tracks if _dp._is_tensor(r.pos)), None)
+    return given if given is not None else torch.device(f"cuda:{_dp._device_index()}")
+
+
+def record_flag_facts_device(records_list: Sequence[AlignmentRecords], cat=None, offsets=None) -> Tuple[list, list]:
+    """`rocco_hip_record_flag_facts`: per track the number of records with ``flag & 4 == 0`` and whether its ``pos`` fails to
+    ascend."""
+    T = len(records_list)
+    if T == 0:
+        return [], []
+    lib = _native.load()
+    if cat is None:
+        cat, offsets = _records_on_device(records_list, _device_for(records_list))
+    dev = cat.pos.device
+    rec_offsets = (ctypes.c_longlong * (T + 1))(*[int(o) for o in offsets])
+    mapped, unsorted = (ctypes.c_longlong * T)(), (ctypes.c_int * T)()
+    _native.check(lib.rocco_hip_record_flag_facts(_native.solver_for(dev.index).handle, cat.pos.data_ptr(), cat.flag.data_ptr(), rec_offsets,
+                                                  T, mapped, unsorted, _dp._stream_ptr(cat.pos)), "rocco_hip_record_flag_facts")
+    return [int(m) for m in mapped], [int(u) for u in unsorted]
+
+
+def alignment_mapped_read_count_from_records(file, exclude_chromosomes=()) -> Tuple[int, int]:
+    """``ccounts_getMappedReadCount`` (rocco/native/ccounts_backend.c:1712-1888, the alignment branch) for a file's decoded
+    records: (mapped, unmapped) summed over the contigs not in ``exclude_chromosomes``, as the index statistics count them
+    (``flag & 4``).  The unmapped count leaves out the records without a contig, which are not part of the input (the
+    reference's callers drop it)."""
+    file = _as_file(file)
+    excluded = {str(c) for c in (exclude_chromosomes or ())}
+    tracks = [(n, r) for n, r in file.tracks() if n not in excluded]
+    if not tracks:
+        return 0, 0
+    mapped, _ = record_flag_facts_device([r for _, r in tracks])
+    total = sum(len(r) for _, r in tracks)
+    return int(sum(mapped)), int(total - sum(mapped))
+
+
+def fragment_length_shape() -> dict:
+    """`rocco_hip_fragment_length_shape`: the sizes the fragment-length kernels are built to."""
+    shape = (ctypes.c_int * 4)()
+    _native.load().rocco_hip_fragment_length_shape(shape)
+    return {"threads": int(shape[0]), "density_records": int(shape[1]), "density_window": int(shape[2]), "max_block_size": int(shape[3])}
+
+
+def _fragment_params(flag_exclude, max_iterations, max_insert_size, block_size, rolling_chunk_size, lag_step, early_exit, fallback) -> dict:
+    """rocco/native/ccounts_backend.c:940-967."""
+    p = dict(flag_exclude=int(flag_exclude) & 0xFFFF if int(flag_exclude) > 0 else 0, max_iterations=max(int(max_iterations), 1),
+             max_insert_size=max(int(max_insert_size), 1), block_size=max(int(block_size), 64),
+             rolling_chunk_size=max(int(rolling_chunk_size), 1), lag_step=max(int(lag_step), 1), early_exit=int(early_exit),
+             fallback=int(fallback) if int(fallback) > 0 else 0)
+    if p["early_exit"] < 1:
+        p["early_exit"] = p["max_iterations"]
+    return p
+
+
+def _top_contigs(contigs) -> list:
+    """rocco/native/ccounts_backend.c:994-1013: the three longest contigs; a strictly longer one replaces, so the first of
+    equals stays ahead; a length of 0 never enters."""
+    top = []
+    for name, length in contigs:
+        for i in range(3):
+            if i >= len(top) or length > top[i][1]:
+                if length > 0:
+                    top.insert(i, (name, length))
+                    del top[3:]
+                break
+    return top
+
+
+def _sample_pass(tracks, flag_exclude: int, max_iterations: int) -> Tuple[int, float, bool]:
+    """rocco/native/ccounts_backend.c:1015-1060 on a downloaded head: (records sampled, the sum of their query lengths,
+    whether a record seen up to the last sampled one -- passing the flags, mapped, of any query length -- is paired)."""
+    count, total, paired = 0, 0.0, False
+    for chunk in _head_chunks(tracks, ("flag", "qlen"), first=max(4096, 2 * max_iterations)):
+        flags, qlen = chunk["flag"].astype(np.int64), chunk["qlen"]
+        seen = ((flags & flag_exclude) == 0) & ((flags & 4) == 0)
+        sampled = seen & (qlen > 0)
+        running = np.cumsum(sampled)
+        need = max_iterations - count
+        if running.size and running[-1] >= need:
+            last = int(np.searchsorted(running, need))  # the record that completes the sample
+            seen, sampled = seen[: last + 1], sampled[: last + 1]
+            flags, qlen = flags[: last + 1], qlen[: last + 1]
+        count += int(sampled.sum())
+        total += float(qlen[sampled].astype(np.int64).sum())  # (integers: exact in a double, as the reference's running sum)
+        paired = paired or bool(np.any(seen & ((flags & 1) != 0)))
+        if count >= max_iterations:
+            break
+    return count, total, paired
+
+
+def fragment_block_centers_device(records_list: Sequence[AlignmentRecords], contig_lengths: Sequence[int], flag_exclude: int = 0,
+                                  max_iterations: int = 1000, block_size: int = 5000, rolling_chunk_size: int = 250,
+                                  return_density: bool = False, cat=None, offsets=None):
+    """`rocco_hip_fragment_block_centers` (rocco/native/ccounts_backend.c:1217-1339) per track: the block centres (chunk
+    indices) in the order the reference accepts them, as a list of int32 arrays.  With ``return_density`` also the window
+    sums and the ranking per track (int32 CUDA tensors)."""
+    import torch
+
+    T = len(records_list)
+    lib = _native.load()
+    if cat is None:
+        cat, offsets = _records_on_device(records_list, _device_for(records_list))
+    dev = cat.pos.device
+    rec_offsets = (ctypes.c_longlong * (T + 1))(*[int(o) for o in offsets])
+    lengths = (ctypes.c_longlong * T)(*[int(n) for n in contig_lengths])
+    chunks = [0 if int(n) < block_size else max((int(n) + rolling_chunk_size - 1) // rolling_chunk_size, 0) for n in contig_lengths]
+    chunk_offsets = (ctypes.c_longlong * (T + 1))(*np.concatenate([[0], np.cumsum(chunks)]).astype(np.int64).tolist())
+    density = rank = None
+    if return_density:
+        density = torch.empty(max(int(chunk_offsets[T]), 1), dtype=torch.int32, device=dev)
+        rank = torch.empty_like(density)
+    centers, counts = (ctypes.c_int * (T * int(max_iterations)))(), (ctypes.c_int * T)()
+    _native.check(lib.rocco_hip_fragment_block_centers(
+        _native.solver_for(dev.index).handle, cat.pos.data_ptr(), cat.flag.data_ptr(), rec_offsets, T, lengths, int(flag_exclude),
+        int(max_iterations), int(block_size), int(rolling_chunk_size), centers, counts, chunk_offsets,
+        None if density is None else density.data_ptr(), None if rank is None else rank.data_ptr(), _dp._stream_ptr(cat.pos)),
+        "rocco_hip_fragment_block_centers")
+    flat = np.ctypeslib.as_array(centers)
+    picked = [flat[t * int(max_iterations): t * int(max_iterations) + int(counts[t])].copy() for t in range(T)]
+    if not return_density:
+        return picked
+    return (picked, [density[chunk_offsets[t]: chunk_offsets[t + 1]] for t in range(T)],
+            [rank[chunk_offsets[t]: chunk_offsets[t + 1]] for t in range(T)])
+
+
+def _block_starts(centers: np.ndarray, contig_length: int, block_size: int, rolling_chunk_size: int) -> np.ndarray:
+    """rocco/native/ccounts_backend.c:1343-1359 (the contig is at least a block long, so the clamped start is never negative)."""
+    starts = centers.astype(np.int64) * rolling_chunk_size + (rolling_chunk_size // 2) - (block_size // 2)
+    starts = np.maximum(starts, 0)
+    return np.where(starts + block_size > contig_length, contig_length - block_size, starts)
+
+
+def strand_xcorr_blocks_device(records_list: Sequence[AlignmentRecords], block_track, block_start, min_lag, flag_exclude: int = 0,
+                               block_size: int = 5000, max_insert_size: int = 1000, lag_step: int = 5, cat=None, offsets=None):
+    """`rocco_hip_strand_xcorr_blocks` (rocco/native/ccounts_backend.c:1361-1469): for block b = [block_start[b], +block_size)
+    of track block_track[b], (best_lag int32, best_score float64, fwd_sum int32, rev_sum int32) as NumPy arrays; ``min_lag``
+    per track.  A block is a candidate iff ``best_lag > 0 and best_score != 0.0``.  ``pos`` must ascend in every track."""
+    limit = fragment_length_shape()["max_block_size"]
+    if int(block_size) > limit:
+        raise ValueError(f"block_size {int(block_size)} is beyond {limit}: the two strand arrays of a block must fit one workgroup's "
+                         "LDS (there is no CPU fallback)")
+    T, B = len(records_list), len(block_track)
+    lib = _native.load()
+    if cat is None:
+        cat, offsets = _records_on_device(records_list, _device_for(records_list))
+    dev = cat.pos.device
+    rec_offsets = (ctypes.c_longlong * (T + 1))(*[int(o) for o in offsets])
+    tracks = (ctypes.c_int * B)(*[int(t) for t in block_track])
+    starts = (ctypes.c_longlong * B)(*[int(s) for s in block_start])
+    lags = (ctypes.c_int * T)(*[int(v) for v in min_lag])
+    best_lag, fwd_sum, rev_sum, best_score = (ctypes.c_int * B)(), (ctypes.c_int * B)(), (ctypes.c_int * B)(), (ctypes.c_double * B)()
+    _native.check(lib.rocco_hip_strand_xcorr_blocks(
+        _native.solver_for(dev.index).handle, cat.pos.data_ptr(), cat.end.data_ptr(), cat.flag.data_ptr(), rec_offsets, T, tracks, starts, B,
+        lags, int(flag_exclude), int(block_size), int(max_insert_size), int(lag_step), best_lag, best_score, fwd_sum, rev_sum,
+        _dp._stream_ptr(cat.pos)), "rocco_hip_strand_xcorr_blocks")
+    return (np.ctypeslib.as_array(best_lag).copy(), np.ctypeslib.as_array(best_score).copy(), np.ctypeslib.as_array(fwd_sum).copy(),
+            np.ctypeslib.as_array(rev_sum).copy())
+
+
+def _clamped_median(values, low: int, high: int) -> int:
+    """rocco/native/ccounts_backend.c:1149-1168 and 1485-1504."""
+    return min(max(_uint_median(values), low), high)
+
+
+def _paired_fragment_lengths(jobs: list, p: dict) -> None:
+    """rocco/native/ccounts_backend.c:1084-1180 for every paired file of ``jobs``: predicate and compaction on the device,
+    the first max(max_iterations, 2000) lengths in contig order, their median."""
+    import torch
+
+    lib = _native.load()
+    tracks = [(j, r) for j in jobs for _, r in j["tracks"]]
+    if not tracks:
+        return
+    records = [r for _, r in tracks]
+    cat, offsets = _records_on_device(records, _device_for(records))
+    dev, T = cat.pos.device, len(tracks)
+    total = max(int(offsets[-1]), 1)
+    tmp, out = torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, dtype=torch.int32, device=dev)
+    rec_offsets = (ctypes.c_longlong * (T + 1))(*[int(o) for o in offsets])
+    floors = (ctypes.c_int * T)(*[int(j["min_insert"]) for j, _ in tracks])
+    counts = (ctypes.c_longlong * T)()
+    _native.check(lib.rocco_hip_template_lengths(
+        _native.solver_for(dev.index).handle, cat.isize.data_ptr(), cat.flag.data_ptr(), cat.mate_same.data_ptr(), rec_offsets, T, floors,
+        p["flag_exclude"], p["max_insert_size"], tmp.data_ptr(), out.data_ptr(), counts, _dp._stream_ptr(cat.pos)),
+        "rocco_hip_template_lengths")
+    required = max(p["max_iterations"], 2000)
+    taken = {id(j): [] for j in jobs}
+    for t, (job, _) in enumerate(tracks):
+        have = sum(a.size for a in taken[id(job)])
+        take = min(int(counts[t]), required - have)
+        if take > 0:
+            taken[id(job)].append(out[offsets[t]: offsets[t] + take].cpu().numpy())
+    for job in jobs:
+        if taken[id(job)]:
+            job["result"] = _clamped_median(np.concatenate(taken[id(job)]), job["min_insert"], p["max_insert_size"])
+
+
+def _single_end_fragment_lengths(jobs: list, p: dict) -> None:
+    """rocco/native/ccounts_backend.c:1182-1509 for every single-end file of ``jobs``: block centres of all their contigs in
+    one call, then the blocks of all files in rounds -- each file submits the next blocks of the contig it is in, in the
+    reference's order, and stops where the reference stops (``early_exit`` candidates, moving to its next contig only while
+    fewer exist); surplus blocks of a round are discarded."""
+    block_size, chunk = p["block_size"], p["rolling_chunk_size"]
+    limit = fragment_length_shape()["max_block_size"]
+    if block_size > limit:
+        raise ValueError(f"block_size {block_size} is beyond {limit}: the two strand arrays of a block must fit one workgroup's LDS "
+                         "(there is no CPU fallback)")
+    tracks = [(j, contig, length, r) for j in jobs for (contig, r), length in zip(j["tracks"], j["track_lengths"])]
+    if not tracks:
+        return
+    records = [r for _, _, _, r in tracks]
+    cat, offsets = _records_on_device(records, _device_for(records))
+    _, unsorted = record_flag_facts_device(records, cat, offsets)
+    for (job, contig, _, _), bad in zip(tracks, unsorted):
+        if bad:
+            raise ValueError(f"the records of file {job['name']} on {contig} are not in coordinate order: the fragment-length "
+                             "estimate needs the file order of an indexed BAM")
+    centers = fragment_block_centers_device(records, [length for _, _, length, _ in tracks], p["flag_exclude"], p["max_iterations"],
+                                            block_size, chunk, cat=cat, offsets=offsets)
+    min_lag = [int(j["min_insert"]) for j, _, _, _ in tracks]
+    for t, (job, _, length, _) in enumerate(tracks):
+        job.setdefault("queue", []).append((t, _block_starts(centers[t], length, block_size, chunk)))
+        job.update(at=0, lags=[])
+    live = [j for j in jobs if j.get("queue")]
+    while live:
+        block_track, block_start, owners = [], [], []
+        for job in live:
+            t, starts = job["queue"][0]
+            n = min(starts.size - job["at"], max(64, 2 * (p["early_exit"] - len(job["lags"]))))
+            block_track += [t] * n
+            block_start += starts[job["at"]: job["at"] + n].tolist()
+            owners.append((job, n))
+        if block_track:
+            best_lag, best_score, _, _ = strand_xcorr_blocks_device(records, block_track, block_start, min_lag, p["flag_exclude"], block_size,
+                                                                     p["max_insert_size"], p["lag_step"], cat=cat, offsets=offsets)
+        at = 0
+        for job, n in owners:
+            for b in range(at, at + n):
+                if len(job["lags"]) >= p["early_exit"]:
+                    break
+                if best_lag[b] > 0 and best_score[b] != 0.0:
+                    job["lags"].append(int(best_lag[b]) + 1)
+            at += n
+            job["at"] += n
+            if job["at"] >= job["queue"][0][1].size:
+                job["queue"].pop(0)
+                job["at"] = 0
+            if len(job["lags"]) >= p["early_exit"]:
+                job["queue"] = []
+        live = [j for j in live if j["queue"]]
+    for job in jobs:
+        if job.get("lags"):
+            job["result"] = _clamped_median(job["lags"], job["min_insert"], p["max_insert_size"])
+
+
+def alignment_fragment_length_from_records_batch(files: Sequence, flag_exclude: int = 0, max_iterations: int = 1000,
+                                                 max_insert_size: int = 1000, block_size: int = 5000, rolling_chunk_size: int = 250,
+                                                 lag_step: int = 5, early_exit: int = 250, fallback: int = 0) -> list:
+    """``ccounts_getFragmentLength`` (rocco/native/ccounts_backend.c:861-1524; keywords and defaults of
+    ``get_alignment_fragment_length``, rocco/_hts_counts.c:196-205) for F files' decoded records in one launch series: per
+    file the fragment length (paired-end: the median template length; single-end: the median of the best strand
+    cross-correlation lags + 1 over its densest blocks), ``fallback`` where nothing qualifies (0 for ``fallback <= 0``).
+    The records need ``qlen``; every contig's ``pos`` must ascend (ValueError naming file and contig otherwise).  The
+    sample pass runs on a downloaded head; density, ranking, cross-correlation and the paired branch's compaction run on
+    the device; a ``block_size`` beyond `fragment_length_shape`'s limit is a ValueError."""
+    p = _fragment_params(flag_exclude, max_iterations, max_insert_size, block_size, rolling_chunk_size, lag_step, early_exit, fallback)
+    jobs, paired_jobs, single_jobs = [], [], []
+    for k, given in enumerate(files):
+        file = _as_file(given)
+        top = _top_contigs(file.contigs)
+        tracks = file.tracks([n for n, _ in top])
+        _need_qlen(file, tracks, "alignment_fragment_length_from_records")
+        lengths = dict(top)
+        job = {"name": file.name or str(k), "tracks": tracks, "track_lengths": [lengths[n] for n, _ in tracks], "result": p["fallback"]}
+        jobs.append(job)
+        count, total, paired = _sample_pass(tracks, p["flag_exclude"], p["max_iterations"])
+        if count <= 0:
+            continue
+        job["min_insert"] = min(max(int(total / float(count)), 1), p["max_insert_size"])
+        (paired_jobs if paired else single_jobs).append(job)
+    if paired_jobs:
+        _paired_fragment_lengths(paired_jobs, p)
+    if single_jobs:
+        _single_end_fragment_lengths(single_jobs, p)
+    return [int(job["result"]) for job in jobs]
+
+
+def alignment_fragment_length_from_records(file, flag_exclude: int = 0, max_iterations: int = 1000, max_insert_size: int = 1000,
+                                           block_size: int = 5000, rolling_chunk_size: int = 250, lag_step: int = 5, early_exit: int = 250,
+                                           fallback: int = 0) -> int:
+    """One file of `alignment_fragment_length_from_records_batch`."""
+    return alignment_fragment_length_from_records_batch([file], flag_exclude, max_iterations, max_insert_size, block_size,
+                                                        rolling_chunk_size, lag_step, early_exit, fallback)[0]
+
+
+def bam_count_metadata_from_records_batch(files: Sequence, step: int, norm_method: str, effective_genome_size: float, ignore_for_norm,
+                                          flag_exclude: int = 0, extend_reads: int = -1, scale_factor: float = 1.0,
+                                          bam_files: Optional[Sequence[str]] = None) -> list:
+    """`bam_count_metadata_from_records` for K files: the fragment lengths of all files that need one (``extend_reads == 0``)
+    come from one launch series."""
+    files = [_as_file(f) for f in files]
+    names = list(bam_files) if bam_files is not None else [f.name for f in files]
+    ignore = tuple(ignore_for_norm or [])
+    facts = []
+    for file in files:
+        paired_end = bool(is_alignment_paired_end_from_records(file, max_reads=1024))
+        read_length = int(alignment_read_length_from_records(file, min_reads=32, max_iterations=4096, flag_exclude=max(0, int(flag_exclude))))
+        mapped_reads, _ = alignment_mapped_read_count_from_records(file, exclude_chromosomes=list(ignore))
+        facts.append((paired_end, read_length, mapped_reads))
+    fragment_lengths = [None] * len(files)
+    if int(extend_reads) == 0:  # `_estimate_fragment_length` (rocco/readtracks.py:189-207)
+        lengths = alignment_fragment_length_from_records_batch(files, flag_exclude=max(0, int(flag_exclude)), max_iterations=4096, fallback=0)
+        fragment_lengths = [n if n > 0 else None for n in lengths]
+    out = []
+    for bam_file, (paired_end, read_length, mapped_reads), fragment_length in zip(names, facts, fragment_lengths):
+        norm_read_length, resolved_extend_bp, paired_end_mode = int(read_length), int(extend_reads), False
+        if int(extend_reads) == 0:
+            if paired_end:
+                if fragment_length is not None and fragment_length > 0:
+                    norm_read_length, paired_end_mode, resolved_extend_bp = int(fragment_length), True, 0
+                else:
+                    logger.warning("Could not estimate fragment length for %s; falling back to read length %s.", bam_file, read_length)
+            else:
+                if fragment_length is not None and fragment_length > int(read_length):
+                    norm_read_length = resolved_extend_bp = int(fragment_length)
+                    logger.info("Using inferred single-end fragment length %s for %s.", fragment_length, bam_file)
+                else:
+                    logger.warning("`extend_reads=0` requests fragment-length inference, but %s did not yield a larger single-end "
+                                   "fragment length; using read length %s.", bam_file, read_length)
+                    resolved_extend_bp = -1
+        elif int(extend_reads) > 0:
+            norm_read_length = resolved_extend_bp = int(extend_reads)
+        norm_scale = _compute_native_scale_factor(norm_method=norm_method, effective_genome_size=effective_genome_size, step=step,
+                                                  mapped_reads=int(mapped_reads), norm_read_length=int(norm_read_length),
+                                                  scale_factor=float(scale_factor))
+        out.append({"paired_end": paired_end, "paired_end_mode": paired_end_mode, "read_length": int(read_length),
+                    "norm_read_length": int(norm_read_length), "resolved_extend_bp": int(resolved_extend_bp),
+                    "mapped_reads": int(mapped_reads), "norm_scale": float(norm_scale)})
+    return out
+
+
+def bam_count_metadata_from_records(file, step: int, norm_method: str, effective_genome_size: float, ignore_for_norm,
+                                    flag_exclude: int = 0, extend_reads: int = -1, scale_factor: float = 1.0, bam_file: str = "") -> dict:
+    """The body of the reference's ``_get_bam_count_metadata`` after its cache lookup (rocco/readtracks.py:269-351) for a
+    file's decoded records (`AlignmentFileRecords`, with ``qlen``): the four probes above, the same ``extend_reads``
+    branches, the same three log lines at the same levels, `_compute_native_scale_factor` as it is.  Returns the
+    reference's dict without ``threads`` (host configuration, like its cache): ``paired_end``, ``paired_end_mode``,
+    ``read_length``, ``norm_read_length``, ``resolved_extend_bp``, ``mapped_reads``, ``norm_scale`` -- the ``metadata`` that
+    `bam_chrom_reads_from_records` takes.  This is the function to bind behind `_get_bam_count_metadata`."""
+    file = _as_file(file)
+    return bam_count_metadata_from_records_batch([file], step, norm_method, effective_genome_size, ignore_for_norm, flag_exclude,
+                                                 extend_reads, scale_factor, [bam_file or file.name])[0]
 
 
 # --------------------------------------------------------------------------------------------
