@@ -90,6 +90,19 @@ void PinnedBuffer::release()
 
 using namespace rocco;
 
+// What the record entry points (count.hip, interval_count.hip, fragment_length.hip) do once their arguments have passed:
+// the solver's device, no other library's stale error for this call's launch checks, `bytes` of dev_misc (0: the launcher's
+// *_scratch_bytes refused the shape).
+static int enter_record_call(rocco_hip_solver *solver, size_t bytes)
+{
+    if (bytes == 0) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device));
+    (void)hipGetLastError();
+    return solver->dev_misc.reserve(bytes);
+}
+
 extern "C" {
 
 int rocco_hip_abi_version(void) { return 1000; }
@@ -1452,12 +1465,7 @@ int rocco_hip_count_alignment_records_batch(rocco_hip_solver *solver, const int3
         return ROCCO_HIP_EINVAL;
     }
     const size_t bytes = count_alignment_scratch_bytes(rec_offsets_host, K, options_host, regions_host, out_offsets_host);
-    if (bytes == 0) {
-        return ROCCO_HIP_EINVAL;
-    }
-    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
-    int rc;
-    if ((rc = solver->dev_misc.reserve(bytes)) != ROCCO_HIP_OK) {
+    if (const int rc = enter_record_call(solver, bytes); rc != ROCCO_HIP_OK) {
         return rc;
     }
     return launch_count_alignment_records(pos_dev, end_dev, isize_dev, flag_dev, mapq_dev, mate_same_dev, rec_offsets_host, K,
@@ -1481,9 +1489,7 @@ int rocco_hip_alignment_chrom_range(rocco_hip_solver *solver, const int32_t *pos
         (n > 0 && (pos_dev == nullptr || end_dev == nullptr || flag_dev == nullptr))) {
         return ROCCO_HIP_EINVAL;
     }
-    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
-    int rc;
-    if ((rc = solver->dev_misc.reserve(256)) != ROCCO_HIP_OK) {
+    if (const int rc = enter_record_call(solver, 256); rc != ROCCO_HIP_OK) {
         return rc;
     }
     return launch_alignment_chrom_range(pos_dev, end_dev, flag_dev, n, chrom_len, flag_exclude, start_out, end_out,
@@ -1498,9 +1504,7 @@ int rocco_hip_alignment_count_tail_f64(rocco_hip_solver *solver, const float *co
         (n > 0 && (counts_dev == nullptr || vals_out_dev == nullptr))) {
         return ROCCO_HIP_EINVAL;
     }
-    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
-    int rc;
-    if ((rc = solver->dev_misc.reserve(256)) != ROCCO_HIP_OK) {
+    if (const int rc = enter_record_call(solver, 256); rc != ROCCO_HIP_OK) {
         return rc;
     }
     return launch_alignment_count_tail(counts_dev, n, norm_scale, scale_by_step, step, const_scale, round_digits, vals_out_dev,
@@ -1520,7 +1524,7 @@ int rocco_hip_count_alignment_intervals_batch(rocco_hip_solver *solver, const in
         return ROCCO_HIP_EINVAL;
     }
     const size_t bytes = count_intervals_scratch_bytes(rec_offsets_host, F, C, P);
-    if (bytes == 0) {
+    if (bytes == 0) {  // (before rec_offsets_host[F * C] is read: F * C may be what was refused)
         return ROCCO_HIP_EINVAL;
     }
     if (rec_offsets_host[F * C] > rec_offsets_host[0] &&
@@ -1528,9 +1532,7 @@ int rocco_hip_count_alignment_intervals_batch(rocco_hip_solver *solver, const in
          mate_same_dev == nullptr)) {
         return ROCCO_HIP_EINVAL;
     }
-    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
-    int rc;
-    if ((rc = solver->dev_misc.reserve(bytes)) != ROCCO_HIP_OK) {
+    if (const int rc = enter_record_call(solver, bytes); rc != ROCCO_HIP_OK) {
         return rc;
     }
     return launch_count_alignment_intervals(pos_dev, end_dev, isize_dev, flag_dev, mapq_dev, mate_same_dev, rec_offsets_host, F, C,
@@ -1553,9 +1555,7 @@ int rocco_hip_record_flag_facts(rocco_hip_solver *solver, const int32_t *pos_dev
         unsorted_out_host == nullptr || (rec_offsets_host[T] > rec_offsets_host[0] && (pos_dev == nullptr || flag_dev == nullptr))) {
         return ROCCO_HIP_EINVAL;
     }
-    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
-    int rc;
-    if ((rc = solver->dev_misc.reserve(record_flag_facts_scratch_bytes(T))) != ROCCO_HIP_OK) {
+    if (const int rc = enter_record_call(solver, record_flag_facts_scratch_bytes(T)); rc != ROCCO_HIP_OK) {
         return rc;
     }
     return launch_record_flag_facts(pos_dev, flag_dev, rec_offsets_host, T, mapped_out_host, unsorted_out_host, solver->dev_misc.ptr,
@@ -1574,12 +1574,7 @@ int rocco_hip_fragment_block_centers(rocco_hip_solver *solver, const int32_t *po
         return ROCCO_HIP_EINVAL;
     }
     const size_t bytes = fragment_block_centers_scratch_bytes(rec_offsets_host, T, contig_len_host, block_size, rolling_chunk_size);
-    if (bytes == 0) {
-        return ROCCO_HIP_EINVAL;
-    }
-    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
-    int rc;
-    if ((rc = solver->dev_misc.reserve(bytes)) != ROCCO_HIP_OK) {
+    if (const int rc = enter_record_call(solver, bytes); rc != ROCCO_HIP_OK) {
         return rc;
     }
     return launch_fragment_block_centers(pos_dev, flag_dev, rec_offsets_host, T, contig_len_host, flag_exclude, max_iterations, block_size,
@@ -1599,9 +1594,7 @@ int rocco_hip_strand_xcorr_blocks(rocco_hip_solver *solver, const int32_t *pos_d
         (rec_offsets_host[T] > rec_offsets_host[0] && (pos_dev == nullptr || end_dev == nullptr || flag_dev == nullptr))) {
         return ROCCO_HIP_EINVAL;
     }
-    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
-    int rc;
-    if ((rc = solver->dev_misc.reserve(strand_xcorr_scratch_bytes(T, n_blocks))) != ROCCO_HIP_OK) {
+    if (const int rc = enter_record_call(solver, strand_xcorr_scratch_bytes(T, n_blocks)); rc != ROCCO_HIP_OK) {
         return rc;
     }
     return launch_strand_xcorr_blocks(pos_dev, end_dev, flag_dev, rec_offsets_host, T, block_track_host, block_start_host, n_blocks,
@@ -1621,12 +1614,7 @@ int rocco_hip_template_lengths(rocco_hip_solver *solver, const int32_t *isize_de
         return ROCCO_HIP_EINVAL;
     }
     const size_t bytes = template_lengths_scratch_bytes(rec_offsets_host, T);
-    if (bytes == 0) {
-        return ROCCO_HIP_EINVAL;
-    }
-    ROCCO_HIP_TRY(hipSetDevice(solver->device)); (void)hipGetLastError();  // (no other library's stale error for this call's launch checks)
-    int rc;
-    if ((rc = solver->dev_misc.reserve(bytes)) != ROCCO_HIP_OK) {
+    if (const int rc = enter_record_call(solver, bytes); rc != ROCCO_HIP_OK) {
         return rc;
     }
     return launch_template_lengths(isize_dev, flag_dev, mate_same_dev, rec_offsets_host, T, min_insert_host, flag_exclude,

@@ -17,7 +17,6 @@ namespace rocco {
 
 namespace {
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 __global__ __launch_bounds__(256) void fixed_step_kernel(const long long *__restrict__ common, const unsigned long long *m_ptr,
                                                         int *__restrict__ not_fixed)
@@ -73,7 +72,7 @@ size_t union_scratch_bytes(size_t count)
     (void)hipcub::DeviceRadixSort::SortKeys(nullptr, a, (const long long *)nullptr, (long long *)nullptr, (int)count);
     (void)hipcub::DeviceSelect::Unique(nullptr, b, (const long long *)nullptr, (long long *)nullptr,
                                        (unsigned long long *)nullptr, (int)count);
-    return align256(count * 8) + align256(a > b ? a : b) + 512;
+    return align_up(count * 8, 256) + align_up(a > b ? a : b, 256) + 512;
 }
 
 int launch_union_intervals(const int64_t *values_dev, size_t count, int64_t *unique_out_dev, size_t *n_unique_out,
@@ -81,9 +80,9 @@ int launch_union_intervals(const int64_t *values_dev, size_t count, int64_t *uni
 {
     char *sc = (char *)scratch_dev;
     long long *sorted = (long long *)sc;
-    unsigned long long *m_dev = (unsigned long long *)(sc + align256(count * 8));
+    unsigned long long *m_dev = (unsigned long long *)(sc + align_up(count * 8, 256));
     int *flag = (int *)(m_dev + 1);
-    void *tmp = sc + align256(count * 8) + 256;
+    void *tmp = sc + align_up(count * 8, 256) + 256;
     size_t a = 0, b = 0;
     (void)hipcub::DeviceRadixSort::SortKeys(nullptr, a, (const long long *)values_dev, sorted, (int)count);
     (void)hipcub::DeviceSelect::Unique(nullptr, b, sorted, (long long *)unique_out_dev, m_dev, (int)count);
@@ -103,7 +102,7 @@ int launch_union_intervals(const int64_t *values_dev, size_t count, int64_t *uni
     return ROCCO_HIP_OK;
 }
 
-size_t scatter_scratch_bytes(size_t K, size_t m) { return align256(K * m * sizeof(unsigned)) + 256; }
+size_t scatter_scratch_bytes(size_t K, size_t m) { return align_up(K * m * sizeof(unsigned), 256) + 256; }
 
 int launch_scatter_tracks(const int64_t *common_dev, size_t m, const int64_t *intervals_concat_dev,
                           const double *vals_concat_dev, const size_t *offsets_host, size_t K, int out_dtype,

@@ -138,7 +138,6 @@ __global__ __launch_bounds__(256) void soft_count_kernel(const double *__restric
     }
 }
 
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace
 

@@ -28,6 +28,34 @@ void set_last_error(const std::string &msg);
         }                                                                                    \
     } while (0)
 
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// Regions of one buffer, one behind the other, each aligned to 256 bytes.
+struct Layout {
+    size_t off = 0, uploaded = 0;
+    size_t at(size_t bytes)
+    {
+        const size_t begin = off;
+        off += align_up(bytes, 256);
+        return begin;
+    }
+    void end_upload() { uploaded = off; }  // what was laid out so far is the prefix copied from the host
+    size_t bytes() const { return off; }
+};
+
+// Runs `body`, which queues work on `stream` and returns a ROCCO_HIP_* code.  Where it gave up part-way, what it queued may
+// still be running: wait for it, drop the error the runtime keeps for the thread, hand the code on.
+template <class F>
+int queue_then_drain(hipStream_t stream, F &&body)
+{
+    const int rc = body();
+    if (rc != ROCCO_HIP_OK) {
+        (void)hipStreamSynchronize(stream);
+        (void)hipGetLastError();
+    }
+    return rc;
+}
+
 // Growable device / pinned-host buffers owned by a solver handle.
 struct DeviceBuffer {
     void *ptr = nullptr;

@@ -18,6 +18,8 @@
 // memory directly.  The prefix sum is reduce-then-scan over tiles (three launches, no waiting between workgroups).
 #include "kernels.h"
 #include "record_cells.h"
+#include "record_layouts.h"
+#include "record_stream.h"
 #include "round_np.h"
 
 #include <hipcub/hipcub.hpp>
@@ -45,30 +47,6 @@ static_assert(kChunk == ROCCO_COUNT_CHUNK_RECORDS && kScanTile == ROCCO_COUNT_SC
                   kMaxGrid > 0,
               "rocco_hip.h states the shape");
 
-// largest k with first[k] <= item (first has K + 1 ascending entries, item < first[K]): tracks without work are skipped
-__device__ __forceinline__ int find_track(const int *__restrict__ first, int K, int item)
-{
-    int lo = 0, hi = K;  // answer in [lo, hi)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= item) {
-            lo = mid;
-        } else {
-            hi = mid;
-        }
-    }
-    return lo;
-}
-
-__device__ __forceinline__ int wave_min(int v)
-{
-    for (int off = warpSize / 2; off > 0; off >>= 1) {
-        const int o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 // chunk_first[k]: the first chunk of track k among all chunks (K + 1 entries).  A workgroup takes chunks blockIdx.x,
 // blockIdx.x + gridDim.x, ...
 __global__ __launch_bounds__(kThreads) void count_records_kernel(
@@ -83,7 +61,7 @@ __global__ __launch_bounds__(kThreads) void count_records_kernel(
         window[c] = 0;
     }
     for (int chunk = blockIdx.x; chunk < total_chunks; chunk += gridDim.x) {
-        const int k = find_track(chunk_first, K, chunk);
+        const int k = find_slot(chunk_first, K, chunk);
         const CountTrack t = tracks[k];
         const long long base = t.rec_begin + (long long)(chunk - chunk_first[k]) * kChunk;
         int *__restrict__ track_delta = delta + t.delta_offset;
@@ -163,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void tile_sum_kernel(const CountTrack *__
     using Reduce = hipcub::BlockReduce<int, kThreads>;
     __shared__ typename Reduce::TempStorage temp;
     const int tile = blockIdx.x;
-    const int k = find_track(tile_first, K, tile);
+    const int k = find_slot(tile_first, K, tile);
     const long long base = (long long)(tile - tile_first[k]) * kScanTile;
     const int n_bins = tracks[k].n_bins;
     int sum = 0;
@@ -217,7 +195,7 @@ __global__ __launch_bounds__(kThreads) void scan_write_kernel(const CountTrack *
         typename Reduce::TempStorage reduce;
     } temp;
     const int tile = blockIdx.x;
-    const int k = find_track(tile_first, K, tile);
+    const int k = find_slot(tile_first, K, tile);
     const long long base = (long long)(tile - tile_first[k]) * kScanTile;
     const int n_bins = tracks[k].n_bins;
     const int valid = (int)(n_bins - base < kScanTile ? n_bins - base : kScanTile);
@@ -301,19 +279,7 @@ __global__ __launch_bounds__(kThreads) void chrom_range_kernel(const int *__rest
             last = (unsigned long long)i + 1 > last ? (unsigned long long)i + 1 : last;
         }
     }
-    for (int off = warpSize / 2; off > 0; off >>= 1) {
-        const unsigned long long f = __shfl_xor(first, off), l = __shfl_xor(last, off);
-        first = f < first ? f : first;
-        last = l > last ? l : last;
-    }
-    if ((threadIdx.x & (warpSize - 1)) == 0) {
-        if (first != ~0ULL) {
-            atomicMin(&result[0], first);
-        }
-        if (last != 0) {
-            atomicMax(&result[1], last);
-        }
-    }
+    wave_first_last(first, last, result);
 }
 
 __global__ void chrom_range_fetch_kernel(const int *__restrict__ pos, const int *__restrict__ end,
@@ -347,73 +313,48 @@ __global__ __launch_bounds__(kThreads) void count_tail_kernel(const float *__res
         }
         out[i] = round_like_numpy(v, pow10, digits);
     }
-    for (int off = warpSize / 2; off > 0; off >>= 1) {
-        const unsigned long long f = __shfl_xor(first, off), l = __shfl_xor(last, off);
-        first = f < first ? f : first;
-        last = l > last ? l : last;
-    }
-    if ((threadIdx.x & (warpSize - 1)) == 0) {
-        if (first != ~0ULL) {
-            atomicMin(&support[0], first);
-        }
-        if (last != 0) {
-            atomicMax(&support[1], last);
-        }
-    }
+    wave_first_last(first, last, support);
 }
-
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 struct CountPlan {
     std::vector<CountTrack> tracks;
     std::vector<int> chunk_first, tile_first;
-    size_t delta_cells = 0;
-    size_t off_tracks = 0, off_chunk_first = 0, off_tile_first = 0, off_max = 0, off_tile_sums = 0, off_delta = 0, bytes = 0;
+    CountLayout at = CountLayout(0, 0, 0);
 };
 
 int make_plan(const int64_t *rec_offsets, size_t K, const rocco_hip_count_options *options,
               const rocco_hip_count_region *regions, const int64_t *out_offsets, CountPlan &plan)
 {
+    const int rc = check_record_tracks(rec_offsets, K, "count_alignment_records");
+    if (rc != ROCCO_HIP_OK) {
+        return rc;
+    }
     plan.tracks.resize(K);
     plan.chunk_first.assign(K + 1, 0);
     plan.tile_first.assign(K + 1, 0);
     long long chunks = 0, tiles = 0;
     size_t cells = 0;
     for (size_t k = 0; k < K; ++k) {
-        const rocco_hip_count_options &o = options[k];
         const rocco_hip_count_region &r = regions[k];
-        const long long n = rec_offsets[k + 1] - rec_offsets[k];
-        if (n < 0 || n >= (1LL << 31) || rec_offsets[k] < 0 || r.step <= 0 || r.start < 0 || r.end <= r.start || r.n_bins <= 0 ||
-            out_offsets[k] < 0) {
-            set_last_error("count_alignment_records: a track's record range, region or output offset is invalid");
+        if (r.step <= 0 || r.start < 0 || r.end <= r.start || r.n_bins <= 0 || out_offsets[k] < 0) {
+            set_last_error("count_alignment_records: a track's region or output offset is invalid");
             return ROCCO_HIP_EINVAL;
         }
         CountTrack &t = plan.tracks[k];
+        t = count_track_from_options(options[k]);
         t.rec_begin = rec_offsets[k];
         t.rec_end = rec_offsets[k + 1];
         t.out_offset = out_offsets[k];
         t.delta_offset = (long long)cells;
-        t.read_length = o.read_length;
-        t.extend_bp = o.extend_bp;
-        t.min_template_length = o.min_template_length;
-        t.max_insert_size = o.max_insert_size;
-        t.shift_fwd = o.shift_fwd;
-        t.shift_rev = o.shift_rev;
         t.start = r.start;
         t.end = r.end;
         t.step = r.step;
         t.n_bins = r.n_bins;
-        t.flag_include = o.flag_include > 0 ? (o.flag_include & 0xffff) : 0;  // uint16 in ccounts_countOptions
-        t.flag_exclude = o.flag_exclude > 0 ? (o.flag_exclude & 0xffff) : 0;
-        t.min_mapq = o.min_mapq;
-        t.paired_end_mode = o.paired_end_mode;
-        t.one_read_per_bin = o.one_read_per_bin != 0;
-        t.pad_ = 0;
         plan.chunk_first[k] = (int)chunks;
         plan.tile_first[k] = (int)tiles;
-        chunks += (n + kChunk - 1) / kChunk;
-        tiles += ((long long)r.n_bins + kScanTile - 1) / kScanTile;
-        cells += ((size_t)r.n_bins + 1 + 3) / 4 * 4;
+        chunks += (t.rec_end - t.rec_begin + kChunk - 1) / kChunk;
+        tiles += (long long)count_scan_tiles((size_t)r.n_bins);
+        cells += count_delta_cells((size_t)r.n_bins);
         if (chunks >= INT_MAX || tiles >= INT_MAX) {
             set_last_error("count_alignment_records: too many records or bins for one call");
             return ROCCO_HIP_EINVAL;
@@ -421,21 +362,7 @@ int make_plan(const int64_t *rec_offsets, size_t K, const rocco_hip_count_option
     }
     plan.chunk_first[K] = (int)chunks;
     plan.tile_first[K] = (int)tiles;
-    plan.delta_cells = cells;
-    size_t at = 0;
-    plan.off_tracks = at;
-    at += align256(K * sizeof(CountTrack));
-    plan.off_chunk_first = at;
-    at += align256((K + 1) * sizeof(int));
-    plan.off_tile_first = at;
-    at += align256((K + 1) * sizeof(int));
-    plan.off_max = at;
-    at += align256(K * sizeof(int));
-    plan.off_tile_sums = at;
-    at += align256((size_t)tiles * sizeof(int));
-    plan.off_delta = at;
-    at += align256(cells * sizeof(int));
-    plan.bytes = at;
+    plan.at = CountLayout(K, (size_t)tiles, cells);
     return ROCCO_HIP_OK;
 }
 
@@ -448,7 +375,7 @@ size_t count_alignment_scratch_bytes(const int64_t *rec_offsets_host, size_t K, 
     if (make_plan(rec_offsets_host, K, options_host, regions_host, out_offsets_host, plan) != ROCCO_HIP_OK) {
         return 0;
     }
-    return plan.bytes;
+    return plan.at.bytes;
 }
 
 int launch_count_alignment_records(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
@@ -464,17 +391,18 @@ int launch_count_alignment_records(const int32_t *pos_dev, const int32_t *end_de
         return rc;
     }
     std::vector<int> maxima(K, 0);
-    // the copies below read this call's host vectors: no return before the stream has taken them
-    const int queued = [&]() -> int {
+    // the copies below read this call's host vectors (plan's going up, `maxima` coming back): no return before the stream has
+    // taken them
+    const int queued = queue_then_drain(stream, [&]() -> int {
         char *sc = (char *)scratch_dev;
-        CountTrack *tracks = (CountTrack *)(sc + plan.off_tracks);
-        int *chunk_first = (int *)(sc + plan.off_chunk_first), *tile_first = (int *)(sc + plan.off_tile_first);
-        int *max_dev = (int *)(sc + plan.off_max), *tile_sums = (int *)(sc + plan.off_tile_sums), *delta = (int *)(sc + plan.off_delta);
+        CountTrack *tracks = (CountTrack *)(sc + plan.at.tracks);
+        int *chunk_first = (int *)(sc + plan.at.chunk_first), *tile_first = (int *)(sc + plan.at.tile_first);
+        int *max_dev = (int *)(sc + plan.at.maxima), *tile_sums = (int *)(sc + plan.at.tile_sums), *delta = (int *)(sc + plan.at.delta);
         ROCCO_HIP_TRY(hipMemcpyAsync(tracks, plan.tracks.data(), K * sizeof(CountTrack), hipMemcpyHostToDevice, stream));
         ROCCO_HIP_TRY(hipMemcpyAsync(chunk_first, plan.chunk_first.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
         ROCCO_HIP_TRY(hipMemcpyAsync(tile_first, plan.tile_first.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-        // the difference arrays and, in front of them, the per-track maxima and the tile sums
-        ROCCO_HIP_TRY(hipMemsetAsync(max_dev, 0, plan.bytes - plan.off_max, stream));
+        // the difference arrays and, in front of them, the per-track maxima and the tile sums: the tail of the layout
+        ROCCO_HIP_TRY(hipMemsetAsync(max_dev, 0, plan.at.bytes - plan.at.maxima, stream));
         const int chunks = plan.chunk_first[K], tiles = plan.tile_first[K];
         if (chunks > 0) {
             const int grid = chunks < kMaxGrid ? chunks : kMaxGrid;
@@ -492,10 +420,8 @@ int launch_count_alignment_records(const int32_t *pos_dev, const int32_t *end_de
         ROCCO_HIP_TRY(hipMemcpyAsync(maxima.data(), max_dev, K * sizeof(int), hipMemcpyDeviceToHost, stream));
         ROCCO_HIP_TRY(hipStreamSynchronize(stream));  // the scratch buffer is the solver's; the maxima are the caller's guard
         return ROCCO_HIP_OK;
-    }();
+    });
     if (queued != ROCCO_HIP_OK) {
-        (void)hipStreamSynchronize(stream);  // (copies of plan's vectors or into `maxima` may be pending)
-        (void)hipGetLastError();
         return queued;
     }
     for (size_t k = 0; k < K; ++k) {

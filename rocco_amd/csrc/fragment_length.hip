@@ -16,6 +16,8 @@
 // integer, except the lag scores: one lane per lag runs the reference's sum in the reference's order (sequential in i,
 // multiply and add apart: -ffp-contract=off), so a score has the reference's bits on every schedule.
 #include "kernels.h"
+#include "record_layouts.h"
+#include "record_stream.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -36,36 +38,6 @@ constexpr int kMaxGrid = 2048;
 
 static_assert(kThreads == 256 && kDensityRecords % kThreads == 0 && kDensityWindow % kThreads == 0, "rocco_hip.h states the shape");
 static_assert((size_t)kMaxBlockSize * 2 * sizeof(int) + 256 <= 160 * 1024, "two int32 arrays of a block fit one CU's LDS");
-
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
-__device__ __forceinline__ int find_slot(const long long *__restrict__ offsets, int T, long long item)
-{
-    int lo = 0, hi = T;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= item) {
-            lo = mid;
-        } else {
-            hi = mid;
-        }
-    }
-    return lo;
-}
-
-// first index in [lo, hi) with pos[index] >= key (hi where none)
-__device__ __forceinline__ long long lower_bound_pos(const int *__restrict__ pos, long long lo, long long hi, long long key)
-{
-    while (lo < hi) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if ((long long)pos[mid] < key) {
-            lo = mid + 1;
-        } else {
-            hi = mid;
-        }
-    }
-    return lo;
-}
 
 // mapped[t]: records of track t with flag & 4 == 0 (what hts_idx_get_stat reports as mapped for a contig);
 // unsorted[t]: 1 when some pos is smaller than the one before it
@@ -339,22 +311,6 @@ struct NotNegative {
     __host__ __device__ bool operator()(const int &v) const { return v >= 0; }
 };
 
-int check_tracks(const int64_t *rec_offsets_host, size_t T, const char *who)
-{
-    if (T == 0 || T >= (size_t)0x7fffffff || rec_offsets_host[0] < 0) {
-        set_last_error(std::string(who) + ": the number of tracks or a record range is invalid");
-        return ROCCO_HIP_EINVAL;
-    }
-    for (size_t t = 0; t < T; ++t) {
-        const long long n = rec_offsets_host[t + 1] - rec_offsets_host[t];
-        if (n < 0 || n >= (1LL << 31)) {
-            set_last_error(std::string(who) + ": a track's record range is invalid");
-            return ROCCO_HIP_EINVAL;
-        }
-    }
-    return ROCCO_HIP_OK;
-}
-
 unsigned grid_for(long long items, int per_group)
 {
     const long long groups = (items + per_group - 1) / per_group;
@@ -371,12 +327,8 @@ long long chunks_of(long long contig_len, int block_size, int chunk)
     return n < 1 ? 0 : n;
 }
 
-struct CentersPlan {
-    size_t off_raw = 0, off_prefix = 0, off_density = 0, off_index = 0, off_density_sorted = 0, off_index_sorted = 0, off_cub = 0;
-    size_t cub_bytes = 0, bytes = 0;
-};
-
-int make_centers_plan(long long max_chunks, CentersPlan &plan)
+// bytes hipcub wants for the scan over max_chunks + 1 cells or the sort of max_chunks pairs, whichever is more
+int size_centers_cub(long long max_chunks, size_t &cub_bytes)
 {
     size_t scan_bytes = 0, sort_bytes = 0;
     const int n = (int)max_chunks;
@@ -387,24 +339,7 @@ int make_centers_plan(long long max_chunks, CentersPlan &plan)
         set_last_error("fragment_block_centers: cannot size the scan or the sort");
         return ROCCO_HIP_EHIP;
     }
-    const size_t cells = align256(((size_t)max_chunks + 1) * sizeof(int));
-    size_t at = 0;
-    plan.off_raw = at;
-    at += cells;
-    plan.off_prefix = at;
-    at += cells;
-    plan.off_density = at;
-    at += cells;
-    plan.off_index = at;
-    at += cells;
-    plan.off_density_sorted = at;
-    at += cells;
-    plan.off_index_sorted = at;
-    at += cells;
-    plan.off_cub = at;
-    plan.cub_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
-    at += align256(plan.cub_bytes > 0 ? plan.cub_bytes : 1);
-    plan.bytes = at;
+    cub_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
     return ROCCO_HIP_OK;
 }
 
@@ -420,15 +355,12 @@ long long max_chunks_of(const int64_t *contig_len_host, size_t T, int block_size
 
 }  // namespace
 
-size_t record_flag_facts_scratch_bytes(size_t T)
-{
-    return align256((T + 1) * sizeof(long long)) + align256(T * sizeof(unsigned long long)) + align256(T * sizeof(int));
-}
+size_t record_flag_facts_scratch_bytes(size_t T) { return FlagFactsLayout(T).bytes; }
 
 int launch_record_flag_facts(const int32_t *pos_dev, const uint16_t *flag_dev, const int64_t *rec_offsets_host, size_t T,
                              int64_t *mapped_out_host, int32_t *unsorted_out_host, void *scratch_dev, hipStream_t stream)
 {
-    int rc = check_tracks(rec_offsets_host, T, "record_flag_facts");
+    int rc = check_record_tracks(rec_offsets_host, T, "record_flag_facts");
     if (rc != ROCCO_HIP_OK) {
         return rc;
     }
@@ -436,11 +368,13 @@ int launch_record_flag_facts(const int32_t *pos_dev, const uint16_t *flag_dev, c
     std::vector<unsigned long long> mapped(T, 0);
     std::vector<int> unsorted(T, 0);
     const long long records = offsets[T] - offsets[0];
+    const FlagFactsLayout at(T);
     char *sc = (char *)scratch_dev;
-    long long *offsets_dev = (long long *)sc;
-    unsigned long long *mapped_dev = (unsigned long long *)(sc + align256((T + 1) * sizeof(long long)));
-    int *unsorted_dev = (int *)((char *)mapped_dev + align256(T * sizeof(unsigned long long)));
-    const int queued = [&]() -> int {
+    long long *offsets_dev = (long long *)(sc + at.rec_offsets);
+    unsigned long long *mapped_dev = (unsigned long long *)(sc + at.mapped);
+    int *unsorted_dev = (int *)(sc + at.unsorted);
+    // the copies below read and write this call's host vectors: no return before the stream is done with them
+    const int queued = queue_then_drain(stream, [&]() -> int {
         ROCCO_HIP_TRY(hipMemcpyAsync(offsets_dev, offsets.data(), (T + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
         ROCCO_HIP_TRY(hipMemsetAsync(mapped_dev, 0, T * sizeof(unsigned long long), stream));
         ROCCO_HIP_TRY(hipMemsetAsync(unsorted_dev, 0, T * sizeof(int), stream));
@@ -453,10 +387,8 @@ int launch_record_flag_facts(const int32_t *pos_dev, const uint16_t *flag_dev, c
         ROCCO_HIP_TRY(hipMemcpyAsync(unsorted.data(), unsorted_dev, T * sizeof(int), hipMemcpyDeviceToHost, stream));
         ROCCO_HIP_TRY(hipStreamSynchronize(stream));
         return ROCCO_HIP_OK;
-    }();
+    });
     if (queued != ROCCO_HIP_OK) {
-        (void)hipStreamSynchronize(stream);  // (copies of this call's vectors may be pending)
-        (void)hipGetLastError();
         return queued;
     }
     for (size_t t = 0; t < T; ++t) {
@@ -469,7 +401,7 @@ int launch_record_flag_facts(const int32_t *pos_dev, const uint16_t *flag_dev, c
 size_t fragment_block_centers_scratch_bytes(const int64_t *rec_offsets_host, size_t T, const int64_t *contig_len_host, int block_size,
                                             int rolling_chunk_size)
 {
-    if (check_tracks(rec_offsets_host, T, "fragment_block_centers") != ROCCO_HIP_OK || block_size < 64 || rolling_chunk_size < 1) {
+    if (check_record_tracks(rec_offsets_host, T, "fragment_block_centers") != ROCCO_HIP_OK || block_size < 64 || rolling_chunk_size < 1) {
         return 0;
     }
     const long long max_chunks = max_chunks_of(contig_len_host, T, block_size, rolling_chunk_size);
@@ -477,11 +409,11 @@ size_t fragment_block_centers_scratch_bytes(const int64_t *rec_offsets_host, siz
         set_last_error("fragment_block_centers: a contig has 2^31 chunks or more");
         return 0;
     }
-    CentersPlan plan;
-    if (make_centers_plan(max_chunks, plan) != ROCCO_HIP_OK) {
+    size_t cub_bytes = 0;
+    if (size_centers_cub(max_chunks, cub_bytes) != ROCCO_HIP_OK) {
         return 0;
     }
-    return plan.bytes;
+    return CentersLayout((size_t)max_chunks, cub_bytes).bytes;
 }
 
 int launch_fragment_block_centers(const int32_t *pos_dev, const uint16_t *flag_dev, const int64_t *rec_offsets_host, size_t T,
@@ -495,19 +427,20 @@ int launch_fragment_block_centers(const int32_t *pos_dev, const uint16_t *flag_d
         set_last_error("fragment_block_centers: parameters below the reference's clamps, or outputs without their offsets");
         return ROCCO_HIP_EINVAL;
     }
-    int rc = check_tracks(rec_offsets_host, T, "fragment_block_centers");
+    int rc = check_record_tracks(rec_offsets_host, T, "fragment_block_centers");
     if (rc != ROCCO_HIP_OK) {
         return rc;
     }
     const long long max_chunks = max_chunks_of(contig_len_host, T, block_size, rolling_chunk_size);
-    CentersPlan plan;
-    if (max_chunks >= 0x7ffffffeLL || (rc = make_centers_plan(max_chunks, plan)) != ROCCO_HIP_OK) {
+    size_t cub_size = 0;
+    if (max_chunks >= 0x7ffffffeLL || (rc = size_centers_cub(max_chunks, cub_size)) != ROCCO_HIP_OK) {
         return max_chunks >= 0x7ffffffeLL ? ROCCO_HIP_EINVAL : rc;
     }
+    const CentersLayout lay((size_t)max_chunks, cub_size);
     char *sc = (char *)scratch_dev;
-    int *raw = (int *)(sc + plan.off_raw), *prefix = (int *)(sc + plan.off_prefix), *density = (int *)(sc + plan.off_density);
-    int *index = (int *)(sc + plan.off_index), *density_sorted = (int *)(sc + plan.off_density_sorted);
-    int *index_sorted = (int *)(sc + plan.off_index_sorted);
+    int *raw = (int *)(sc + lay.raw), *prefix = (int *)(sc + lay.prefix), *density = (int *)(sc + lay.density);
+    int *index = (int *)(sc + lay.index), *density_sorted = (int *)(sc + lay.density_sorted);
+    int *index_sorted = (int *)(sc + lay.index_sorted);
     int win_size = block_size / rolling_chunk_size;  // ccounts_backend.c:1274-1283
     if (win_size < 1) {
         win_size = 1;
@@ -541,13 +474,13 @@ int launch_fragment_block_centers(const int32_t *pos_dev, const uint16_t *flag_d
                                (long long)contig_len_host[t], n, raw);
             ROCCO_HIP_TRY(hipGetLastError());
         }
-        size_t cub_bytes = plan.cub_bytes;
-        ROCCO_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc + plan.off_cub, cub_bytes, (const int *)raw, prefix, n + 1, stream));
+        size_t cub_bytes = cub_size;
+        ROCCO_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc + lay.cub, cub_bytes, (const int *)raw, prefix, n + 1, stream));
         hipLaunchKernelGGL(window_sums_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
                            (const int *)prefix, n, win_size, density, index);
         ROCCO_HIP_TRY(hipGetLastError());
-        cub_bytes = plan.cub_bytes;
-        ROCCO_HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(sc + plan.off_cub, cub_bytes, (const int *)density, density_sorted,
+        cub_bytes = cub_size;
+        ROCCO_HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(sc + lay.cub, cub_bytes, (const int *)density, density_sorted,
                                                                    (const int *)index, index_sorted, n, 0, 32, stream));
         if (density_out_dev != nullptr) {
             ROCCO_HIP_TRY(hipMemcpyAsync(density_out_dev + chunk_offsets_host[t], density, (size_t)n * sizeof(int),
@@ -573,17 +506,15 @@ int launch_fragment_block_centers(const int32_t *pos_dev, const uint16_t *flag_d
                 const int upto = (int)((long long)have + more < n ? (long long)have + more : n);
                 values.resize((size_t)upto);
                 indices.resize((size_t)upto);
-                const int copied = [&]() -> int {
+                const int copied = queue_then_drain(stream, [&]() -> int {  // (into `values` and `indices`)
                     ROCCO_HIP_TRY(hipMemcpyAsync(values.data() + have, density_sorted + have, (size_t)(upto - have) * sizeof(int),
                                                  hipMemcpyDeviceToHost, stream));
                     ROCCO_HIP_TRY(hipMemcpyAsync(indices.data() + have, index_sorted + have, (size_t)(upto - have) * sizeof(int),
                                                  hipMemcpyDeviceToHost, stream));
                     ROCCO_HIP_TRY(hipStreamSynchronize(stream));
                     return ROCCO_HIP_OK;
-                }();
+                });
                 if (copied != ROCCO_HIP_OK) {
-                    (void)hipStreamSynchronize(stream);
-                    (void)hipGetLastError();
                     return copied;
                 }
                 have = upto;
@@ -612,11 +543,7 @@ int launch_fragment_block_centers(const int32_t *pos_dev, const uint16_t *flag_d
     return ROCCO_HIP_OK;
 }
 
-size_t strand_xcorr_scratch_bytes(size_t T, size_t n_blocks)
-{
-    return align256((T + 1) * sizeof(long long)) + align256(T * sizeof(int)) + align256(n_blocks * sizeof(int)) +
-           align256(n_blocks * sizeof(long long)) + 3 * align256(n_blocks * sizeof(int)) + align256(n_blocks * sizeof(double));
-}
+size_t strand_xcorr_scratch_bytes(size_t T, size_t n_blocks) { return XcorrLayout(T, n_blocks).bytes; }
 
 int launch_strand_xcorr_blocks(const int32_t *pos_dev, const int32_t *end_dev, const uint16_t *flag_dev, const int64_t *rec_offsets_host,
                                size_t T, const int32_t *block_track_host, const int64_t *block_start_host, size_t n_blocks,
@@ -624,7 +551,7 @@ int launch_strand_xcorr_blocks(const int32_t *pos_dev, const int32_t *end_dev, c
                                int32_t *best_lag_out_host, double *best_score_out_host, int32_t *fwd_sum_out_host,
                                int32_t *rev_sum_out_host, void *scratch_dev, hipStream_t stream)
 {
-    int rc = check_tracks(rec_offsets_host, T, "strand_xcorr_blocks");
+    int rc = check_record_tracks(rec_offsets_host, T, "strand_xcorr_blocks");
     if (rc != ROCCO_HIP_OK) {
         return rc;
     }
@@ -650,21 +577,14 @@ int launch_strand_xcorr_blocks(const int32_t *pos_dev, const int32_t *end_dev, c
     std::vector<long long> offsets(rec_offsets_host, rec_offsets_host + T + 1), starts(block_start_host, block_start_host + n_blocks);
     std::vector<int> best_lag(n_blocks), fwd_sum(n_blocks), rev_sum(n_blocks);
     std::vector<double> best_score(n_blocks);
-    char *at = (char *)scratch_dev;
-    const auto carve = [&at](size_t bytes) {
-        char *p = at;
-        at += align256(bytes);
-        return p;
-    };
-    long long *offsets_dev = (long long *)carve((T + 1) * sizeof(long long));
-    int *min_lag_dev = (int *)carve(T * sizeof(int));
-    int *track_dev = (int *)carve(n_blocks * sizeof(int));
-    long long *start_dev = (long long *)carve(n_blocks * sizeof(long long));
-    int *lag_dev = (int *)carve(n_blocks * sizeof(int)), *fwd_dev = (int *)carve(n_blocks * sizeof(int));
-    int *rev_dev = (int *)carve(n_blocks * sizeof(int));
-    double *score_dev = (double *)carve(n_blocks * sizeof(double));
+    const XcorrLayout at(T, n_blocks);
+    char *sc = (char *)scratch_dev;
+    long long *offsets_dev = (long long *)(sc + at.rec_offsets), *start_dev = (long long *)(sc + at.block_start);
+    int *min_lag_dev = (int *)(sc + at.min_lag), *track_dev = (int *)(sc + at.block_track);
+    int *lag_dev = (int *)(sc + at.best_lag), *fwd_dev = (int *)(sc + at.fwd_sum), *rev_dev = (int *)(sc + at.rev_sum);
+    double *score_dev = (double *)(sc + at.best_score);
     const size_t lds_bytes = (size_t)block_size * 2 * sizeof(int);
-    const int queued = [&]() -> int {
+    const int queued = queue_then_drain(stream, [&]() -> int {  // (the caller's arrays and this call's vectors are read and written)
         ROCCO_HIP_TRY(hipFuncSetAttribute((const void *)strand_xcorr_blocks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)lds_bytes));
         ROCCO_HIP_TRY(hipMemcpyAsync(offsets_dev, offsets.data(), (T + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
@@ -681,10 +601,8 @@ int launch_strand_xcorr_blocks(const int32_t *pos_dev, const int32_t *end_dev, c
         ROCCO_HIP_TRY(hipMemcpyAsync(best_score.data(), score_dev, n_blocks * sizeof(double), hipMemcpyDeviceToHost, stream));
         ROCCO_HIP_TRY(hipStreamSynchronize(stream));
         return ROCCO_HIP_OK;
-    }();
+    });
     if (queued != ROCCO_HIP_OK) {
-        (void)hipStreamSynchronize(stream);  // (copies of this call's arrays may be pending)
-        (void)hipGetLastError();
         return queued;
     }
     for (size_t b = 0; b < n_blocks; ++b) {
@@ -725,11 +643,11 @@ long long most_records(const int64_t *rec_offsets_host, size_t T)
 size_t template_lengths_scratch_bytes(const int64_t *rec_offsets_host, size_t T)
 {
     size_t select_bytes = 0;
-    if (check_tracks(rec_offsets_host, T, "template_lengths") != ROCCO_HIP_OK ||
+    if (check_record_tracks(rec_offsets_host, T, "template_lengths") != ROCCO_HIP_OK ||
         size_select(most_records(rec_offsets_host, T), select_bytes) != ROCCO_HIP_OK) {
         return 0;
     }
-    return align256((T + 1) * sizeof(long long)) + 2 * align256(T * sizeof(int)) + align256(select_bytes > 0 ? select_bytes : 1);
+    return TemplateLayout(T, select_bytes).bytes;
 }
 
 int launch_template_lengths(const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mate_same_dev,
@@ -737,7 +655,7 @@ int launch_template_lengths(const int32_t *isize_dev, const uint16_t *flag_dev, 
                             int max_insert_size, int32_t *lengths_tmp_dev, int32_t *lengths_out_dev, int64_t *count_out_host,
                             void *scratch_dev, hipStream_t stream)
 {
-    int rc = check_tracks(rec_offsets_host, T, "template_lengths");
+    int rc = check_record_tracks(rec_offsets_host, T, "template_lengths");
     size_t select_bytes = 0;
     if (rc != ROCCO_HIP_OK || (rc = size_select(most_records(rec_offsets_host, T), select_bytes)) != ROCCO_HIP_OK) {
         return rc;
@@ -745,12 +663,12 @@ int launch_template_lengths(const int32_t *isize_dev, const uint16_t *flag_dev, 
     std::vector<long long> offsets(rec_offsets_host, rec_offsets_host + T + 1);
     std::vector<int> counts(T, 0);
     const long long records = offsets[T] - offsets[0];
+    const TemplateLayout at(T, select_bytes);
     char *sc = (char *)scratch_dev;
-    long long *offsets_dev = (long long *)sc;
-    int *min_insert_dev = (int *)(sc + align256((T + 1) * sizeof(long long)));
-    int *counts_dev = (int *)((char *)min_insert_dev + align256(T * sizeof(int)));
-    char *select_dev = (char *)counts_dev + align256(T * sizeof(int));
-    const int queued = [&]() -> int {
+    long long *offsets_dev = (long long *)(sc + at.rec_offsets);
+    int *min_insert_dev = (int *)(sc + at.min_insert), *counts_dev = (int *)(sc + at.counts);
+    char *select_dev = sc + at.select;
+    const int queued = queue_then_drain(stream, [&]() -> int {  // (this call's vectors go up and `counts` comes back)
         ROCCO_HIP_TRY(hipMemcpyAsync(offsets_dev, offsets.data(), (T + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
         ROCCO_HIP_TRY(hipMemcpyAsync(min_insert_dev, min_insert_host, T * sizeof(int), hipMemcpyHostToDevice, stream));
         ROCCO_HIP_TRY(hipMemsetAsync(counts_dev, 0, T * sizeof(int), stream));
@@ -772,10 +690,8 @@ int launch_template_lengths(const int32_t *isize_dev, const uint16_t *flag_dev, 
         ROCCO_HIP_TRY(hipMemcpyAsync(counts.data(), counts_dev, T * sizeof(int), hipMemcpyDeviceToHost, stream));
         ROCCO_HIP_TRY(hipStreamSynchronize(stream));
         return ROCCO_HIP_OK;
-    }();
+    });
     if (queued != ROCCO_HIP_OK) {
-        (void)hipStreamSynchronize(stream);  // (copies of this call's vectors may be pending)
-        (void)hipGetLastError();
         return queued;
     }
     for (size_t t = 0; t < T; ++t) {

@@ -22,10 +22,10 @@
 // are read and filtered (time), never a wrong count.
 #include "kernels.h"
 #include "record_cells.h"
+#include "record_layouts.h"
+#include "record_stream.h"
 
 #include <hipcub/hipcub.hpp>
-
-#include <cstring>
 
 namespace rocco {
 
@@ -41,21 +41,6 @@ constexpr int kMaxGrid = ROCCO_COUNT_INTERVALS_MAX_GRID;  // workgroups of the c
 static_assert(kUnit == ROCCO_COUNT_INTERVALS_UNIT && kWavesPerGroup == ROCCO_COUNT_INTERVALS_WAVES_PER_GROUP && kMaxGrid > 0 &&
                   kUnit % kWave == 0,
               "rocco_hip.h states the shape");
-
-// largest t in [0, T) with offsets[t] <= item (offsets ascends, item < offsets[T]): entries without work are skipped
-__device__ __forceinline__ int find_slot(const long long *__restrict__ offsets, int T, long long item)
-{
-    int lo = 0, hi = T;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= item) {
-            lo = mid;
-        } else {
-            hi = mid;
-        }
-    }
-    return lo;
-}
 
 // facts[2 t]: L of track t; facts[2 t + 1]: 1 when some pos is smaller than the one before it
 __global__ __launch_bounds__(kThreads) void interval_track_facts_kernel(const int *__restrict__ pos, const int *__restrict__ end,
@@ -92,20 +77,6 @@ __global__ __launch_bounds__(kThreads) void interval_track_facts_kernel(const in
             }
         }
     }
-}
-
-// first index in [lo, hi) with pos[index] >= key (hi where none)
-__device__ __forceinline__ long long lower_bound_pos(const int *__restrict__ pos, long long lo, long long hi, long long key)
-{
-    while (lo < hi) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if ((long long)pos[mid] < key) {
-            lo = mid + 1;
-        } else {
-            hi = mid;
-        }
-    }
-    return lo;
 }
 
 // one thread per (interval p, file f), pair = p * F + f: cand_lo / cand_n = its candidates, units = its work units.
@@ -199,39 +170,16 @@ __global__ __launch_bounds__(kThreads) void interval_count_kernel(
     }
 }
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
-struct IntervalPlan {
-    size_t off_rec_offsets = 0, off_facts = 0, off_lo = 0, off_n = 0, off_units = 0, off_unit_first = 0, off_scan = 0;
-    size_t scan_bytes = 0, bytes = 0;
-};
-
-int make_interval_plan(size_t T, size_t pairs, IntervalPlan &plan)
+// bytes hipcub's scan over the pairs + 1 unit counts wants
+int size_interval_scan(size_t pairs, size_t &scan_bytes)
 {
-    size_t scan_bytes = 0;
+    scan_bytes = 0;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const long long *)nullptr, (long long *)nullptr, (int)(pairs + 1)) !=
         hipSuccess) {
         (void)hipGetLastError();
         set_last_error("count_alignment_intervals: cannot size the scan");
         return ROCCO_HIP_EHIP;
     }
-    size_t at = 0;
-    plan.off_rec_offsets = at;
-    at += align256((T + 1) * sizeof(long long));
-    plan.off_facts = at;
-    at += align256(2 * T * sizeof(int));
-    plan.off_lo = at;
-    at += align256(pairs * sizeof(long long));
-    plan.off_n = at;
-    at += align256(pairs * sizeof(int));
-    plan.off_units = at;
-    at += align256((pairs + 1) * sizeof(long long));
-    plan.off_unit_first = at;
-    at += align256((pairs + 1) * sizeof(long long));
-    plan.off_scan = at;
-    at += align256(scan_bytes > 0 ? scan_bytes : 1);
-    plan.scan_bytes = scan_bytes;
-    plan.bytes = at;
     return ROCCO_HIP_OK;
 }
 
@@ -242,30 +190,18 @@ int check_interval_shape(const int64_t *rec_offsets_host, size_t F, size_t C, si
         set_last_error("count_alignment_intervals: files x contigs or intervals x files is out of range");
         return ROCCO_HIP_EINVAL;
     }
-    const size_t T = F * C;
-    if (rec_offsets_host[0] < 0) {
-        set_last_error("count_alignment_intervals: a track's record range is invalid");
-        return ROCCO_HIP_EINVAL;
-    }
-    for (size_t t = 0; t < T; ++t) {
-        const long long n = rec_offsets_host[t + 1] - rec_offsets_host[t];
-        if (n < 0 || n >= (1LL << 31)) {
-            set_last_error("count_alignment_intervals: a track's record range is invalid");
-            return ROCCO_HIP_EINVAL;
-        }
-    }
-    return ROCCO_HIP_OK;
+    return check_record_tracks(rec_offsets_host, F * C, "count_alignment_intervals");
 }
 
 }  // namespace
 
 size_t count_intervals_scratch_bytes(const int64_t *rec_offsets_host, size_t F, size_t C, size_t P)
 {
-    IntervalPlan plan;
-    if (check_interval_shape(rec_offsets_host, F, C, P) != ROCCO_HIP_OK || make_interval_plan(F * C, P * F, plan) != ROCCO_HIP_OK) {
+    size_t scan_bytes = 0;
+    if (check_interval_shape(rec_offsets_host, F, C, P) != ROCCO_HIP_OK || size_interval_scan(P * F, scan_bytes) != ROCCO_HIP_OK) {
         return 0;
     }
-    return plan.bytes;
+    return IntervalLayout(F * C, P * F, scan_bytes).bytes;
 }
 
 int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
@@ -274,38 +210,23 @@ int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_
                                      const int32_t *contig_id_dev, const int32_t *start_dev, const int32_t *end_region_dev, size_t P,
                                      int32_t *out_dev, int32_t *track_facts_out_host, void *scratch_dev, hipStream_t stream)
 {
-    int rc = check_interval_shape(rec_offsets_host, F, C, P);
-    if (rc != ROCCO_HIP_OK) {
-        return rc;
-    }
     const size_t T = F * C, pairs = P * F;
-    IntervalPlan plan;
-    if ((rc = make_interval_plan(T, pairs, plan)) != ROCCO_HIP_OK) {
+    size_t scan_bytes = 0;
+    int rc = check_interval_shape(rec_offsets_host, F, C, P);
+    if (rc != ROCCO_HIP_OK || (rc = size_interval_scan(pairs, scan_bytes)) != ROCCO_HIP_OK) {
         return rc;
     }
-    const rocco_hip_count_options &o = *options_host;
-    CountTrack options;
-    memset(&options, 0, sizeof(options));
-    options.read_length = o.read_length;
-    options.extend_bp = o.extend_bp;
-    options.min_template_length = o.min_template_length;
-    options.max_insert_size = o.max_insert_size;
-    options.shift_fwd = o.shift_fwd;
-    options.shift_rev = o.shift_rev;
-    options.flag_include = o.flag_include > 0 ? (o.flag_include & 0xffff) : 0;  // uint16 in ccounts_countOptions
-    options.flag_exclude = o.flag_exclude > 0 ? (o.flag_exclude & 0xffff) : 0;
-    options.min_mapq = o.min_mapq;
-    options.paired_end_mode = o.paired_end_mode;
-    options.one_read_per_bin = o.one_read_per_bin != 0;
+    const IntervalLayout at(T, pairs, scan_bytes);
+    const CountTrack options = count_track_from_options(*options_host);
     std::vector<long long> offsets(rec_offsets_host, rec_offsets_host + T + 1);
     std::vector<int> facts(2 * T, 0);
     const long long records = offsets[T] - offsets[0];
     // the copies below read this call's host vectors: no return before the stream has taken them
-    const int queued = [&]() -> int {
+    const int queued = queue_then_drain(stream, [&]() -> int {
         char *sc = (char *)scratch_dev;
-        long long *rec_offsets = (long long *)(sc + plan.off_rec_offsets), *cand_lo = (long long *)(sc + plan.off_lo);
-        long long *units = (long long *)(sc + plan.off_units), *unit_first = (long long *)(sc + plan.off_unit_first);
-        int *facts_dev = (int *)(sc + plan.off_facts), *cand_n = (int *)(sc + plan.off_n);
+        long long *rec_offsets = (long long *)(sc + at.rec_offsets), *cand_lo = (long long *)(sc + at.cand_lo);
+        long long *units = (long long *)(sc + at.units), *unit_first = (long long *)(sc + at.unit_first);
+        int *facts_dev = (int *)(sc + at.facts), *cand_n = (int *)(sc + at.cand_n);
         ROCCO_HIP_TRY(hipMemcpyAsync(rec_offsets, offsets.data(), (T + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
         ROCCO_HIP_TRY(hipMemsetAsync(facts_dev, 0, 2 * T * sizeof(int), stream));
         ROCCO_HIP_TRY(hipMemsetAsync(out_dev, 0, pairs * sizeof(int), stream));
@@ -318,8 +239,7 @@ int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_
                            (const int *)pos_dev, rec_offsets, facts_dev, (int)F, (int)C, (const int *)contig_id_dev,
                            (const int *)start_dev, (const int *)end_region_dev, (long long)pairs, cand_lo, cand_n, units);
         ROCCO_HIP_TRY(hipGetLastError());
-        size_t scan_bytes = plan.scan_bytes;
-        ROCCO_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc + plan.off_scan, scan_bytes, (const long long *)units, unit_first,
+        ROCCO_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc + at.scan, scan_bytes, (const long long *)units, unit_first,
                                                        (int)(pairs + 1), stream));
         if (records > 0) {
             // at least one wavefront per pair is the most the launch can use when every pair has one unit; pairs with many
@@ -338,10 +258,8 @@ int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_
         ROCCO_HIP_TRY(hipMemcpyAsync(facts.data(), facts_dev, 2 * T * sizeof(int), hipMemcpyDeviceToHost, stream));
         ROCCO_HIP_TRY(hipStreamSynchronize(stream));  // the scratch buffer is the solver's; the facts are the caller's guard
         return ROCCO_HIP_OK;
-    }();
+    });
     if (queued != ROCCO_HIP_OK) {
-        (void)hipStreamSynchronize(stream);  // (copies of this call's vectors may be pending)
-        (void)hipGetLastError();
         return queued;
     }
     for (size_t i = 0; i < 2 * T; ++i) {

@@ -9,22 +9,7 @@
 
 namespace rocco {
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 inline int lean_tiles(size_t n) { return (int)((n + kLeanTile - 1) / kLeanTile); }
-
-// Regions of one buffer, one behind the other, each aligned to 256 bytes.
-struct Layout {
-    size_t off = 0, uploaded = 0;
-    size_t at(size_t bytes)
-    {
-        const size_t begin = off;
-        off += align_up(bytes, 256);
-        return begin;
-    }
-    void end_upload() { uploaded = off; }  // what was laid out so far is the prefix copied from the host
-    size_t bytes() const { return off; }
-};
 
 // What tells the kinds of LeanTask apart; everything else follows from the level and the problem.
 struct LeanTaskKind {

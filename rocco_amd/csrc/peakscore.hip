@@ -176,7 +176,6 @@ __global__ __launch_bounds__(1024) void bh_finish_kernel(const u64 *__restrict__
     }
 }
 
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace
 

@@ -3,6 +3,8 @@
 // (one bin per interval): one copy of the filter / fragment / clip / index arithmetic.
 #pragma once
 
+#include "../../include/rocco_hip.h"
+
 namespace rocco {
 
 namespace {
@@ -19,6 +21,25 @@ struct CountTrack {
     int flag_include, flag_exclude, min_mapq, paired_end_mode, one_read_per_bin;
     int pad_;
 };
+
+// The caller's options as the kernels read them, one conversion for count.hip and interval_count.hip: the two count the
+// same record alike.  Records, region and buffer places are zero: the caller's to fill.
+inline CountTrack count_track_from_options(const rocco_hip_count_options &o)
+{
+    CountTrack t = {};
+    t.read_length = o.read_length;
+    t.extend_bp = o.extend_bp;
+    t.min_template_length = o.min_template_length;
+    t.max_insert_size = o.max_insert_size;
+    t.shift_fwd = o.shift_fwd;
+    t.shift_rev = o.shift_rev;
+    t.flag_include = o.flag_include > 0 ? (o.flag_include & 0xffff) : 0;  // uint16 in ccounts_countOptions
+    t.flag_exclude = o.flag_exclude > 0 ? (o.flag_exclude & 0xffff) : 0;
+    t.min_mapq = o.min_mapq;
+    t.paired_end_mode = o.paired_end_mode;
+    t.one_read_per_bin = o.one_read_per_bin != 0;
+    return t;
+}
 
 // One record through the reference's loop (ccounts_backend.c:2420-2560).  Returns false when the record adds nothing;
 // otherwise *i0 is the cell that gains one and *i1 the cell that loses one (-1: none, the one-read-per-bin form).

@@ -1,0 +1,117 @@
+// rocco_amd/csrc/record_layouts.h -- where the launchers of count.hip, interval_count.hip and fragment_length.hip keep
+// their regions of the solver's scratch buffer: one struct per launcher, read by its *_scratch_bytes (the total) and by
+// the launcher itself (the offsets), so the two cannot drift apart.  A hipcub region takes the bytes hipcub asked for and
+// is never empty.  Plain C++ (no HIP call): tests/host_logic/harness.cpp checks the layouts on the CPU.
+#pragma once
+
+#include "common.h"
+#include "record_cells.h"
+
+namespace rocco {
+
+namespace {  // (as record_cells.h, whose CountTrack CountLayout measures)
+
+// a track's difference array (n_bins + 1 cells, a multiple of 4) and its scan tiles
+inline size_t count_delta_cells(size_t n_bins) { return (n_bins + 1 + 3) / 4 * 4; }
+inline size_t count_scan_tiles(size_t n_bins) { return (n_bins + ROCCO_COUNT_SCAN_TILE - 1) / ROCCO_COUNT_SCAN_TILE; }
+
+// launch_count_alignment_records: K tracks with `tiles` scan tiles and `cells` difference cells in all.  maxima, tile_sums
+// and delta stay the tail of the buffer, in this order: the launcher zeroes them with one memset from `maxima` to `bytes`.
+struct CountLayout {
+    size_t tracks, chunk_first, tile_first, maxima, tile_sums, delta, bytes;
+    CountLayout(size_t K, size_t tiles, size_t cells)
+    {
+        Layout lay;
+        tracks = lay.at(K * sizeof(CountTrack));
+        chunk_first = lay.at((K + 1) * sizeof(int));
+        tile_first = lay.at((K + 1) * sizeof(int));
+        maxima = lay.at(K * sizeof(int));
+        tile_sums = lay.at(tiles * sizeof(int));
+        delta = lay.at(cells * sizeof(int));
+        bytes = lay.bytes();
+    }
+};
+
+// launch_count_alignment_intervals: T tracks, `pairs` (interval, file) pairs, hipcub's scan over pairs + 1 unit counts
+struct IntervalLayout {
+    size_t rec_offsets, facts, cand_lo, cand_n, units, unit_first, scan, bytes;
+    IntervalLayout(size_t T, size_t pairs, size_t scan_bytes)
+    {
+        Layout lay;
+        rec_offsets = lay.at((T + 1) * sizeof(long long));
+        facts = lay.at(2 * T * sizeof(int));
+        cand_lo = lay.at(pairs * sizeof(long long));
+        cand_n = lay.at(pairs * sizeof(int));
+        units = lay.at((pairs + 1) * sizeof(long long));
+        unit_first = lay.at((pairs + 1) * sizeof(long long));
+        scan = lay.at(scan_bytes > 0 ? scan_bytes : 1);
+        bytes = lay.bytes();
+    }
+};
+
+// launch_record_flag_facts
+struct FlagFactsLayout {
+    size_t rec_offsets, mapped, unsorted, bytes;
+    explicit FlagFactsLayout(size_t T)
+    {
+        Layout lay;
+        rec_offsets = lay.at((T + 1) * sizeof(long long));
+        mapped = lay.at(T * sizeof(unsigned long long));
+        unsorted = lay.at(T * sizeof(int));
+        bytes = lay.bytes();
+    }
+};
+
+// launch_fragment_block_centers: six arrays of max_chunks + 1 cells (the longest contig's), hipcub's scan and sort
+struct CentersLayout {
+    size_t raw, prefix, density, index, density_sorted, index_sorted, cub, bytes;
+    CentersLayout(size_t max_chunks, size_t cub_bytes)
+    {
+        const size_t cells = (max_chunks + 1) * sizeof(int);
+        Layout lay;
+        raw = lay.at(cells);
+        prefix = lay.at(cells);
+        density = lay.at(cells);
+        index = lay.at(cells);
+        density_sorted = lay.at(cells);
+        index_sorted = lay.at(cells);
+        cub = lay.at(cub_bytes > 0 ? cub_bytes : 1);
+        bytes = lay.bytes();
+    }
+};
+
+// launch_strand_xcorr_blocks
+struct XcorrLayout {
+    size_t rec_offsets, min_lag, block_track, block_start, best_lag, fwd_sum, rev_sum, best_score, bytes;
+    XcorrLayout(size_t T, size_t n_blocks)
+    {
+        Layout lay;
+        rec_offsets = lay.at((T + 1) * sizeof(long long));
+        min_lag = lay.at(T * sizeof(int));
+        block_track = lay.at(n_blocks * sizeof(int));
+        block_start = lay.at(n_blocks * sizeof(long long));
+        best_lag = lay.at(n_blocks * sizeof(int));
+        fwd_sum = lay.at(n_blocks * sizeof(int));
+        rev_sum = lay.at(n_blocks * sizeof(int));
+        best_score = lay.at(n_blocks * sizeof(double));
+        bytes = lay.bytes();
+    }
+};
+
+// launch_template_lengths: hipcub's stream compaction over the longest track
+struct TemplateLayout {
+    size_t rec_offsets, min_insert, counts, select, bytes;
+    TemplateLayout(size_t T, size_t select_bytes)
+    {
+        Layout lay;
+        rec_offsets = lay.at((T + 1) * sizeof(long long));
+        min_insert = lay.at(T * sizeof(int));
+        counts = lay.at(T * sizeof(int));
+        select = lay.at(select_bytes > 0 ? select_bytes : 1);
+        bytes = lay.bytes();
+    }
+};
+
+}  // namespace
+
+}  // namespace rocco

@@ -2065,7 +2065,6 @@ __global__ __launch_bounds__(256) void subtract_kernel(const double *__restrict_
     }
 }
 
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace
 

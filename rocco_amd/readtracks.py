@@ -329,6 +329,15 @@ def _records_on_device(records_list: Sequence[AlignmentRecords], dev) -> Tuple[A
     return out, offsets
 
 
+def _record_args(records_list, cat=None, offsets=None, dev=None):
+    """What every record entry point of the C ABI takes: the tracks' records back to back on one device (``cat`` and
+    ``offsets`` where the caller holds them already, else uploaded to ``dev`` or to the device the tracks name), the
+    T + 1 ``rec_offsets`` as ctypes reads them, and that device."""
+    if cat is None:
+        cat, offsets = _records_on_device(records_list, dev if dev is not None else _device_for(records_list))
+    return cat, (ctypes.c_longlong * len(offsets))(*[int(o) for o in offsets]), cat.pos.device
+
+
 def _records_slice(records: AlignmentRecords, lo: int, hi: int) -> AlignmentRecords:
     out = object.__new__(AlignmentRecords)
     for name, _ in _RECORD_FIELDS:
@@ -347,10 +356,9 @@ def _count_concatenated(cat: AlignmentRecords, offsets: Sequence[int], regions: 
     K = len(offsets) - 1
     if K <= 0 or len(regions) != K or len(options_list) != K:
         raise ValueError("one region and one set of options per track are required")
-    dev = cat.pos.device
+    cat, rec_offsets, dev = _record_args(None, cat, offsets)
     opts = (CountOptions * K)()
     regs = (CountRegion * K)()
-    rec_offsets = (ctypes.c_longlong * (K + 1))(*[int(o) for o in offsets])
     out_offsets = (ctypes.c_longlong * K)()
     total_bins = 0
     for k, (region, options) in enumerate(zip(regions, options_list)):
@@ -585,11 +593,10 @@ def count_alignment_intervals_batch_device(records_by_file: Sequence[dict], chro
     index = {contig: c for c, contig in enumerate(contigs)}
     ids_h = np.fromiter((index[c] for c in chrom_list), dtype=np.int32, count=P)
     tracks = [records_by_file[f][contig] for f in range(F) for contig in contigs]
-    cat, offsets = _records_on_device(tracks, dev)
+    cat, rec_offsets, dev = _record_args(tracks, dev=dev)
     lib = _native.load()
     ids_t, starts_t, ends_t = (torch.from_numpy(a).to(dev) for a in (ids_h, starts_h, ends_h))
     out = torch.empty((P, F), dtype=torch.int32, device=dev)
-    rec_offsets = (ctypes.c_longlong * (F * C + 1))(*[int(o) for o in offsets])
     facts = (ctypes.c_int * (2 * F * C))()
     solver, stream = _native.solver_for(dev.index), _dp._stream_ptr(out)
     _native.check(lib.rocco_hip_count_alignment_intervals_batch(
@@ -744,10 +751,7 @@ def record_flag_facts_device(records_list: Sequence[AlignmentRecords], cat=None,
     if T == 0:
         return [], []
     lib = _native.load()
-    if cat is None:
-        cat, offsets = _records_on_device(records_list, _device_for(records_list))
-    dev = cat.pos.device
-    rec_offsets = (ctypes.c_longlong * (T + 1))(*[int(o) for o in offsets])
+    cat, rec_offsets, dev = _record_args(records_list, cat, offsets)
     mapped, unsorted = (ctypes.c_longlong * T)(), (ctypes.c_int * T)()
     _native.check(lib.rocco_hip_record_flag_facts(_native.solver_for(dev.index).handle, cat.pos.data_ptr(), cat.flag.data_ptr(), rec_offsets,
                                                   T, mapped, unsorted, _dp._stream_ptr(cat.pos)), "rocco_hip_record_flag_facts")
@@ -833,10 +837,7 @@ def fragment_block_centers_device(records_list: Sequence[AlignmentRecords], cont
 
     T = len(records_list)
     lib = _native.load()
-    if cat is None:
-        cat, offsets = _records_on_device(records_list, _device_for(records_list))
-    dev = cat.pos.device
-    rec_offsets = (ctypes.c_longlong * (T + 1))(*[int(o) for o in offsets])
+    cat, rec_offsets, dev = _record_args(records_list, cat, offsets)
     lengths = (ctypes.c_longlong * T)(*[int(n) for n in contig_lengths])
     chunks = [0 if int(n) < block_size else max((int(n) + rolling_chunk_size - 1) // rolling_chunk_size, 0) for n in contig_lengths]
     chunk_offsets = (ctypes.c_longlong * (T + 1))(*np.concatenate([[0], np.cumsum(chunks)]).astype(np.int64).tolist())
@@ -876,10 +877,7 @@ def strand_xcorr_blocks_device(records_list: Sequence[AlignmentRecords], block_t
                          "LDS (there is no CPU fallback)")
     T, B = len(records_list), len(block_track)
     lib = _native.load()
-    if cat is None:
-        cat, offsets = _records_on_device(records_list, _device_for(records_list))
-    dev = cat.pos.device
-    rec_offsets = (ctypes.c_longlong * (T + 1))(*[int(o) for o in offsets])
+    cat, rec_offsets, dev = _record_args(records_list, cat, offsets)
     tracks = (ctypes.c_int * B)(*[int(t) for t in block_track])
     starts = (ctypes.c_longlong * B)(*[int(s) for s in block_start])
     lags = (ctypes.c_int * T)(*[int(v) for v in min_lag])
@@ -907,11 +905,10 @@ def _paired_fragment_lengths(jobs: list, p: dict) -> None:
     if not tracks:
         return
     records = [r for _, r in tracks]
-    cat, offsets = _records_on_device(records, _device_for(records))
-    dev, T = cat.pos.device, len(tracks)
+    cat, rec_offsets, dev = _record_args(records)
+    offsets, T = list(rec_offsets), len(tracks)
     total = max(int(offsets[-1]), 1)
     tmp, out = torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, dtype=torch.int32, device=dev)
-    rec_offsets = (ctypes.c_longlong * (T + 1))(*[int(o) for o in offsets])
     floors = (ctypes.c_int * T)(*[int(j["min_insert"]) for j, _ in tracks])
     counts = (ctypes.c_longlong * T)()
     _native.check(lib.rocco_hip_template_lengths(

@@ -14,6 +14,7 @@
 #include "../../rocco_amd/csrc/search.h"
 #include "../../rocco_amd/csrc/chain.h"
 #include "../../rocco_amd/csrc/lean_tasks.h"
+#include "../../rocco_amd/csrc/record_layouts.h"
 
 using namespace rocco;
 
@@ -327,6 +328,19 @@ public:
     }
 };
 
+struct Region {
+    size_t offset, need;
+};
+
+void put_regions(std::initializer_list<Region> regions, size_t bytes, long long *offsets, long long *needs, long long *total)
+{
+    for (const Region &r : regions) {
+        *offsets++ = (long long)r.offset;
+        *needs++ = (long long)r.need;
+    }
+    *total = (long long)bytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -500,5 +514,69 @@ void hostlogic_model_chain_layout(long long B, long long n_wcap, int rounds, lon
     totals[0] = (long long)m.dev_bytes;
     totals[1] = (long long)m.up_bytes;
     totals[2] = (long long)m.follow_bytes;
+}
+
+// The scratch regions of the record launchers as the product lays them out (csrc/record_layouts.h, the structs count.hip,
+// interval_count.hip and fragment_length.hip build).  Per region, in the documented order, its offset and the bytes it has to
+// hold (elements x sizeof, worked out here; a hipcub region holds at least one byte); `total`: bytes of the buffer.
+// K tracks of `bins` bins each: [tracks][chunk_first][tile_first][maxima][tile_sums][delta]
+void hostlogic_count_layout(long long K, long long bins, long long *offsets, long long *needs, long long *total)
+{
+    const size_t k = (size_t)K, tiles = k * count_scan_tiles((size_t)bins), cells = k * count_delta_cells((size_t)bins);
+    const CountLayout m(k, tiles, cells);
+    put_regions({{m.tracks, k * sizeof(CountTrack)}, {m.chunk_first, (k + 1) * sizeof(int)}, {m.tile_first, (k + 1) * sizeof(int)},
+                 {m.maxima, k * sizeof(int)}, {m.tile_sums, tiles * sizeof(int)}, {m.delta, cells * sizeof(int)}},
+                m.bytes, offsets, needs, total);
+}
+
+// [rec_offsets][facts][cand_lo][cand_n][units][unit_first][scan]
+void hostlogic_interval_layout(long long T, long long pairs, long long scan_bytes, long long *offsets, long long *needs, long long *total)
+{
+    const size_t t = (size_t)T, p = (size_t)pairs, scan = (size_t)scan_bytes;
+    const IntervalLayout m(t, p, scan);
+    put_regions({{m.rec_offsets, (t + 1) * sizeof(long long)}, {m.facts, 2 * t * sizeof(int)}, {m.cand_lo, p * sizeof(long long)},
+                 {m.cand_n, p * sizeof(int)}, {m.units, (p + 1) * sizeof(long long)}, {m.unit_first, (p + 1) * sizeof(long long)},
+                 {m.scan, scan > 0 ? scan : 1}},
+                m.bytes, offsets, needs, total);
+}
+
+// [rec_offsets][mapped][unsorted]
+void hostlogic_flag_facts_layout(long long T, long long *offsets, long long *needs, long long *total)
+{
+    const size_t t = (size_t)T;
+    const FlagFactsLayout m(t);
+    put_regions({{m.rec_offsets, (t + 1) * sizeof(long long)}, {m.mapped, t * sizeof(unsigned long long)}, {m.unsorted, t * sizeof(int)}},
+                m.bytes, offsets, needs, total);
+}
+
+// [raw][prefix][density][index][density_sorted][index_sorted][cub]
+void hostlogic_centers_layout(long long max_chunks, long long cub_bytes, long long *offsets, long long *needs, long long *total)
+{
+    const size_t cells = ((size_t)max_chunks + 1) * sizeof(int), cub = (size_t)cub_bytes;
+    const CentersLayout m((size_t)max_chunks, cub);
+    put_regions({{m.raw, cells}, {m.prefix, cells}, {m.density, cells}, {m.index, cells}, {m.density_sorted, cells},
+                 {m.index_sorted, cells}, {m.cub, cub > 0 ? cub : 1}},
+                m.bytes, offsets, needs, total);
+}
+
+// [rec_offsets][min_lag][block_track][block_start][best_lag][fwd_sum][rev_sum][best_score]
+void hostlogic_xcorr_layout(long long T, long long n_blocks, long long *offsets, long long *needs, long long *total)
+{
+    const size_t t = (size_t)T, b = (size_t)n_blocks;
+    const XcorrLayout m(t, b);
+    put_regions({{m.rec_offsets, (t + 1) * sizeof(long long)}, {m.min_lag, t * sizeof(int)}, {m.block_track, b * sizeof(int)},
+                 {m.block_start, b * sizeof(long long)}, {m.best_lag, b * sizeof(int)}, {m.fwd_sum, b * sizeof(int)},
+                 {m.rev_sum, b * sizeof(int)}, {m.best_score, b * sizeof(double)}},
+                m.bytes, offsets, needs, total);
+}
+
+// [rec_offsets][min_insert][counts][select]
+void hostlogic_template_layout(long long T, long long select_bytes, long long *offsets, long long *needs, long long *total)
+{
+    const size_t t = (size_t)T, select = (size_t)select_bytes;
+    const TemplateLayout m(t, select);
+    put_regions({{m.rec_offsets, (t + 1) * sizeof(long long)}, {m.min_insert, t * sizeof(int)}, {m.counts, t * sizeof(int)},
+                 {m.select, select > 0 ? select : 1}},
+                m.bytes, offsets, needs, total);
 }
 }

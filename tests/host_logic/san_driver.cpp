@@ -20,6 +20,12 @@ int hostlogic_solve_fixed(const double *scores, const double *costs, double gamm
                           double *value_out, long long *count_out, long long *out_i);
 void hostlogic_model_chain_layout(long long B, long long n_wcap, int rounds, long long cap_pairs, int *limits, long long *dev_offsets,
                                   long long *dev_needs, long long *follow_offsets, long long *follow_needs, long long *totals);
+void hostlogic_count_layout(long long K, long long bins, long long *offsets, long long *needs, long long *total);
+void hostlogic_interval_layout(long long T, long long pairs, long long scan_bytes, long long *offsets, long long *needs, long long *total);
+void hostlogic_flag_facts_layout(long long T, long long *offsets, long long *needs, long long *total);
+void hostlogic_centers_layout(long long max_chunks, long long cub_bytes, long long *offsets, long long *needs, long long *total);
+void hostlogic_xcorr_layout(long long T, long long n_blocks, long long *offsets, long long *needs, long long *total);
+void hostlogic_template_layout(long long T, long long select_bytes, long long *offsets, long long *needs, long long *total);
 }
 
 // the buffers of a chain of rounding-model rounds: every region starts where the one before ends, on a multiple of 256, and
@@ -37,6 +43,61 @@ static int layout_faults(long long B, long long n_wcap, int rounds, long long ca
         bad += (off[k] % 256 != 0) + (off[k] != begin_want) + (end - off[k] < need[k]);
     }
     return bad + (totals[1] != off[3]);
+}
+
+// the same rule for the n regions of a record launcher's scratch (csrc/record_layouts.h)
+static int region_faults(const long long *off, const long long *need, int n, long long total)
+{
+    int bad = 0;
+    long long at = 0;
+    for (int k = 0; k < n; ++k) {
+        bad += (off[k] % 256 != 0) + (off[k] != at);
+        at += (need[k] + 255) / 256 * 256;
+    }
+    return bad + (at != total);
+}
+
+// the shapes of tests/test_host_logic.py::test_record_launcher_scratch_layouts
+static int record_layout_faults(int *walked)
+{
+    const long long tracks[] = {1, 31, 32, 33, 64, 65}, blocks[] = {1, 32, 33, 64, 65}, pairs[] = {1, 31, 32, 63, 64, 65};
+    const long long temps[] = {0, 1, 255, 256, 257}, bins[] = {1, 3, 4, 5, 2047, 2048, 2049}, chunks[] = {1, 63, 64};
+    long long off[8], need[8], total = 0;
+    int bad = 0, n = 0;
+    const auto tally = [&](int regions) {
+        bad += region_faults(off, need, regions, total);
+        ++n;
+    };
+    for (long long K = 1; K <= 3; ++K) {
+        for (long long b : bins) {
+            hostlogic_count_layout(K, b, off, need, &total);
+            tally(6);
+        }
+    }
+    for (long long T : tracks) {
+        hostlogic_flag_facts_layout(T, off, need, &total);
+        tally(3);
+        for (long long temp : temps) {
+            hostlogic_template_layout(T, temp, off, need, &total);
+            tally(4);
+            for (long long p : pairs) {
+                hostlogic_interval_layout(T, p, temp, off, need, &total);
+                tally(7);
+            }
+        }
+        for (long long b : blocks) {
+            hostlogic_xcorr_layout(T, b, off, need, &total);
+            tally(8);
+        }
+    }
+    for (long long c : chunks) {
+        for (long long temp : temps) {
+            hostlogic_centers_layout(c, temp, off, need, &total);
+            tally(7);
+        }
+    }
+    *walked = n;
+    return bad;
 }
 
 static uint64_t state = 0x9E3779B97F4A7C15ULL;
@@ -141,5 +202,8 @@ int main(int argc, char **argv)
     hostlogic_model_chain_layout(1, 0, 1, 0, limits, off, need, off + 12, need + 12, totals);
     const int layout_bad = layout_faults(1, 0, 1, 0) + layout_faults(1, 1, 3, 2048) + layout_faults(limits[0], limits[0], limits[2], 32768);
     std::printf("3 layouts, %d faults\n", layout_bad);
-    return (bad == 0 && layout_bad == 0) ? 0 : 1;
+    int walked = 0;
+    const int record_bad = record_layout_faults(&walked);
+    std::printf("%d record layouts, %d faults\n", walked, record_bad);
+    return (bad == 0 && layout_bad == 0 && record_bad == 0) ? 0 : 1;
 }

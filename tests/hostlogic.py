@@ -95,3 +95,24 @@ def model_chain_layout(B, n_wcap, rounds, cap_pairs):
         "device_bytes": totals[0], "upload_bytes": totals[1], "follow_bytes": totals[2],
         "limits": dict(zip(["chain_max_problems", "model_chain_max_problems", "model_chain_max_rounds", "lean_max_points"], limits)),
     }
+
+
+RECORD_LAYOUT_REGIONS = {
+    "count": ["tracks", "chunk_first", "tile_first", "maxima", "tile_sums", "delta"],
+    "interval": ["rec_offsets", "facts", "cand_lo", "cand_n", "units", "unit_first", "scan"],
+    "flag_facts": ["rec_offsets", "mapped", "unsorted"],
+    "centers": ["raw", "prefix", "density", "index", "density_sorted", "index_sorted", "cub"],
+    "xcorr": ["rec_offsets", "min_lag", "block_track", "block_start", "best_lag", "fwd_sum", "rev_sum", "best_score"],
+    "template": ["rec_offsets", "min_insert", "counts", "select"],
+}
+
+
+def record_layout(kind, *shape):
+    """The scratch buffer of one record launcher as csrc/record_layouts.h lays it out (``kind``: a key of
+    `RECORD_LAYOUT_REGIONS`; ``shape``: the integers its layout function takes, for "count" the tracks and the bins of each):
+    a list of (region, offset, bytes the region must hold) in the documented order, and the total."""
+    names = RECORD_LAYOUT_REGIONS[kind]
+    off, need = (ctypes.c_longlong * len(names))(), (ctypes.c_longlong * len(names))()
+    total = ctypes.c_longlong()
+    getattr(lib(), f"hostlogic_{kind}_layout")(*[ctypes.c_longlong(int(v)) for v in shape], off, need, ctypes.byref(total))
+    return list(zip(names, off, need)), total.value

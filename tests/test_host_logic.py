@@ -277,6 +277,49 @@ def test_model_chain_buffer_layouts():
     assert middle["follow_bytes"] == 5376
 
 
+def test_record_launcher_scratch_layouts():
+    """The scratch regions of the six record launchers (csrc/record_layouts.h: the structs count.hip, interval_count.hip and
+    fragment_length.hip size their scratch with and take their pointers from): aligned, in order, without overlap, ending at
+    the total, and every offset and total what the launchers computed before they shared `Layout` -- the sums of 256-rounded
+    sizes their *_scratch_bytes and their pointer arithmetic spelt out, written out again here.  Shapes: around every size at
+    which a rounding step changes ((T + 1) * 8 at T = 31 / 32, T * 4 at 64 / 65, pairs + 1 at 31 / 32 and 63 / 64, the 120
+    bytes of a CountTrack between K = 2 and 3, the + 1 cell and the round-to-4 of a difference array, a scan tile of 2048
+    bins, max_chunks + 1 cells at 63 / 64, hipcub temporary sizes around 0 and 256)."""
+    up = lambda x: (x + 255) // 256 * 256
+    tracks, blocks, pair_counts, temps = (1, 31, 32, 33, 64, 65), (1, 32, 33, 64, 65), (1, 31, 32, 63, 64, 65), (0, 1, 255, 256, 257)
+
+    def check(kind, shape, sizes):
+        regions, total = hl.record_layout(kind, *shape)
+        _check_layout_regions(regions, total, (kind, shape))
+        want, at = [], 0
+        for size in sizes:
+            want.append(at)
+            at += up(size)
+        assert [off for _name, off, _need in regions] == want and total == at, (kind, shape, regions, total, want, at)
+
+    for K in (1, 2, 3):
+        for bins in (1, 3, 4, 5, 2047, 2048, 2049):
+            tiles, cells = K * ((bins + 2047) // 2048), K * ((bins + 1 + 3) // 4 * 4)
+            check("count", (K, bins), [K * 120, (K + 1) * 4, (K + 1) * 4, K * 4, tiles * 4, cells * 4])
+    for T in tracks:
+        check("flag_facts", (T,), [(T + 1) * 8, T * 8, T * 4])
+        for temp in temps:
+            check("template", (T, temp), [(T + 1) * 8, T * 4, T * 4, max(temp, 1)])
+            for pairs in pair_counts:
+                check("interval", (T, pairs, temp), [(T + 1) * 8, 2 * T * 4, pairs * 8, pairs * 4, (pairs + 1) * 8, (pairs + 1) * 8, max(temp, 1)])
+        for n in blocks:
+            check("xcorr", (T, n), [(T + 1) * 8, T * 4, n * 4, n * 8, n * 4, n * 4, n * 4, n * 8])
+    for max_chunks in (1, 63, 64):
+        for temp in temps:
+            check("centers", (max_chunks, temp), 6 * [(max_chunks + 1) * 4] + [max(temp, 1)])
+    # K = 3 tracks of 2049 bins by hand: 360 bytes of tracks -> 512, 16 and 16 -> 256 each, maxima 12 -> 256, 6 tiles -> 256,
+    # 3 * 2052 cells = 24624 bytes -> 24832: the buffer ends with the difference arrays, behind the maxima and the tile sums
+    regions, total = hl.record_layout("count", 3, 2049)
+    assert [(name, off) for name, off, _need in regions] == [
+        ("tracks", 0), ("chunk_first", 512), ("tile_first", 768), ("maxima", 1024), ("tile_sums", 1280), ("delta", 1536)]
+    assert total == 1536 + 24832
+
+
 # ---- the envelope of the fast path's gates (inputs: tests/envelope_cases.py; the same rungs run on the GPU in
 # tests/test_gpu_calibration_envelope.py, so a failure there can be placed: search.cpp here, the device side there) ----
 
