@@ -785,6 +785,69 @@ int rocco_hip_template_lengths(rocco_hip_solver *solver, const int32_t *isize_de
                                void *stream);
 void rocco_hip_fragment_length_shape(int *shape_out);
 
+/* ---- the inflated bytes of a BAM file -> record offsets -> record arrays (note (29)) ------
+ * What the reference's counter has htslib do per record: bam_read1 (the framing of a record and its consistency
+ * checks), bam_endpos and bam_cigar2qlen.  The BGZF blocks are inflated on the host (rocco_amd/bam.py); bytes_dev holds
+ * the inflated stream of a whole file or of a slab of it.  Every load of every kernel is bounded by n_bytes: a corrupt
+ * length yields a report, never an access outside the buffer.  Each call synchronises once, at its end.
+ *
+ * rocco_hip_bam_walk_records: the offsets of the records of bytes_dev[0, n_bytes) in stream order, the first at entry0
+ *   (0 <= entry0 <= n_bytes).  The stream is cut into segments of segment_bytes (S, a power of two in [64, 2^30]; fewer
+ *   than 2^31 - 1 segments).  The guess of segment i is the lowest offset o in [iS, (i + 1)S) with o + 36 <= n_bytes from
+ *   which ROCCO_BAM_GUESS_DEPTH records in a row are plausible, or none; a record at p is plausible when block_size >= 32,
+ *   refID and next_refID lie in [-1, n_ref), l_read_name >= 1, l_seq >= 0 and 4 n_cigar_op + l_read_name +
+ *   ceil(l_seq / 2) + l_seq <= block_size - 32; a chain that runs off the stream's end behind its first record is
+ *   plausible where it ends less than ROCCO_BAM_RUNOFF_BYTES past n_bytes (a slab is cut at a BGZF block boundary).  guess_mode 0 makes every guess its segment's first byte (for tests: the repair then does all the work);
+ *   guess_mode 1 is the above.  The segment of entry0 always enters at entry0, those before it have none.  All segments are
+ *   walked from their guesses in parallel (to the first offset >= (i + 1)S, their exit); then the true chain is followed
+ *   from entry0: a guess equal to the exit of the last confirmed segment is confirmed, any other is a wrong guess and its
+ *   segment is walked again from the true entry; segments the chain jumps over are overruled to none.  Only confirmed
+ *   walks contribute, so the result is the sequential walk's whatever was guessed.  A walk stops at a block_size below 32
+ *   (ROCCO_BAM_ERR_BLOCK_SIZE) or where the block_size word or the record it announces ends past n_bytes
+ *   (ROCCO_BAM_ERR_TRUNCATED: the place to cut a slab).
+ *   offsets_out_dev: int64, room for `capacity` offsets (n_bytes / 36 + 1 always suffices; ROCCO_HIP_EINVAL, with the
+ *   report filled in, where it does not).  segment_entry_out_dev: optional, int64 per segment, the confirmed entry or -1.
+ *   report_out_host, ROCCO_BAM_WALK_REPORT int64: [0] records, [1] the offset behind the last complete record, [2]
+ *   segments, [3] wrong guesses, [4] segments walked again, [5] why the chain stopped (0: at n_bytes exactly), [6] where
+ *   (-1: nowhere).
+ * rocco_hip_bam_record_fields: per record r at offsets_dev[r]: tid (refID), pos, end = pos + rlen (rlen: the M, D, N, =, X
+ *   lengths of the CIGAR; 0 for a record with flag 4; 0 becomes 1: bam_endpos), isize (tlen), flag, mapq, mate_same
+ *   (next_refID == refID) and qlen (l_seq, or the M, I, S, =, X lengths where l_seq <= 0 and n_cigar_op > 0:
+ *   bam_cigar2qlen as rocco/native/ccounts_backend.c:812-816 uses it).  Checks: the size inequality above against the
+ *   true block_size (ROCCO_BAM_ERR_SIZES), l_read_name >= 1 (_READ_NAME), refID and next_refID in [-1, n_ref) (_REF_ID),
+ *   the CIGAR's query length against l_seq for a mapped record with a CIGAR and l_seq > 0 (_CIGAR_SEQ), pos >= 0 where
+ *   refID >= 0 (_POSITION), end < 2^31 (_END), refID ascending with -1 last (_ORDER), an offset that frames no record
+ *   inside the stream (_OFFSET), and a first CIGAR operation that soft-clips exactly l_seq bases on a placed record
+ *   (_CG_TAG: the real CIGAR may sit in a CG tag, which is not decoded).  report_out_host: [0] the code of the first
+ *   error in record order (the lowest code within a record; 0: none), [1] its record (-1).  contig_first_out_host,
+ *   n_ref + 2 int64: [k] the first record of contig k or later for k = 0 .. n_ref (records without a contig count as
+ *   n_ref), [n_ref + 1] = n; meaningful when there is no error.
+ * rocco_hip_bam_shape: shape_out[0..2] = ROCCO_BAM_GUESS_DEPTH, ROCCO_BAM_SEGMENT_BYTES (the default S), ROCCO_BAM_THREADS. */
+#define ROCCO_BAM_GUESS_DEPTH 3
+#define ROCCO_BAM_SEGMENT_BYTES 16384
+#define ROCCO_BAM_RUNOFF_BYTES 65536
+#define ROCCO_BAM_THREADS 256
+#define ROCCO_BAM_WALK_REPORT 8
+#define ROCCO_BAM_ERR_BLOCK_SIZE 1
+#define ROCCO_BAM_ERR_TRUNCATED 2
+#define ROCCO_BAM_ERR_SIZES 3
+#define ROCCO_BAM_ERR_READ_NAME 4
+#define ROCCO_BAM_ERR_REF_ID 5
+#define ROCCO_BAM_ERR_CIGAR_SEQ 6
+#define ROCCO_BAM_ERR_POSITION 7
+#define ROCCO_BAM_ERR_END 8
+#define ROCCO_BAM_ERR_CG_TAG 9
+#define ROCCO_BAM_ERR_ORDER 10
+#define ROCCO_BAM_ERR_OFFSET 11
+int rocco_hip_bam_walk_records(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, int64_t entry0, int n_ref,
+                               size_t segment_bytes, int guess_mode, int64_t *offsets_out_dev, size_t capacity,
+                               int64_t *segment_entry_out_dev, int64_t *report_out_host, void *stream);
+int rocco_hip_bam_record_fields(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, const int64_t *offsets_dev, size_t n,
+                                int n_ref, int32_t *tid_out_dev, int32_t *pos_out_dev, int32_t *end_out_dev, int32_t *isize_out_dev,
+                                uint16_t *flag_out_dev, uint8_t *mapq_out_dev, uint8_t *mate_same_out_dev, int32_t *qlen_out_dev,
+                                int64_t *contig_first_out_host, int64_t *report_out_host, void *stream);
+void rocco_hip_bam_shape(int *shape_out);
+
 /* ---- synthetic signal matrices (benchmark / test support, device-resident) -------------------
  * Fills a row-major [K][n] matrix with the counter-based synthetic tracks described in
  * DESIGN.md section 7 (5-decimal background + planted peaks with per-sample dropout); the same

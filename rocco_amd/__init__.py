@@ -51,6 +51,13 @@ from .readtracks import (  # noqa: F401  (rocco/native/ccounts_backend.c:598-152
     bam_count_metadata_from_records_batch,
     is_alignment_paired_end_from_records,
 )
+from .bam import (  # noqa: F401  (htslib's BGZF reader, bam_read1, bam_endpos, bam_cigar2qlen; rocco/readtracks.py:242-518)
+    clear_alignment_cache,
+    get_bam_chrom_reads,
+    inflate_bgzf,
+    parse_bam_header,
+    read_alignment_file,
+)
 from .rocco import (  # noqa: F401
     chrom_solution_to_bed,
     combine_chrom_results,

@@ -301,6 +301,15 @@ PROTOTYPES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_size_t, c_int_p, ctypes.c_int, ctypes.c_int,
       ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_void_p]),
     ("rocco_hip_fragment_length_shape", None, [c_int_p]),
+    # row f8 (csrc/bam_records.hip): htslib's bam_read1, bam_endpos and bam_cigar2qlen as the reference's counter uses them
+    ("rocco_hip_bam_walk_records", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_void_p, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_bam_record_fields", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, c_ll_p,
+      ctypes.c_void_p]),
+    ("rocco_hip_bam_shape", None, [c_int_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t,
       ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]),

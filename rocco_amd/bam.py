@@ -1,0 +1,481 @@
+"""Read BAM files (note (29)): BGZF blocks are inflated on the host with Python's zlib, everything
+after the inflate runs on the device (csrc/bam_records.hip): the record walk over the inflated bytes, the seven values per
+record that rows f5-f7 consume, and the split by contig.  `get_bam_chrom_reads` and `_get_bam_count_metadata` have the
+reference's signatures (rocco/readtracks.py:389-407, 242-252) and are composed from `read_alignment_file`,
+`rocco_amd.readtracks.bam_count_metadata_from_records` and `bam_chrom_reads_from_records`; an integrator binds the first
+behind the stub: ``rocco_amd.readtracks.get_bam_chrom_reads = rocco_amd.bam.get_bam_chrom_reads``.
+
+Not built: DEFLATE on the device, CRAM and SAM, the ``.bai`` index (the whole file is decoded; the index iterator's overlap
+test is already applied by the counting kernels), CIGARs kept in a ``CG`` tag (reported as an error).  There is no CPU
+fallback for the record walk."""
+from __future__ import annotations
+
+import collections
+import ctypes
+import multiprocessing
+import os
+import struct
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+from typing import Iterator, List, Optional, Tuple
+
+import numpy as np
+
+from . import _native
+from . import dp as _dp
+from . import readtracks as _rt
+from .readtracks import AlignmentFileRecords, AlignmentRecords
+
+logger = _rt.logger  # (the reference's reader logs where its readtracks module does)
+
+DEFAULT_SLAB_BYTES = 256 << 20
+GUESS_DEPTH = 3                # ROCCO_BAM_GUESS_DEPTH of include/rocco_hip.h
+DEFAULT_SEGMENT_BYTES = 16384  # ROCCO_BAM_SEGMENT_BYTES
+_BGZF_HEADER = 12              # ID1 ID2 CM FLG MTIME(4) XFL OS XLEN(2)
+
+ERR_BLOCK_SIZE, ERR_TRUNCATED, ERR_SIZES, ERR_READ_NAME, ERR_REF_ID, ERR_CIGAR_SEQ, ERR_POSITION, ERR_END, ERR_CG_TAG, ERR_ORDER, \
+    ERR_OFFSET = range(1, 12)
+_ERROR_TEXT = {
+    ERR_BLOCK_SIZE: "its block_size is below 32",
+    ERR_TRUNCATED: "the stream ends inside it",
+    ERR_SIZES: "its name, CIGAR, sequence and qualities do not fit its block_size",
+    ERR_READ_NAME: "its l_read_name is 0",
+    ERR_REF_ID: "its refID or next_refID is outside the header's contigs",
+    ERR_CIGAR_SEQ: "the query length of its CIGAR differs from l_seq",
+    ERR_POSITION: "it lies on a contig at a negative position",
+    ERR_END: "it ends at or beyond 2**31",
+    ERR_CG_TAG: "its first CIGAR operation soft-clips the whole sequence: the real CIGAR may be kept in a CG tag, which is not decoded",
+    ERR_ORDER: "its contig comes before the previous record's: the file is not coordinate-sorted (contigs in header order, "
+               "records without a contig last)",
+    ERR_OFFSET: "no record is framed there",
+}
+
+
+# --------------------------------------------------------------------------------------------
+# host: BGZF
+# --------------------------------------------------------------------------------------------
+
+def _default_threads() -> int:
+    try:
+        return max(1, min(16, len(os.sched_getaffinity(0))))
+    except AttributeError:  # (no affinity interface on this platform)
+        return 1
+
+
+def _source_bytes(source):
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        return memoryview(source), "<bytes>"
+    with open(os.fspath(source), "rb") as handle:
+        return memoryview(handle.read()), os.fspath(source)
+
+
+def _bgzf_blocks(raw: memoryview, name: str) -> List[Tuple[int, int, int, int, int]]:
+    """(file offset, first byte of the deflate data, one past its last, CRC32, ISIZE) per block, from the block headers."""
+    blocks, at, total = [], 0, len(raw)
+    while at < total:
+        index = len(blocks)
+        where = f"{name}: BGZF block {index} at file offset {at}"
+        if at + _BGZF_HEADER > total:
+            raise ValueError(f"{where}: the file ends inside the block header")
+        id1, id2, cm, flg = raw[at], raw[at + 1], raw[at + 2], raw[at + 3]
+        if id1 != 0x1F or id2 != 0x8B or cm != 8:
+            raise ValueError(f"{where}: bad header (no gzip magic)")
+        if not flg & 4:
+            raise ValueError(f"{where}: bad header (FLG.FEXTRA is not set)")
+        (xlen,) = struct.unpack_from("<H", raw, at + 10)
+        extra, extra_end = at + _BGZF_HEADER, at + _BGZF_HEADER + xlen
+        if extra_end > total:
+            raise ValueError(f"{where}: the file ends inside the block header")
+        bsize = None
+        while extra + 4 <= extra_end:
+            si1, si2, slen = raw[extra], raw[extra + 1], struct.unpack_from("<H", raw, extra + 2)[0]
+            if extra + 4 + slen > extra_end:
+                raise ValueError(f"{where}: bad header (an extra subfield overruns XLEN)")
+            if si1 == 66 and si2 == 67 and slen == 2:
+                bsize = struct.unpack_from("<H", raw, extra + 4)[0] + 1
+            extra += 4 + slen
+        if bsize is None:
+            raise ValueError(f"{where}: bad header (no BC subfield)")
+        if bsize < _BGZF_HEADER + xlen + 8:
+            raise ValueError(f"{where}: bad header (BSIZE is smaller than the header and trailer)")
+        if at + bsize > total:
+            raise ValueError(f"{where}: the file ends inside the block ({total - at} of {bsize} bytes)")
+        crc, isize = struct.unpack_from("<II", raw, at + bsize - 8)
+        blocks.append((at, extra_end, at + bsize - 8, crc, isize))
+        at += bsize
+    return blocks
+
+
+def _host_buffer(n: int) -> np.ndarray:
+    """n bytes of host memory as a uint8 array: pinned where a device is present (uploads from it run asynchronously)."""
+    import torch
+
+    t = torch.empty(max(int(n), 1), dtype=torch.uint8)
+    if torch.cuda.is_available():
+        try:
+            t = t.pin_memory()
+        except RuntimeError:  # (no pinned memory left: ordinary memory uploads as well, synchronously)
+            pass
+    return t.numpy()[: int(n)]
+
+
+def _inflate_group(raw: memoryview, blocks, first_index: int, name: str, pool) -> np.ndarray:
+    starts = np.zeros(len(blocks) + 1, dtype=np.int64)
+    np.cumsum([b[4] for b in blocks], out=starts[1:])
+    out = _host_buffer(int(starts[-1]))
+
+    def one(k):
+        at, lo, hi, crc, isize = blocks[k]
+        where = f"{name}: BGZF block {first_index + k} at file offset {at}"
+        try:
+            data = zlib.decompress(raw[lo:hi], wbits=-15)
+        except zlib.error as exc:
+            raise ValueError(f"{where}: the deflate stream does not inflate ({exc})") from None
+        if len(data) != isize:
+            raise ValueError(f"{where}: length mismatch (ISIZE says {isize}, the data inflates to {len(data)})")
+        if zlib.crc32(data) != crc:
+            raise ValueError(f"{where}: CRC32 mismatch")
+        out[starts[k]: starts[k + 1]] = np.frombuffer(data, dtype=np.uint8)
+
+    for _ in pool.map(one, range(len(blocks))):
+        pass
+    return out
+
+
+def inflate_bgzf(source, threads: Optional[int] = None, slab_bytes: Optional[int] = None):
+    """The inflated bytes of a BGZF file (``source``: a path or bytes) as a uint8 array in pinned host memory: the block
+    headers are walked (gzip magic, FLG.FEXTRA, the ``BC`` subfield among possibly several, ``BSIZE``; ``CRC32`` and
+    ``ISIZE`` from the trailer), the blocks are inflated with ``zlib.decompress(..., wbits=-15)`` on a pool of ``threads``
+    threads (zlib releases the GIL; default ``min(16, len(os.sched_getaffinity(0)))``) and placed at the prefix sum of their
+    ``ISIZE``; every block's length and CRC32 are checked.  ValueError naming the block and its file offset for a bad header,
+    a mismatch or a file that ends inside a block; a missing end-of-file marker block is accepted.
+
+    With ``slab_bytes``: a generator of such arrays, each of about that many inflated bytes (at least one block), cut at
+    BGZF block boundaries."""
+    threads = _default_threads() if threads is None else max(1, int(threads))
+    if slab_bytes is None:
+        slabs = list(_inflate_slabs(source, threads, None))
+        return slabs[0] if slabs else _host_buffer(0)
+    if int(slab_bytes) < 1:
+        raise ValueError("inflate_bgzf: slab_bytes must be positive")
+    return _inflate_slabs(source, threads, int(slab_bytes))
+
+
+def _inflate_slabs(source, threads: int, slab_bytes: Optional[int]) -> Iterator[np.ndarray]:
+    raw, name = _source_bytes(source)
+    blocks = _bgzf_blocks(raw, name)
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        first = 0
+        while first < len(blocks):
+            last, size = first, 0
+            while last < len(blocks) and (slab_bytes is None or size < slab_bytes or last == first):
+                size += blocks[last][4]
+                last += 1
+            while last < len(blocks) and blocks[last][4] == 0:  # (the end-of-file marker and its like go with the slab before)
+                last += 1
+            yield _inflate_group(raw, blocks[first:last], first, name, pool)
+            first = last
+
+
+# --------------------------------------------------------------------------------------------
+# host: the BAM header
+# --------------------------------------------------------------------------------------------
+
+class _HeaderCutShort(ValueError):
+    """The bytes end inside the header (more of the stream may follow)."""
+
+
+def parse_bam_header(inflated) -> Tuple[str, List[Tuple[str, int]], int]:
+    """(text, [(name, length)] in header order, the byte offset of the first record) from the head of an inflated BAM stream:
+    the magic ``BAM\\1``, ``l_text``, the text, ``n_ref`` and per contig ``l_name``, the NUL-terminated name and ``l_ref``.
+    ValueError for anything else."""
+    data = memoryview(np.ascontiguousarray(np.frombuffer(inflated, dtype=np.uint8) if not isinstance(inflated, np.ndarray) else inflated))
+    total = len(data)
+
+    def need(at, n, what):
+        if at + n > total:
+            raise _HeaderCutShort(f"BAM header: the stream ends inside {what} (at byte {at} of {total})")
+
+    need(0, 4, "the magic")
+    if bytes(data[0:4]) != b"BAM\x01":
+        raise ValueError("BAM header: the magic is not `BAM\\1` (not a BAM file, or not inflated)")
+    need(4, 4, "l_text")
+    (l_text,) = struct.unpack_from("<i", data, 4)
+    if l_text < 0:
+        raise ValueError(f"BAM header: l_text is negative ({l_text})")
+    need(8, l_text, "the text")
+    text = bytes(data[8: 8 + l_text]).split(b"\0", 1)[0].decode("utf-8", "replace")
+    at = 8 + l_text
+    need(at, 4, "n_ref")
+    (n_ref,) = struct.unpack_from("<i", data, at)
+    if n_ref < 0:
+        raise ValueError(f"BAM header: n_ref is negative ({n_ref})")
+    at += 4
+    contigs = []
+    for k in range(n_ref):
+        need(at, 4, f"l_name of contig {k}")
+        (l_name,) = struct.unpack_from("<i", data, at)
+        if l_name < 1:
+            raise ValueError(f"BAM header: l_name of contig {k} is {l_name}")
+        need(at + 4, l_name + 4, f"contig {k}")
+        name = bytes(data[at + 4: at + 4 + l_name])
+        if name[-1:] != b"\0":
+            raise ValueError(f"BAM header: the name of contig {k} is not NUL-terminated")
+        (l_ref,) = struct.unpack_from("<i", data, at + 4 + l_name)
+        if l_ref < 0:
+            raise ValueError(f"BAM header: the length of contig {k} is negative ({l_ref})")
+        contigs.append((name[:-1].decode("utf-8", "replace"), int(l_ref)))
+        at += 8 + l_name
+    return text, contigs, at
+
+
+# --------------------------------------------------------------------------------------------
+# device: the record walk and the record fields (csrc/bam_records.hip)
+# --------------------------------------------------------------------------------------------
+
+def bam_shape() -> dict:
+    """`rocco_hip_bam_shape`: the depth of a guess, the default segment size, the threads of a workgroup."""
+    shape = (ctypes.c_int * 3)()
+    _native.load().rocco_hip_bam_shape(shape)
+    return {"guess_depth": int(shape[0]), "segment_bytes": int(shape[1]), "threads": int(shape[2])}
+
+
+def walk_records_device(bytes_t, entry0: int, n_ref: int, segment_bytes: Optional[int] = None, guess_mode: int = 1,
+                        want_segment_entries: bool = False):
+    """`rocco_hip_bam_walk_records` over a uint8 CUDA tensor: (int64 CUDA tensor of the record offsets in stream order, report).
+    The report: ``records``, ``end_offset`` (behind the last complete record), ``segments``, ``wrong_guesses``,
+    ``repair_rounds`` (segments walked again), ``error`` (0, ERR_BLOCK_SIZE or ERR_TRUNCATED) and ``error_offset``; with
+    ``want_segment_entries`` also ``segment_entries``, the confirmed entry of every segment or -1."""
+    import torch
+
+    lib = _native.load()
+    if not _dp._is_tensor(bytes_t) or bytes_t.dtype != torch.uint8 or bytes_t.dim() != 1 or not bytes_t.is_cuda:
+        raise TypeError("walk_records_device: a one-dimensional uint8 CUDA tensor is required")
+    bytes_t = bytes_t.contiguous()
+    n_bytes = int(bytes_t.shape[0])
+    S = DEFAULT_SEGMENT_BYTES if segment_bytes is None else int(segment_bytes)
+    capacity = n_bytes // 36 + 1
+    offsets = torch.empty(capacity, dtype=torch.int64, device=bytes_t.device)
+    segments = max((n_bytes + S - 1) // S, 1) if S > 0 else 1
+    entries = torch.empty(segments, dtype=torch.int64, device=bytes_t.device) if want_segment_entries else None
+    back = (ctypes.c_longlong * 8)()
+    _native.check(lib.rocco_hip_bam_walk_records(
+        _native.solver_for(bytes_t.device.index).handle, bytes_t.data_ptr(), n_bytes, int(entry0), int(n_ref), S, int(guess_mode),
+        offsets.data_ptr(), capacity, entries.data_ptr() if entries is not None else None, back, _dp._stream_ptr(bytes_t)),
+        "rocco_hip_bam_walk_records")
+    report = {"records": int(back[0]), "end_offset": int(back[1]), "segments": int(back[2]), "wrong_guesses": int(back[3]),
+              "repair_rounds": int(back[4]), "error": int(back[5]), "error_offset": int(back[6])}
+    if entries is not None:
+        report["segment_entries"] = entries
+    return offsets[: report["records"]], report
+
+
+_FIELD_DTYPES = (("tid", "int32"), ("pos", "int32"), ("end", "int32"), ("isize", "int32"), ("flag", "int16"), ("mapq", "uint8"),
+                 ("mate_same", "uint8"), ("qlen", "int32"))
+
+
+def record_fields_device(bytes_t, offsets_t, n_ref: int):
+    """`rocco_hip_bam_record_fields`: ({field: CUDA tensor} for tid, pos, end, isize, flag (the uint16 bit pattern as int16),
+    mapq, mate_same, qlen; the n_ref + 2 contig offsets; (error code, record index))."""
+    import torch
+
+    lib = _native.load()
+    bytes_t, offsets_t = bytes_t.contiguous(), offsets_t.contiguous()
+    n = int(offsets_t.shape[0])
+    out = {name: torch.empty(n, dtype=getattr(torch, dtype), device=bytes_t.device) for name, dtype in _FIELD_DTYPES}
+    firsts, back = (ctypes.c_longlong * (int(n_ref) + 2))(), (ctypes.c_longlong * 2)()
+    _native.check(lib.rocco_hip_bam_record_fields(
+        _native.solver_for(bytes_t.device.index).handle, bytes_t.data_ptr(), int(bytes_t.shape[0]), offsets_t.data_ptr(), n, int(n_ref),
+        *[out[name].data_ptr() for name, _ in _FIELD_DTYPES], firsts, back, _dp._stream_ptr(bytes_t)), "rocco_hip_bam_record_fields")
+    return out, [int(v) for v in firsts], (int(back[0]), int(back[1]))
+
+
+def _record_error(name: str, code: int, record: int, offset: int) -> ValueError:
+    return ValueError(f"{name}: record {record} at byte {offset} of the inflated stream: {_ERROR_TEXT.get(code, f'error {code}')}")
+
+
+def decode_records_device(bytes_t, entry0: int, n_ref: int, segment_bytes: Optional[int] = None, guess_mode: int = 1, name: str = "<bytes>",
+                          whole: bool = True, first_record: int = 0, first_byte: int = 0):
+    """Walk plus fields over one inflated stream (or slab) on the device, every error code turned into a ValueError that
+    names ``name``, the record index and the byte offset.  ``whole``: the stream must end behind a complete record (else
+    the bytes behind ``report["end_offset"]`` belong in front of the next slab).  Returns (fields, contig offsets, report)."""
+    offsets, report = walk_records_device(bytes_t, entry0, n_ref, segment_bytes, guess_mode)
+    if report["error"] == ERR_BLOCK_SIZE or (report["error"] == ERR_TRUNCATED and whole):
+        raise _record_error(name, report["error"], first_record + report["records"], first_byte + report["error_offset"])
+    fields, firsts, (code, record) = record_fields_device(bytes_t, offsets, n_ref)
+    if code:
+        raise _record_error(name, code, first_record + record, first_byte + int(offsets[record]))
+    return fields, firsts, report
+
+
+def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT_SLAB_BYTES, segment_bytes: Optional[int] = None,
+                        threads: Optional[int] = None, guess_mode: int = 1, report: Optional[dict] = None):
+    """A whole BAM file as (`AlignmentFileRecords` whose records carry ``qlen`` and are CUDA tensors, ``name`` the path; the
+    number of records without a contig).  Slab by slab: `inflate_bgzf` yields about ``slab_bytes`` inflated bytes, they are
+    uploaded, walked and decoded on the device; a slab's bytes behind its last complete record are carried in front of the
+    next slab; the per-contig arrays are views of the seven concatenated arrays.  ``names``: keep these contigs only.
+    ``report`` (a dict) receives the walk's totals."""
+    import torch
+
+    path = os.fspath(path)
+    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
+    if dev.index is None:
+        dev = torch.device(f"cuda:{_dp._device_index()}")
+    contigs, n_ref = None, 0
+    carry = np.empty(0, dtype=np.uint8)
+    parts, counts, last_key, n_records, consumed = [], None, -1, 0, 0
+    totals = {"records": 0, "segments": 0, "wrong_guesses": 0, "repair_rounds": 0, "slabs": 0}
+    pending = None
+    slabs = inflate_bgzf(path, threads=threads, slab_bytes=max(1, int(slab_bytes)))
+
+    def with_last(it):
+        previous = None
+        for item in it:
+            if previous is not None:
+                yield previous, False
+            previous = item
+        yield (previous if previous is not None else np.empty(0, dtype=np.uint8)), True
+
+    for slab, is_last in with_last(slabs):
+        data = np.concatenate([carry, slab]) if carry.size else slab
+        entry0 = 0
+        if contigs is None:
+            try:
+                _, contigs, entry0 = parse_bam_header(data)
+            except _HeaderCutShort as exc:
+                if is_last:
+                    raise ValueError(f"{path}: {exc}") from None
+                carry = data
+                continue
+            except ValueError as exc:
+                raise ValueError(f"{path}: {exc}") from None
+            n_ref = len(contigs)
+            counts = np.zeros(n_ref + 1, dtype=np.int64)
+        bytes_t = torch.from_numpy(data).to(dev, non_blocking=True)
+        fields, firsts, rep = decode_records_device(bytes_t, entry0, n_ref, segment_bytes, guess_mode, path, whole=is_last,
+                                                    first_record=n_records, first_byte=consumed)
+        slab_counts = np.diff(np.asarray(firsts, dtype=np.int64))
+        present = np.flatnonzero(slab_counts)
+        if present.size:
+            if int(present[0]) < last_key:
+                raise _record_error(path, ERR_ORDER, n_records, consumed + entry0)
+            last_key = int(present[-1])
+        counts += slab_counts
+        parts.append(fields)
+        n_records += rep["records"]
+        for key in ("records", "segments", "wrong_guesses", "repair_rounds"):
+            totals[key] += rep[key]
+        totals["slabs"] += 1
+        carry = data[rep["end_offset"]:].copy() if rep["end_offset"] < data.shape[0] else np.empty(0, dtype=np.uint8)
+        consumed += rep["end_offset"]
+        pending = bytes_t  # (the upload's source `data` lives until the next slab's synchronising call has returned)
+    del pending
+    if contigs is None:
+        raise ValueError(f"{path}: BAM header: the file is empty")
+    if report is not None:
+        report.update(totals)
+    whole = {name: (torch.cat([p[name] for p in parts]) if len(parts) > 1 else parts[0][name]) for name, _ in _FIELD_DTYPES}
+    firsts = np.concatenate([[0], np.cumsum(counts)])
+    keep = None if names is None else {str(n) for n in names}
+    records = {}
+    for k, (contig, _) in enumerate(contigs):
+        if keep is not None and contig not in keep:
+            continue
+        lo, hi = int(firsts[k]), int(firsts[k + 1])
+        r = object.__new__(AlignmentRecords)  # (the kernel checked every value: no second pass over the arrays)
+        for field in ("pos", "end", "isize", "flag", "mapq", "mate_same", "qlen"):
+            setattr(r, field, whole[field][lo:hi])
+        records[contig] = r
+    return AlignmentFileRecords(contigs, records, name=path), int(counts[n_ref])
+
+
+# --------------------------------------------------------------------------------------------
+# decoded files kept on the device (generate_chrom_matrix asks once per file and chromosome)
+# --------------------------------------------------------------------------------------------
+
+ALIGNMENT_CACHE_BYTES = 8 << 30  # the budget: 20 bytes per record; least recently used files leave first
+_ALIGNMENT_CACHE: "collections.OrderedDict" = collections.OrderedDict()
+_BAM_COUNT_METADATA_CACHE: dict = {}
+
+
+def clear_alignment_cache() -> None:
+    """Drops every decoded file (and the metadata derived from them)."""
+    _ALIGNMENT_CACHE.clear()
+    _BAM_COUNT_METADATA_CACHE.clear()
+
+
+def _file_bytes(file: AlignmentFileRecords) -> int:
+    return 20 * sum(len(r) for r in file.records.values())
+
+
+def _cached_file(bam_file: str) -> AlignmentFileRecords:
+    stat = os.stat(bam_file)
+    key = (os.path.abspath(bam_file), int(stat.st_size), int(stat.st_mtime_ns))
+    hit = _ALIGNMENT_CACHE.get(key)
+    if hit is not None:
+        _ALIGNMENT_CACHE.move_to_end(key)
+        return hit[0]
+    file, _ = read_alignment_file(bam_file)
+    file.name = bam_file
+    size = _file_bytes(file)
+    _ALIGNMENT_CACHE[key] = (file, size)
+    while len(_ALIGNMENT_CACHE) > 1 and sum(s for _, s in _ALIGNMENT_CACHE.values()) > ALIGNMENT_CACHE_BYTES:
+        _ALIGNMENT_CACHE.popitem(last=False)
+    return file
+
+
+def _resolve_num_processors(num_processors) -> int:
+    """rocco/readtracks.py:45-48 (the ``threads`` key of the metadata and of its cache key; nothing here runs on them)."""
+    if num_processors is None or int(num_processors) < 1:
+        return max(multiprocessing.cpu_count() - 1, 1)
+    return int(num_processors)
+
+
+def _clean_string(text) -> str:
+    return "" if text is None else text.lower().replace(" ", "")
+
+
+def _get_bam_count_metadata(bam_file: str, step: int, norm_method: str, effective_genome_size: float, ignore_for_norm,
+                            flag_exclude: int = 0, extend_reads: int = -1, num_processors: int = 1, scale_factor: float = 1.0) -> dict:
+    """rocco/readtracks.py:242-353 with the same signature, dict, log lines and cache key, from the file's decoded records
+    (`bam_count_metadata_from_records`)."""
+    ignore = tuple(ignore_for_norm or [])
+    threads = _resolve_num_processors(num_processors)
+    cache_key = (bam_file, int(step), _clean_string(norm_method).upper(), float(effective_genome_size if effective_genome_size is not None else -1.0),
+                 ignore, int(flag_exclude), int(extend_reads), int(threads), float(scale_factor))
+    if cache_key in _BAM_COUNT_METADATA_CACHE:
+        return _BAM_COUNT_METADATA_CACHE[cache_key]
+    metadata = dict(_rt.bam_count_metadata_from_records(_cached_file(bam_file), step, norm_method, effective_genome_size, list(ignore),
+                                                        flag_exclude=flag_exclude, extend_reads=extend_reads, scale_factor=scale_factor,
+                                                        bam_file=bam_file))
+    metadata["threads"] = int(threads)
+    _BAM_COUNT_METADATA_CACHE[cache_key] = metadata
+    return metadata
+
+
+def get_bam_chrom_reads(bam_file: str, chromosome: str, chrom_sizes_file: str, step: int, effective_genome_size: float = -1,
+                        norm_method: str = "RPGC", min_mapping_score: int = 10, flag_include=None, flag_exclude: int = 3844,
+                        extend_reads: int = -1, center_reads: bool = False, ignore_for_norm=None, scale_factor: float = 1.0,
+                        num_processors: int = -1, const_scale: float = 1.0, round_digits: int = 5, scale_by_step: bool = False):
+    """rocco/readtracks.py:389-518 with the same signature, return value, errors and warnings: the file is decoded once
+    (`read_alignment_file`, kept on the device), the rest is `bam_chrom_reads_from_records`."""
+    if not os.path.exists(bam_file):
+        raise FileNotFoundError(f"BAM file not found: {bam_file}")
+    if not os.path.exists(chrom_sizes_file):
+        raise FileNotFoundError(f"Chromosome sizes file not found: {chrom_sizes_file}")
+    sizes = _rt.get_chroms_and_sizes(chrom_sizes_file)
+    if chromosome not in sizes:
+        raise ValueError(f"Chromosome {chromosome} not found in chromosome sizes file: {chrom_sizes_file}")
+    if ignore_for_norm is None:
+        ignore_for_norm = ["chrX", "chrY", "chrM"]
+    metadata = _get_bam_count_metadata(bam_file, step=step, norm_method=norm_method, effective_genome_size=effective_genome_size,
+                                       ignore_for_norm=ignore_for_norm, flag_exclude=flag_exclude, extend_reads=extend_reads,
+                                       num_processors=num_processors, scale_factor=scale_factor)
+    file = _cached_file(bam_file)
+    if chromosome not in file.records:
+        logger.warning("Chromosome %s not found in BAM file: %s. Returning (None,None).", chromosome, bam_file)
+        return None, None
+    return _rt.bam_chrom_reads_from_records(file.records[chromosome], int(sizes[chromosome]), step, metadata,
+                                            min_mapping_score=min_mapping_score, flag_include=flag_include, flag_exclude=flag_exclude,
+                                            center_reads=center_reads, const_scale=const_scale, round_digits=round_digits,
+                                            scale_by_step=scale_by_step, bam_file=bam_file, chromosome=chromosome)

@@ -1630,6 +1630,47 @@ void rocco_hip_fragment_length_shape(int *shape_out)
     shape_out[3] = ROCCO_FRAGMENT_MAX_BLOCK_SIZE;
 }
 
+int rocco_hip_bam_walk_records(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, int64_t entry0, int n_ref,
+                               size_t segment_bytes, int guess_mode, int64_t *offsets_out_dev, size_t capacity,
+                               int64_t *segment_entry_out_dev, int64_t *report_out_host, void *stream)
+{
+    if (solver == nullptr || report_out_host == nullptr || n_ref < 0 || entry0 < 0 || (uint64_t)entry0 > (uint64_t)n_bytes ||
+        (guess_mode != 0 && guess_mode != 1) || (n_bytes > 0 && bytes_dev == nullptr) || (capacity > 0 && offsets_out_dev == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, bam_walk_scratch_bytes(n_bytes, segment_bytes)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_bam_walk_records(bytes_dev, n_bytes, entry0, n_ref, segment_bytes, guess_mode, offsets_out_dev, capacity,
+                                   segment_entry_out_dev, report_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_bam_record_fields(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, const int64_t *offsets_dev, size_t n,
+                                int n_ref, int32_t *tid_out_dev, int32_t *pos_out_dev, int32_t *end_out_dev, int32_t *isize_out_dev,
+                                uint16_t *flag_out_dev, uint8_t *mapq_out_dev, uint8_t *mate_same_out_dev, int32_t *qlen_out_dev,
+                                int64_t *contig_first_out_host, int64_t *report_out_host, void *stream)
+{
+    if (solver == nullptr || n_ref < 0 || n >= ((size_t)1 << 55) || contig_first_out_host == nullptr || report_out_host == nullptr ||
+        (n > 0 && (bytes_dev == nullptr || offsets_dev == nullptr || tid_out_dev == nullptr || pos_out_dev == nullptr ||
+                   end_out_dev == nullptr || isize_out_dev == nullptr || flag_out_dev == nullptr || mapq_out_dev == nullptr ||
+                   mate_same_out_dev == nullptr || qlen_out_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, bam_record_fields_scratch_bytes(n_ref)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_bam_record_fields(bytes_dev, n_bytes, offsets_dev, n, n_ref, tid_out_dev, pos_out_dev, end_out_dev, isize_out_dev,
+                                    flag_out_dev, mapq_out_dev, mate_same_out_dev, qlen_out_dev, contig_first_out_host, report_out_host,
+                                    solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+void rocco_hip_bam_shape(int *shape_out)
+{
+    shape_out[0] = ROCCO_BAM_GUESS_DEPTH;
+    shape_out[1] = ROCCO_BAM_SEGMENT_BYTES;
+    shape_out[2] = ROCCO_BAM_THREADS;
+}
+
 int rocco_hip_synth_matrix(rocco_hip_solver *solver, void *matrix_dev, int dtype, size_t K, size_t n,
                            size_t row_stride, uint64_t seed, void *stream)
 {

@@ -365,6 +365,18 @@ int launch_template_lengths(const int32_t *isize_dev, const uint16_t *flag_dev, 
                             int max_insert_size, int32_t *lengths_tmp_dev, int32_t *lengths_out_dev, int64_t *count_out_host,
                             void *scratch_dev, hipStream_t stream);
 
+// ---- bam_records.hip --------------------------------------------------------------------------
+// 0: the shape is out of range
+size_t bam_walk_scratch_bytes(size_t n_bytes, size_t segment_bytes);
+int launch_bam_walk_records(const uint8_t *bytes_dev, size_t n_bytes, int64_t entry0, int n_ref, size_t segment_bytes, int guess_mode,
+                            int64_t *offsets_out_dev, size_t capacity, int64_t *segment_entry_out_dev, int64_t *report_out_host,
+                            void *scratch_dev, hipStream_t stream);
+size_t bam_record_fields_scratch_bytes(int n_ref);
+int launch_bam_record_fields(const uint8_t *bytes_dev, size_t n_bytes, const int64_t *offsets_dev, size_t n, int n_ref, int32_t *tid_out_dev,
+                             int32_t *pos_out_dev, int32_t *end_out_dev, int32_t *isize_out_dev, uint16_t *flag_out_dev,
+                             uint8_t *mapq_out_dev, uint8_t *mate_same_out_dev, int32_t *qlen_out_dev, int64_t *contig_first_out_host,
+                             int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
+
 // ---- synth.hip ------------------------------------------------------------------------------
 int launch_synth(void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, uint64_t seed,
                  hipStream_t stream);

@@ -1,5 +1,5 @@
-// rocco_amd/csrc/record_layouts.h -- where the launchers of count.hip, interval_count.hip and fragment_length.hip keep
-// their regions of the solver's scratch buffer: one struct per launcher, read by its *_scratch_bytes (the total) and by
+// rocco_amd/csrc/record_layouts.h -- where the launchers of count.hip, interval_count.hip, fragment_length.hip and
+// bam_records.hip keep their regions of the solver's scratch buffer: one struct per launcher, read by its *_scratch_bytes (the total) and by
 // the launcher itself (the offsets), so the two cannot drift apart.  A hipcub region takes the bytes hipcub asked for and
 // is never empty.  Plain C++ (no HIP call): tests/host_logic/harness.cpp checks the layouts on the CPU.
 #pragma once
@@ -108,6 +108,43 @@ struct TemplateLayout {
         min_insert = lay.at(T * sizeof(int));
         counts = lay.at(T * sizeof(int));
         select = lay.at(select_bytes > 0 ? select_bytes : 1);
+        bytes = lay.bytes();
+    }
+};
+
+// segments of a stream of n_bytes (at least one: an empty stream is one empty segment)
+inline size_t bam_walk_segments(size_t n_bytes, size_t segment_bytes)
+{
+    const size_t n = (n_bytes + segment_bytes - 1) / segment_bytes;
+    return n > 0 ? n : 1;
+}
+
+// launch_bam_walk_records: per segment its entry, exit, count and the prefix sum of the counts (int64), why its walk
+// stopped (int32); the report; hipcub's scan over the counts
+struct BamWalkLayout {
+    size_t entry, exit_of, count, first, stop, report, scan, bytes;
+    BamWalkLayout(size_t n_segments, size_t scan_bytes)
+    {
+        Layout lay;
+        entry = lay.at(n_segments * sizeof(long long));
+        exit_of = lay.at(n_segments * sizeof(long long));
+        count = lay.at(n_segments * sizeof(long long));
+        first = lay.at(n_segments * sizeof(long long));
+        stop = lay.at(n_segments * sizeof(int));
+        report = lay.at(ROCCO_BAM_WALK_REPORT * sizeof(long long));
+        scan = lay.at(scan_bytes > 0 ? scan_bytes : 1);
+        bytes = lay.bytes();
+    }
+};
+
+// launch_bam_record_fields: the n_ref + 2 contig offsets and the error word
+struct BamFieldsLayout {
+    size_t contig_first, error, bytes;
+    explicit BamFieldsLayout(size_t n_ref)
+    {
+        Layout lay;
+        contig_first = lay.at((n_ref + 2) * sizeof(long long));
+        error = lay.at(sizeof(unsigned long long));
         bytes = lay.bytes();
     }
 };
