@@ -787,7 +787,7 @@ void rocco_hip_fragment_length_shape(int *shape_out);
 
 /* ---- the inflated bytes of a BAM file -> record offsets -> record arrays (note (29)) ------
  * What the reference's counter has htslib do per record: bam_read1 (the framing of a record and its consistency
- * checks), bam_endpos and bam_cigar2qlen.  The BGZF blocks are inflated on the host (rocco_amd/bam.py); bytes_dev holds
+ * checks), bam_endpos and bam_cigar2qlen.  The BGZF blocks are inflated on the host (rocco_amd/bam.py) or by rocco_hip_bgzf_inflate, further down; bytes_dev holds
  * the inflated stream of a whole file or of a slab of it.  Every load of every kernel is bounded by n_bytes: a corrupt
  * length yields a report, never an access outside the buffer.  Each call synchronises once, at its end.
  *
@@ -847,6 +847,54 @@ int rocco_hip_bam_record_fields(rocco_hip_solver *solver, const uint8_t *bytes_d
                                 uint16_t *flag_out_dev, uint8_t *mapq_out_dev, uint8_t *mate_same_out_dev, int32_t *qlen_out_dev,
                                 int64_t *contig_first_out_host, int64_t *report_out_host, void *stream);
 void rocco_hip_bam_shape(int *shape_out);
+
+/* ---- the BGZF blocks of a BAM file -> their inflated bytes (note (29)) ----------------------
+ * What the reference has htslib's BGZF reader do per block: inflate its DEFLATE stream (RFC 1951), compare the length with
+ * the trailer's ISIZE and the CRC32 of the bytes with the trailer's CRC32.  The block headers are walked on the host
+ * (rocco_amd/bam.py: _bgzf_blocks), which states every block as one row of the block table:
+ *   table_dev: int64 [n_blocks][ROCCO_BGZF_TABLE_COLUMNS], one device array, a row = { the first byte of the block's
+ *   deflate data in comp_dev, one past its last, ISIZE, CRC32, the offset of its bytes in out_dev (the prefix sum of ISIZE
+ *   where the blocks are to lie one behind the other) }.
+ *
+ * rocco_hip_bgzf_inflate: comp_dev[0, n_comp) holds the compressed bytes of a file or of a slab of it; every block is
+ *   inflated by one wavefront of ROCCO_BGZF_THREADS lanes into out_dev[offset, offset + ISIZE), then its CRC32 is taken
+ *   (per-lane table-driven CRCs of 64 contiguous chunks, combined as zlib's crc32_combine does).  The streams are accepted
+ *   and rejected exactly as zlib 1.2.11 does for a raw stream (stored, fixed and dynamic blocks, several per BGZF block,
+ *   lengths to 258, distances to 32 768, overlapping copies; block type 3, LEN != ~NLEN, HLIT > 286 or HDIST > 30, an
+ *   incomplete code-length code, a repeat past the lengths or a leading 16, no code for 256, over-subscribed sets,
+ *   incomplete sets other than one code of length 1 or no distance code at all, the use of a missing code, a distance
+ *   beyond the bytes produced and a span that ends inside the stream are rejected; bytes behind the final block are
+ *   ignored).  Every load is bounded by the row's span, every store by its ISIZE: a stream that inflates to more is
+ *   followed to its end without storing, and nothing outside [offset, offset + ISIZE) is written whatever the span holds.
+ *   A row is refused (ROCCO_BGZF_ERR_TABLE, nothing of it read or written) unless 0 <= first <= last <= n_comp,
+ *   0 <= ISIZE <= ROCCO_BGZF_MAX_ISIZE and [offset, offset + ISIZE) lies in [0, n_out).  Rows whose ranges overlap are the
+ *   caller's error.
+ *   status_out_dev: optional, int32 per block: 0, ROCCO_BGZF_ERR_STREAM | reason << 8 (reason 1 ..
+ *   ROCCO_BGZF_STREAM_REASONS: block type, stored length, too many symbols, code-length set, repeat, no end-of-block,
+ *   literal/length set, distance set, literal/length code, distance code, distance too far back, input ends), _LENGTH (the
+ *   stream is sound and inflates to another length), _CRC or _TABLE; in zlib's order: a stream error before a length
+ *   error before a CRC error.  report_out_host, ROCCO_BGZF_REPORT int64: [0] the first failing block in table order or
+ *   -1, [1] its status, [2] the bytes it inflates to (for _LENGTH).  The bytes of blocks that fail are unspecified inside
+ *   their own range.  Synchronises once, at its end.  n_blocks = 0 is a valid call.
+ * rocco_hip_bgzf_inflate_host: test support, as rocco_hip_synth_matrix is: the same rows over HOST memory (comp, table, out
+ *   and status_out are host pointers), on the calling thread, from the same source as the kernels (csrc/inflate_core.h
+ *   compiled for the host); no device is touched, solver may be NULL.
+ * rocco_hip_bgzf_shape: shape_out[0..3] = ROCCO_BGZF_THREADS, ROCCO_BGZF_TABLE_COLUMNS, ROCCO_BGZF_MAX_ISIZE,
+ *   ROCCO_BGZF_STREAM_REASONS. */
+#define ROCCO_BGZF_THREADS 64
+#define ROCCO_BGZF_TABLE_COLUMNS 5
+#define ROCCO_BGZF_MAX_ISIZE 65536
+#define ROCCO_BGZF_REPORT 4
+#define ROCCO_BGZF_STREAM_REASONS 12
+#define ROCCO_BGZF_ERR_STREAM 1
+#define ROCCO_BGZF_ERR_LENGTH 2
+#define ROCCO_BGZF_ERR_CRC 3
+#define ROCCO_BGZF_ERR_TABLE 4
+int rocco_hip_bgzf_inflate(rocco_hip_solver *solver, const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks,
+                           uint8_t *out_dev, size_t n_out, int32_t *status_out_dev, int64_t *report_out_host, void *stream);
+int rocco_hip_bgzf_inflate_host(rocco_hip_solver *solver, const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks,
+                                uint8_t *out, size_t n_out, int32_t *status_out, int64_t *report_out);
+void rocco_hip_bgzf_shape(int *shape_out);
 
 /* ---- synthetic signal matrices (benchmark / test support, device-resident) -------------------
  * Fills a row-major [K][n] matrix with the counter-based synthetic tracks described in

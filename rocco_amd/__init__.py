@@ -55,6 +55,7 @@ from .bam import (  # noqa: F401  (htslib's BGZF reader, bam_read1, bam_endpos, 
     clear_alignment_cache,
     get_bam_chrom_reads,
     inflate_bgzf,
+    inflate_bgzf_device,
     parse_bam_header,
     read_alignment_file,
 )

@@ -310,6 +310,15 @@ PROTOTYPES = [
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, c_ll_p,
       ctypes.c_void_p]),
     ("rocco_hip_bam_shape", None, [c_int_p]),
+    # row f8 (csrc/bgzf_inflate.hip, csrc/inflate_core.h): htslib's bgzf_read_block: inflate, ISIZE and CRC32 of every block
+    ("rocco_hip_bgzf_inflate", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p, c_ll_p, ctypes.c_void_p]),
+    # (test support: the same rules over host memory, on the calling thread)
+    ("rocco_hip_bgzf_inflate_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p, c_ll_p]),
+    ("rocco_hip_bgzf_shape", None, [c_int_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t,
       ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]),

@@ -1,11 +1,12 @@
-"""Read BAM files (note (29)): BGZF blocks are inflated on the host with Python's zlib, everything
+"""Read BAM files (note (29)): BGZF blocks are inflated on the host with Python's zlib (the default)
+or on the device (``inflate="device"``: csrc/bgzf_inflate.hip, DEFLATE and CRC32 in HIP, one wavefront per block), everything
 after the inflate runs on the device (csrc/bam_records.hip): the record walk over the inflated bytes, the seven values per
 record that rows f5-f7 consume, and the split by contig.  `get_bam_chrom_reads` and `_get_bam_count_metadata` have the
 reference's signatures (rocco/readtracks.py:389-407, 242-252) and are composed from `read_alignment_file`,
 `rocco_amd.readtracks.bam_count_metadata_from_records` and `bam_chrom_reads_from_records`; an integrator binds the first
 behind the stub: ``rocco_amd.readtracks.get_bam_chrom_reads = rocco_amd.bam.get_bam_chrom_reads``.
 
-Not built: DEFLATE on the device, CRAM and SAM, the ``.bai`` index (the whole file is decoded; the index iterator's overlap
+Not built: CRAM and SAM, the ``.bai`` index (the whole file is decoded; the index iterator's overlap
 test is already applied by the counting kernels), CIGARs kept in a ``CG`` tag (reported as an error).  There is no CPU
 fallback for the record walk."""
 from __future__ import annotations
@@ -29,6 +30,7 @@ from .readtracks import AlignmentFileRecords, AlignmentRecords
 logger = _rt.logger  # (the reference's reader logs where its readtracks module does)
 
 DEFAULT_SLAB_BYTES = 256 << 20
+DEFAULT_INFLATE = "host"       # where `get_bam_chrom_reads` and `_get_bam_count_metadata` have a file's blocks inflated: "host" or "device"
 GUESS_DEPTH = 3                # ROCCO_BAM_GUESS_DEPTH of include/rocco_hip.h
 DEFAULT_SEGMENT_BYTES = 16384  # ROCCO_BAM_SEGMENT_BYTES
 _BGZF_HEADER = 12              # ID1 ID2 CM FLG MTIME(4) XFL OS XLEN(2)
@@ -48,6 +50,15 @@ _ERROR_TEXT = {
     ERR_ORDER: "its contig comes before the previous record's: the file is not coordinate-sorted (contigs in header order, "
                "records without a contig last)",
     ERR_OFFSET: "no record is framed there",
+}
+
+# ROCCO_BGZF_* of include/rocco_hip.h
+BGZF_THREADS, BGZF_TABLE_COLUMNS, BGZF_MAX_ISIZE, BGZF_STREAM_REASONS = 64, 5, 65536, 12
+BGZF_ERR_STREAM, BGZF_ERR_LENGTH, BGZF_ERR_CRC, BGZF_ERR_TABLE = range(1, 5)
+_STREAM_REASON_TEXT = {
+    1: "invalid block type", 2: "invalid stored block lengths", 3: "too many length or distance symbols", 4: "invalid code lengths set",
+    5: "invalid bit length repeat", 6: "invalid code -- missing end-of-block", 7: "invalid literal/lengths set", 8: "invalid distances set",
+    9: "invalid literal/length code", 10: "invalid distance code", 11: "invalid distance too far back", 12: "incomplete or truncated stream",
 }
 
 
@@ -175,6 +186,169 @@ def _inflate_slabs(source, threads: int, slab_bytes: Optional[int]) -> Iterator[
                 last += 1
             yield _inflate_group(raw, blocks[first:last], first, name, pool)
             first = last
+
+
+# --------------------------------------------------------------------------------------------
+# device: BGZF (csrc/bgzf_inflate.hip, csrc/inflate_core.h)
+# --------------------------------------------------------------------------------------------
+
+def bgzf_shape() -> dict:
+    """`rocco_hip_bgzf_shape`: the lanes per block, the columns of the block table, the largest ISIZE, the stream reasons."""
+    shape = (ctypes.c_int * 4)()
+    _native.load().rocco_hip_bgzf_shape(shape)
+    return {"threads": int(shape[0]), "table_columns": int(shape[1]), "max_isize": int(shape[2]), "stream_reasons": int(shape[3])}
+
+
+def bgzf_block_table(blocks, base: int = 0) -> np.ndarray:
+    """The block table of `rocco_hip_bgzf_inflate` for `_bgzf_blocks` rows: int64 [n][5] = first byte of the deflate data
+    (relative to ``base``), one past its last, ISIZE, CRC32, the prefix sum of ISIZE."""
+    table = np.zeros((len(blocks), BGZF_TABLE_COLUMNS), dtype=np.int64)
+    if blocks:
+        rows = np.asarray(blocks, dtype=np.int64)
+        table[:, 0], table[:, 1], table[:, 2], table[:, 3] = rows[:, 1] - base, rows[:, 2] - base, rows[:, 4], rows[:, 3]
+        table[1:, 4] = np.cumsum(table[:-1, 2])
+    return table
+
+
+def _report(back) -> dict:
+    return {"block": int(back[0]), "status": int(back[1]), "produced": int(back[2])}
+
+
+def inflate_blocks_host(comp, table: np.ndarray, out: np.ndarray):
+    """`rocco_hip_bgzf_inflate_host` (test support: the kernels' decode rules compiled for the host, on the calling thread):
+    inflates the rows of ``table`` from ``comp`` (bytes or a uint8 array) into the uint8 array ``out``; returns (the int32
+    status per block, the report ``block`` / ``status`` / ``produced``)."""
+    comp = np.ascontiguousarray(np.frombuffer(comp, dtype=np.uint8) if not isinstance(comp, np.ndarray) else comp)
+    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, BGZF_TABLE_COLUMNS)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise TypeError("inflate_blocks_host: out must be a writable contiguous uint8 array")
+    status = np.zeros(table.shape[0], dtype=np.int32)
+    back = (ctypes.c_longlong * 4)()
+    _native.check(_native.load().rocco_hip_bgzf_inflate_host(
+        None, comp.ctypes.data if comp.size else None, comp.size, table.ctypes.data if table.size else None, table.shape[0],
+        out.ctypes.data if out.size else None, out.size, status.ctypes.data if status.size else None, back), "rocco_hip_bgzf_inflate_host")
+    return status, _report(back)
+
+
+def inflate_blocks_device(comp_t, table_t, out_t, want_status: bool = False):
+    """`rocco_hip_bgzf_inflate`: inflates the rows of the int64 CUDA tensor ``table_t`` ([n][5]) from the uint8 CUDA tensor
+    ``comp_t`` into the uint8 CUDA tensor ``out_t``; returns (the int32 status per block as a CUDA tensor, or None, the report)."""
+    import torch
+
+    for t, dtype in ((comp_t, torch.uint8), (table_t, torch.int64), (out_t, torch.uint8)):
+        if not _dp._is_tensor(t) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.device != out_t.device:
+            raise TypeError("inflate_blocks_device: contiguous CUDA tensors on one device are required (uint8, int64, uint8)")
+    if table_t.numel() % BGZF_TABLE_COLUMNS:
+        raise ValueError("inflate_blocks_device: the block table has 5 columns")
+    n_blocks = table_t.numel() // BGZF_TABLE_COLUMNS
+    status = torch.empty(n_blocks, dtype=torch.int32, device=out_t.device) if want_status else None
+    back = (ctypes.c_longlong * 4)()
+    _native.check(_native.load().rocco_hip_bgzf_inflate(
+        _native.solver_for(out_t.device.index).handle, comp_t.data_ptr() or None, comp_t.numel(), table_t.data_ptr() or None, n_blocks,
+        out_t.data_ptr() or None, out_t.numel(), status.data_ptr() if status is not None and n_blocks else None, back,
+        _dp._stream_ptr(out_t)), "rocco_hip_bgzf_inflate")
+    return status, _report(back)
+
+
+def _bgzf_error(name: str, index: int, block, report: dict) -> ValueError:
+    """The host path's words (`_inflate_group`) for a block the device refused."""
+    where = f"{name}: BGZF block {index} at file offset {block[0]}"
+    code, why = report["status"] & 0xFF, report["status"] >> 8
+    if code == BGZF_ERR_STREAM:
+        return ValueError(f"{where}: the deflate stream does not inflate ({_STREAM_REASON_TEXT.get(why, f'reason {why}')})")
+    if code == BGZF_ERR_LENGTH:
+        return ValueError(f"{where}: length mismatch (ISIZE says {block[4]}, the data inflates to {report['produced']})")
+    if code == BGZF_ERR_CRC:
+        return ValueError(f"{where}: CRC32 mismatch")
+    return ValueError(f"{where}: its row of the block table does not fit the buffers (status {report['status']})")
+
+
+def _slab_groups(blocks, slab_bytes: Optional[int]):
+    """(first, one past the last) block of every slab: the rule of `_inflate_slabs`."""
+    first = 0
+    while first < len(blocks):
+        last, size = first, 0
+        while last < len(blocks) and (slab_bytes is None or size < slab_bytes or last == first):
+            size += blocks[last][4]
+            last += 1
+        while last < len(blocks) and blocks[last][4] == 0:  # (the end-of-file marker and its like go with the slab before)
+            last += 1
+        yield first, last
+        first = last
+
+
+def _device_of(device):
+    import torch
+
+    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
+    return dev if dev.index is not None else torch.device(f"cuda:{_dp._device_index()}")
+
+
+def _inflate_slabs_device(raw: memoryview, name: str, blocks, dev, slab_bytes: Optional[int]):
+    import torch
+
+    for index, block in enumerate(blocks):
+        if block[4] > BGZF_MAX_ISIZE:
+            raise ValueError(f"{name}: BGZF block {index} at file offset {block[0]}: length mismatch (ISIZE says {block[4]}, a BGZF block "
+                             f"holds at most {BGZF_MAX_ISIZE} bytes; inflate=\"host\" reads a file that breaks this rule)")
+    for first, last in _slab_groups(blocks, slab_bytes):
+        group = blocks[first:last]
+        base, end = group[0][1], group[-1][2]
+        table = bgzf_block_table(group, base)
+        head = table.size * 8
+        staged = _host_buffer(head + end - base)  # (pinned: the table and the compressed bytes go up in one asynchronous copy)
+        staged[:head] = table.reshape(-1).view(np.uint8)
+        staged[head:] = np.frombuffer(raw[base:end], dtype=np.uint8)
+        with torch.cuda.device(dev):
+            up = torch.from_numpy(staged).to(dev, non_blocking=True)
+            out = torch.empty(int(table[-1, 2] + table[-1, 4]), dtype=torch.uint8, device=dev)
+            _, report = inflate_blocks_device(up[head:], up[:head].view(torch.int64), out)  # (synchronises: `staged` may go)
+        if report["block"] >= 0:
+            raise _bgzf_error(name, first + report["block"], group[report["block"]], report)
+        yield out
+
+
+def inflate_bgzf_device(source, device=None, slab_bytes: Optional[int] = None):
+    """The device twin of `inflate_bgzf`: the inflated bytes of a BGZF file (``source``: a path or bytes) as a uint8 CUDA
+    tensor.  The block headers are walked on the host as there; the compressed bytes go up from pinned memory with the block
+    table, `rocco_hip_bgzf_inflate` inflates every block with one wavefront and checks its length and CRC32 on the device.
+    The same ValueErrors as the host path, naming the block and its file offset (between the parentheses of ``the deflate
+    stream does not inflate (...)`` stands the kernel's reason, in zlib's words); a block whose ISIZE exceeds 65 536 is
+    refused.
+
+    With ``slab_bytes``: a generator of such tensors, cut at BGZF block boundaries by the rule of `inflate_bgzf`."""
+    import torch
+
+    dev = _device_of(device)
+    if slab_bytes is not None and int(slab_bytes) < 1:
+        raise ValueError("inflate_bgzf_device: slab_bytes must be positive")
+    raw, name = _source_bytes(source)
+    slabs = _inflate_slabs_device(raw, name, _bgzf_blocks(raw, name), dev, None if slab_bytes is None else int(slab_bytes))
+    if slab_bytes is not None:
+        return slabs
+    slabs = list(slabs)
+    return slabs[0] if slabs else torch.empty(0, dtype=torch.uint8, device=dev)
+
+
+class _Inline:
+    """A pool of the calling thread (for `_inflate_group` over a block or two)."""
+    map = staticmethod(map)
+
+
+def _header_from_leading_blocks(raw: memoryview, name: str, blocks):
+    """(contigs, the offset of the first record) from a host inflate of as many leading blocks as the header covers."""
+    head, k = np.empty(0, dtype=np.uint8), 0
+    while True:
+        try:
+            _, contigs, entry0 = parse_bam_header(head)
+            return contigs, entry0
+        except _HeaderCutShort as exc:
+            if k == len(blocks):
+                raise ValueError(f"{name}: {exc}") from None
+        except ValueError as exc:
+            raise ValueError(f"{name}: {exc}") from None
+        head = np.concatenate([head, _inflate_group(raw, blocks[k: k + 1], k, name, _Inline)])
+        k += 1
 
 
 # --------------------------------------------------------------------------------------------
@@ -309,24 +483,37 @@ def decode_records_device(bytes_t, entry0: int, n_ref: int, segment_bytes: Optio
 
 
 def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT_SLAB_BYTES, segment_bytes: Optional[int] = None,
-                        threads: Optional[int] = None, guess_mode: int = 1, report: Optional[dict] = None):
+                        threads: Optional[int] = None, guess_mode: int = 1, report: Optional[dict] = None, inflate: str = "host"):
     """A whole BAM file as (`AlignmentFileRecords` whose records carry ``qlen`` and are CUDA tensors, ``name`` the path; the
     number of records without a contig).  Slab by slab: `inflate_bgzf` yields about ``slab_bytes`` inflated bytes, they are
     uploaded, walked and decoded on the device; a slab's bytes behind its last complete record are carried in front of the
     next slab; the per-contig arrays are views of the seven concatenated arrays.  ``names``: keep these contigs only.
-    ``report`` (a dict) receives the walk's totals."""
+    ``report`` (a dict) receives the walk's totals.
+
+    ``inflate="device"``: the slabs come from `inflate_bgzf_device` and are inflated where they are consumed; the carry is a
+    device tensor and the inflated bytes never visit the host.  The header alone is read on the host, from an inflate of the
+    leading blocks it covers.  The decoded arrays are the same in both modes."""
     import torch
 
     path = os.fspath(path)
-    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
-    if dev.index is None:
-        dev = torch.device(f"cuda:{_dp._device_index()}")
+    if inflate not in ("host", "device"):
+        raise ValueError(f"read_alignment_file: inflate must be \"host\" or \"device\", not {inflate!r}")
+    on_device = inflate == "device"
+    dev = _device_of(device)
     contigs, n_ref = None, 0
-    carry = np.empty(0, dtype=np.uint8)
+    if on_device:
+        raw, _ = _source_bytes(path)
+        blocks = _bgzf_blocks(raw, path)
+        header = _header_from_leading_blocks(raw, path, blocks)
+        slabs = _inflate_slabs_device(raw, path, blocks, dev, max(1, int(slab_bytes)))
+        empty, join = torch.empty(0, dtype=torch.uint8, device=dev), torch.cat
+    else:
+        slabs = inflate_bgzf(path, threads=threads, slab_bytes=max(1, int(slab_bytes)))
+        empty, join = np.empty(0, dtype=np.uint8), np.concatenate
+    carry = empty
     parts, counts, last_key, n_records, consumed = [], None, -1, 0, 0
     totals = {"records": 0, "segments": 0, "wrong_guesses": 0, "repair_rounds": 0, "slabs": 0}
     pending = None
-    slabs = inflate_bgzf(path, threads=threads, slab_bytes=max(1, int(slab_bytes)))
 
     def with_last(it):
         previous = None
@@ -334,12 +521,19 @@ def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT
             if previous is not None:
                 yield previous, False
             previous = item
-        yield (previous if previous is not None else np.empty(0, dtype=np.uint8)), True
+        yield (previous if previous is not None else empty), True
 
     for slab, is_last in with_last(slabs):
-        data = np.concatenate([carry, slab]) if carry.size else slab
+        data = join([carry, slab]) if carry.shape[0] else slab
         entry0 = 0
-        if contigs is None:
+        if contigs is None and on_device:
+            if data.shape[0] < header[1] and not is_last:  # (the header straddles slabs)
+                carry = data
+                continue
+            contigs, entry0 = header
+            n_ref = len(contigs)
+            counts = np.zeros(n_ref + 1, dtype=np.int64)
+        elif contigs is None:
             try:
                 _, contigs, entry0 = parse_bam_header(data)
             except _HeaderCutShort as exc:
@@ -351,7 +545,7 @@ def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT
                 raise ValueError(f"{path}: {exc}") from None
             n_ref = len(contigs)
             counts = np.zeros(n_ref + 1, dtype=np.int64)
-        bytes_t = torch.from_numpy(data).to(dev, non_blocking=True)
+        bytes_t = data if on_device else torch.from_numpy(data).to(dev, non_blocking=True)
         fields, firsts, rep = decode_records_device(bytes_t, entry0, n_ref, segment_bytes, guess_mode, path, whole=is_last,
                                                     first_record=n_records, first_byte=consumed)
         slab_counts = np.diff(np.asarray(firsts, dtype=np.int64))
@@ -366,7 +560,10 @@ def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT
         for key in ("records", "segments", "wrong_guesses", "repair_rounds"):
             totals[key] += rep[key]
         totals["slabs"] += 1
-        carry = data[rep["end_offset"]:].copy() if rep["end_offset"] < data.shape[0] else np.empty(0, dtype=np.uint8)
+        if rep["end_offset"] < data.shape[0]:
+            carry = data[rep["end_offset"]:].clone() if on_device else data[rep["end_offset"]:].copy()
+        else:
+            carry = empty
         consumed += rep["end_offset"]
         pending = bytes_t  # (the upload's source `data` lives until the next slab's synchronising call has returned)
     del pending
@@ -415,7 +612,7 @@ def _cached_file(bam_file: str) -> AlignmentFileRecords:
     if hit is not None:
         _ALIGNMENT_CACHE.move_to_end(key)
         return hit[0]
-    file, _ = read_alignment_file(bam_file)
+    file, _ = read_alignment_file(bam_file, inflate=DEFAULT_INFLATE)
     file.name = bam_file
     size = _file_bytes(file)
     _ALIGNMENT_CACHE[key] = (file, size)

@@ -9,7 +9,7 @@
 //                                                                                                  bam_emit_kernel
 //   bam_endpos      pos + reference length of the CIGAR (0 for an unmapped record; 0 becomes 1)    bam_fields_kernel
 //   bam_cigar2qlen  the query length of the CIGAR where l_seq <= 0                                 bam_fields_kernel
-// BGZF inflate stays on the host (rocco_amd/bam.py); bam_tag2cigar (the CG tag) is not decoded: it is reported.
+// BGZF inflate is the host's (rocco_amd/bam.py) or bgzf_inflate.hip's; bam_tag2cigar (the CG tag) is not decoded: it is reported.
 //
 // The record stream is a linked list: a record's first word says where the next begins.  It is cut into segments of S
 // bytes.  Every segment i guesses its entry (the lowest offset in [iS, (i + 1)S) from which kBamGuessDepth records in a row

@@ -377,6 +377,14 @@ int launch_bam_record_fields(const uint8_t *bytes_dev, size_t n_bytes, const int
                              uint8_t *mapq_out_dev, uint8_t *mate_same_out_dev, int32_t *qlen_out_dev, int64_t *contig_first_out_host,
                              int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
 
+// ---- bgzf_inflate.hip -------------------------------------------------------------------------
+size_t bgzf_inflate_scratch_bytes(size_t n_blocks);
+int launch_bgzf_inflate(const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks, uint8_t *out_dev, size_t n_out,
+                        int32_t *status_out_dev, int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
+// test support: the same blocks over host memory on the calling thread (inflate_core.h compiled for the host)
+void bgzf_inflate_host_blocks(const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks, uint8_t *out, size_t n_out,
+                              int32_t *status_out, int64_t *report_out);
+
 // ---- synth.hip ------------------------------------------------------------------------------
 int launch_synth(void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, uint64_t seed,
                  hipStream_t stream);

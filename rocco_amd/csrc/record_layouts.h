@@ -149,6 +149,21 @@ struct BamFieldsLayout {
     }
 };
 
+// launch_bgzf_inflate: per block its status (int32; unused where the caller brings its own), the bytes it inflates to (int64);
+// the word of the first failing block; the report
+struct BgzfInflateLayout {
+    size_t status, produced, first_error, report, bytes;
+    explicit BgzfInflateLayout(size_t n_blocks)
+    {
+        Layout lay;
+        status = lay.at(n_blocks * sizeof(int));
+        produced = lay.at(n_blocks * sizeof(long long));
+        first_error = lay.at(sizeof(unsigned long long));
+        report = lay.at(ROCCO_BGZF_REPORT * sizeof(long long));
+        bytes = lay.bytes();
+    }
+};
+
 }  // namespace
 
 }  // namespace rocco

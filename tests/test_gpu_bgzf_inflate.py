@@ -1,0 +1,244 @@
+"""GPU: the BGZF inflate of csrc/bgzf_inflate.hip (DEFLATE and CRC32 in HIP, one wavefront per block; DESIGN.md section 0 row
+f8, note (29)) against the host path of rocco_amd/bam.py -- Python's zlib -- on every case of tests/bgzf_expected.py, byte for
+byte and verdict for verdict, and `read_alignment_file(..., inflate="device")` against `inflate="host"` on the BAM fixtures."""
+import struct
+
+import numpy as np
+import pytest
+
+import bam_expected as bx
+import bgzf_expected as gx
+
+pytestmark = pytest.mark.gpu
+
+BAM_FILES = ["mixed", "blocks", "longread", "header_only", "one_record", "unplaced_only", "cg", "decoy"]
+RECORD_FIELDS = ("pos", "end", "isize", "flag", "mapq", "mate_same", "qlen")
+
+
+def run_device(gpu, raw: bytes, label: str = ""):
+    """`rocco_hip_bgzf_inflate` over a whole file into a guarded buffer, verified against the host's verdicts; the report."""
+    import torch
+
+    from rocco_amd import bam
+
+    table, n_out = gx.guarded_table(raw)
+    out = torch.full((n_out,), gx.GUARD_BYTE, dtype=torch.uint8, device=gpu)
+    comp = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(gpu)
+    status, report = bam.inflate_blocks_device(comp, torch.from_numpy(table).to(gpu), out, want_status=True)
+    first = gx.verify(raw, table, status.cpu().numpy(), out.cpu().numpy(), label)
+    assert report["block"] == first, label
+    return report
+
+
+def test_valid_files_byte_for_byte(gpu):
+    """Every valid case through `inflate_bgzf_device`, whole and in slabs of 1 and 100 000 bytes, against `inflate_bgzf`."""
+    import torch
+
+    from rocco_amd import bam
+
+    for label, raw in gx.valid_files():
+        want = bam.inflate_bgzf(raw).tobytes()
+        whole = bam.inflate_bgzf_device(raw, device=gpu)
+        assert whole.dtype == torch.uint8 and whole.device == gpu and whole.cpu().numpy().tobytes() == want, label
+        for slab_bytes in (1, 100000):
+            slabs = list(bam.inflate_bgzf_device(raw, device=gpu, slab_bytes=slab_bytes))
+            host_slabs = list(bam.inflate_bgzf(raw, slab_bytes=slab_bytes))
+            assert [int(s.shape[0]) for s in slabs] == [int(s.size) for s in host_slabs], (label, slab_bytes)
+            assert (torch.cat(slabs) if slabs else whole).cpu().numpy().tobytes() == want, (label, slab_bytes)
+    assert bam.inflate_bgzf_device(b"", device=gpu).shape[0] == 0
+
+
+def test_corrupt_files_raise_the_hosts_errors(gpu):
+    """One file per acceptance rule and per place of the bad block: a ValueError with the host's prefix (block index, file
+    offset) and the host's leading words, whole and slab by slab."""
+    from rocco_amd import bam
+
+    for label, raw, index, code in gx.corrupt_files():
+        pattern = gx.error_pattern(raw, index, code)
+        with pytest.raises(ValueError, match=pattern):
+            bam.inflate_bgzf_device(raw, device=gpu)
+        with pytest.raises(ValueError, match=pattern):
+            for _ in bam.inflate_bgzf_device(raw, device=gpu, slab_bytes=1):
+                pass
+    big = gx.block(gx.deflate(b"abc"), 0, 65537) + gx.EOF_BLOCK
+    with pytest.raises(ValueError, match=r"BGZF block 0 at file offset 0: length mismatch \(ISIZE says 65537, "):
+        bam.inflate_bgzf_device(big, device=gpu)
+
+
+def test_status_per_block_and_nothing_written_outside(gpu):
+    """Every file, sound or corrupt, into a buffer with guard bytes around each block's range: the status of every block, the
+    bytes of every accepted one, the guards untouched (an ISIZE smaller than the stream among them); the report names the
+    first refused block and, for a length error, the bytes the stream inflates to."""
+    import zlib
+
+    for label, raw in gx.valid_files():
+        assert run_device(gpu, raw, label)["block"] == -1
+    for label, raw, index, code in gx.corrupt_files():
+        report = run_device(gpu, raw, label)
+        assert report["block"] == index and report["status"] & 0xFF == code, label
+        if code == gx.ERR_LENGTH:
+            _, lo, hi, _, _ = gx.blocks_of(raw)[index]
+            assert report["produced"] == len(zlib.decompress(raw[lo:hi], wbits=-15)), label
+
+
+def test_mutation_set_in_one_call(gpu):
+    """2 000 seeded mutations as one file of 2 000 blocks: the status array entry by entry against zlib's verdicts, the bytes
+    of every accepted block; no case is excluded."""
+    raw = gx.mutation_file()
+    assert len(gx.blocks_of(raw)) == gx.MUTATIONS
+    run_device(gpu, raw, "mutations")
+
+
+def test_rows_outside_the_buffers_are_refused(gpu):
+    import torch
+
+    from rocco_amd import bam
+
+    raw = gx.valid_files()[5][1]
+    table = gx.table_of(raw)
+    n_out = int(table[:, 2].sum())
+    comp = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(gpu)
+    for column, value in ((0, -1), (1, len(raw) + 1), (2, 65537), (4, -1), (4, n_out)):
+        bad = table.copy()
+        bad[0, column] = value
+        out = torch.full((n_out,), gx.GUARD_BYTE, dtype=torch.uint8, device=gpu)
+        status, report = bam.inflate_blocks_device(comp, torch.from_numpy(bad).to(gpu), out, want_status=True)
+        assert int(status[0]) == gx.ERR_TABLE and report["block"] == 0 and bool((out == gx.GUARD_BYTE).all()), (column, value)
+    with pytest.raises(TypeError):
+        bam.inflate_blocks_device(comp.cpu(), torch.from_numpy(table).to(gpu), torch.empty(n_out, dtype=torch.uint8, device=gpu))
+
+
+def same_files(a, b):
+    import torch
+
+    (file_a, unplaced_a), (file_b, unplaced_b) = a, b
+    assert file_a.contigs == file_b.contigs and unplaced_a == unplaced_b and sorted(file_a.records) == sorted(file_b.records)
+    for contig in file_a.records:
+        for name in RECORD_FIELDS:
+            x, y = getattr(file_a.records[contig], name), getattr(file_b.records[contig], name)
+            assert x.is_cuda and y.is_cuda and x.dtype == y.dtype and torch.equal(x, y), (contig, name)
+
+
+def read_both(gpu, path, **how):
+    """`read_alignment_file` in both modes: equal files, or the same ValueError text."""
+    from rocco_amd import bam
+
+    try:
+        host = bam.read_alignment_file(path, device=gpu, **how)
+    except ValueError as exc:
+        with pytest.raises(ValueError) as info:
+            bam.read_alignment_file(path, device=gpu, inflate="device", **how)
+        assert str(info.value) == str(exc)
+        return None
+    device_report = {}
+    same_files(host, bam.read_alignment_file(path, device=gpu, inflate="device", report=device_report, **how))
+    return device_report
+
+
+@pytest.mark.parametrize("key", BAM_FILES)
+def test_read_alignment_file_device_equals_host(gpu, tmp_path, key):
+    """All eight fixtures: whole, in slabs of 1 000 and 4 096 bytes (a record and the header straddle slabs, the carry is a
+    device tensor), and at 64-byte segments."""
+    path = bx.write_bam(tmp_path, key)
+    whole = read_both(gpu, path)
+    assert whole is None or whole["slabs"] == 1
+    assert (whole is None) == (key == "cg")
+    for slab_bytes in (1000, 4096):
+        report = read_both(gpu, path, slab_bytes=slab_bytes)
+        if key == "blocks":
+            assert report["slabs"] > 3
+    read_both(gpu, path, segment_bytes=64)
+    data, _ = bx.inflate(bx.bam_bytes(key))
+    if key == "blocks":  # blocks cut every 777 bytes: many records straddle blocks and slabs
+        with open(path, "wb") as handle:
+            handle.write(bx.bgzf_compress(data, cuts=range(777, len(data), 777)))
+        assert read_both(gpu, path, slab_bytes=1000)["slabs"] > 3
+    if len(data) < 3000:  # blocks of 50 bytes in slabs of 60: the header itself straddles slabs
+        assert bx.header(data)[2] > 120
+        with open(path, "wb") as handle:
+            handle.write(bx.bgzf_compress(data, cuts=range(50, len(data), 50)))
+        read_both(gpu, path, slab_bytes=60)
+
+
+def test_corrupt_bam_files_raise_the_same_text(gpu, tmp_path):
+    """Corrupt variants of the `mixed` fixture whose error text does not depend on zlib's wording: the same ValueError in
+    both modes, whole and slab by slab."""
+    data, _ = bx.inflate(bx.bam_bytes("mixed"))
+    _, contigs, entry0 = bx.header(data)
+    offsets, _, _, _ = bx.walk(data, entry0)
+    p = int(offsets[len(offsets) // 2])
+    no_name = bytearray(data)
+    struct.pack_into("<B", no_name, p + 12, 0)
+    sound = bx.bgzf_compress(data, cuts=range(5000, len(data), 5000))
+    crc = bytearray(sound)
+    crc[len(bx.bgzf_block(data[:5000])) - 8] ^= 1
+    isize = bytearray(sound)
+    isize[len(bx.bgzf_block(data[:5000])) - 4] ^= 1
+    variants = {"l_read_name = 0": bx.bgzf_compress(bytes(no_name), cuts=range(5000, len(data), 5000)),
+                "the stream ends inside a record": bx.bgzf_compress(data[:-3]),
+                "a flipped CRC32 bit in block 0": bytes(crc),
+                "not a BAM file": bx.bgzf_compress(b"BAM\x02" + data[4:]),
+                "the header cut short": bx.bgzf_compress(data[: entry0 - 5], cuts=(20,)),
+                "no block at all": b"",
+                "the file ends inside a block": sound[:-40]}
+    path = str(tmp_path / "bad.bam")
+    for label, raw in variants.items():
+        with open(path, "wb") as handle:
+            handle.write(raw)
+        for how in ({}, {"slab_bytes": 6000}):
+            assert read_both(gpu, path, **how) is None, label
+    with open(path, "wb") as handle:
+        handle.write(bytes(isize))
+    from rocco_amd import bam
+
+    for mode in ("host", "device"):  # (the host states zlib's count, the device its own: the leading words are the same)
+        with pytest.raises(ValueError, match=r"BGZF block 0 at file offset 0: length mismatch \(ISIZE says 5001, the data inflates to 5000\)"):
+            bam.read_alignment_file(path, device=gpu, inflate=mode)
+
+
+def test_default_inflate_device_serves_the_reference_results(gpu, tmp_path, monkeypatch):
+    """With DEFAULT_INFLATE = "device" and an empty cache, `get_bam_chrom_reads` on `mixed` and `blocks` returns what the
+    reference returned for them (the golden results of test_gpu_bam_reader.py)."""
+    from rocco_amd import bam
+
+    arrays, meta = bx.golden()
+    sizes = str(tmp_path / "t.sizes")
+    with open(sizes, "w") as handle:
+        handle.write("".join(f"{name}\t{length}\n" for name, length in meta["sizes"]))
+    monkeypatch.setattr(bam, "DEFAULT_INFLATE", "device")
+    modes = []
+    read = bam.read_alignment_file
+    monkeypatch.setattr(bam, "read_alignment_file", lambda path, *a, **kw: (modes.append(kw.get("inflate")), read(path, *a, **kw))[1])
+    bam.clear_alignment_cache()
+    try:
+        for key in ("mixed", "blocks"):
+            path = bx.write_bam(tmp_path, key)
+            seen = 0
+            for entry in meta["chrom_reads"]:
+                if entry["file"] != key:
+                    continue
+                seen += 1
+                call = lambda: bam.get_bam_chrom_reads(path, entry["contig"], sizes, entry["step"], **entry["kwargs"])
+                if entry["error"] is not None:
+                    with pytest.raises({"RuntimeError": RuntimeError, "ValueError": ValueError}[entry["error_type"]]) as info:
+                        call()
+                    assert str(info.value).replace(sizes, "{sizes}") == entry["error"], entry["name"]
+                    continue
+                intervals, vals = call()
+                if entry["none"]:
+                    assert intervals is None and vals is None, entry["name"]
+                    continue
+                want_i, want_v = arrays[f"r_{entry['name']}_intervals"], arrays[f"r_{entry['name']}_values"]
+                assert intervals.dtype == want_i.dtype and np.array_equal(intervals, want_i), entry["name"]
+                assert vals.dtype == want_v.dtype and vals.tobytes() == want_v.tobytes(), entry["name"]
+            assert seen == 16
+        assert modes == ["device", "device"]  # (each file decoded once, on the device path, then served from the cache)
+    finally:
+        bam.clear_alignment_cache()
+
+
+def test_unknown_mode_is_refused(gpu, tmp_path):
+    from rocco_amd import bam
+
+    with pytest.raises(ValueError, match="inflate must be"):
+        bam.read_alignment_file(bx.write_bam(tmp_path, "one_record"), device=gpu, inflate="nonsense")
