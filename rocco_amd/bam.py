@@ -1,7 +1,9 @@
 """Read BAM files (note (29)): BGZF blocks are inflated on the host with Python's zlib (the default)
 or on the device (``inflate="device"``: csrc/bgzf_inflate.hip, DEFLATE and CRC32 in HIP, one wavefront per block), everything
 after the inflate runs on the device (csrc/bam_records.hip): the record walk over the inflated bytes, the seven values per
-record that rows f5-f7 consume, and the split by contig.  `get_bam_chrom_reads` and `_get_bam_count_metadata` have the
+record that rows f5-f7 consume, and the split by contig.  Both modes share one front (the file read once, `_bgzf_blocks`, the
+slab rule `_slab_groups`, one wording of the block errors) and one loop in `read_alignment_file`, which takes the header
+first and then slabs of inflated bytes as device tensors, wherever they were inflated.  `get_bam_chrom_reads` and `_get_bam_count_metadata` have the
 reference's signatures (rocco/readtracks.py:389-407, 242-252) and are composed from `read_alignment_file`,
 `rocco_amd.readtracks.bam_count_metadata_from_records` and `bam_chrom_reads_from_records`; an integrator binds the first
 behind the stub: ``rocco_amd.readtracks.get_bam_chrom_reads = rocco_amd.bam.get_bam_chrom_reads``.
@@ -63,7 +65,7 @@ _STREAM_REASON_TEXT = {
 
 
 # --------------------------------------------------------------------------------------------
-# host: BGZF
+# BGZF: the front both inflates share (source, blocks, slab rule, error words) and the host inflate
 # --------------------------------------------------------------------------------------------
 
 def _default_threads() -> int:
@@ -80,41 +82,90 @@ def _source_bytes(source):
         return memoryview(handle.read()), os.fspath(source)
 
 
+def _block_where(name: str, index: int, at: int) -> str:
+    return f"{name}: BGZF block {index} at file offset {at}"
+
+
+def _does_not_inflate(where: str, why: str) -> ValueError:
+    return ValueError(f"{where}: the deflate stream does not inflate ({why})")
+
+
+def _length_mismatch(where: str, isize: int, produced: int) -> ValueError:
+    return ValueError(f"{where}: length mismatch (ISIZE says {isize}, the data inflates to {produced})")
+
+
+def _crc_mismatch(where: str) -> ValueError:
+    return ValueError(f"{where}: CRC32 mismatch")
+
+
 def _bgzf_blocks(raw: memoryview, name: str) -> List[Tuple[int, int, int, int, int]]:
     """(file offset, first byte of the deflate data, one past its last, CRC32, ISIZE) per block, from the block headers."""
     blocks, at, total = [], 0, len(raw)
+
+    def bad(what: str) -> ValueError:  # (worded only where a block is refused: a file has tens of thousands of blocks)
+        return ValueError(f"{_block_where(name, len(blocks), at)}: {what}")
+
     while at < total:
-        index = len(blocks)
-        where = f"{name}: BGZF block {index} at file offset {at}"
         if at + _BGZF_HEADER > total:
-            raise ValueError(f"{where}: the file ends inside the block header")
+            raise bad("the file ends inside the block header")
         id1, id2, cm, flg = raw[at], raw[at + 1], raw[at + 2], raw[at + 3]
         if id1 != 0x1F or id2 != 0x8B or cm != 8:
-            raise ValueError(f"{where}: bad header (no gzip magic)")
+            raise bad("bad header (no gzip magic)")
         if not flg & 4:
-            raise ValueError(f"{where}: bad header (FLG.FEXTRA is not set)")
+            raise bad("bad header (FLG.FEXTRA is not set)")
         (xlen,) = struct.unpack_from("<H", raw, at + 10)
         extra, extra_end = at + _BGZF_HEADER, at + _BGZF_HEADER + xlen
         if extra_end > total:
-            raise ValueError(f"{where}: the file ends inside the block header")
+            raise bad("the file ends inside the block header")
         bsize = None
         while extra + 4 <= extra_end:
             si1, si2, slen = raw[extra], raw[extra + 1], struct.unpack_from("<H", raw, extra + 2)[0]
             if extra + 4 + slen > extra_end:
-                raise ValueError(f"{where}: bad header (an extra subfield overruns XLEN)")
+                raise bad("bad header (an extra subfield overruns XLEN)")
             if si1 == 66 and si2 == 67 and slen == 2:
                 bsize = struct.unpack_from("<H", raw, extra + 4)[0] + 1
             extra += 4 + slen
         if bsize is None:
-            raise ValueError(f"{where}: bad header (no BC subfield)")
+            raise bad("bad header (no BC subfield)")
         if bsize < _BGZF_HEADER + xlen + 8:
-            raise ValueError(f"{where}: bad header (BSIZE is smaller than the header and trailer)")
+            raise bad("bad header (BSIZE is smaller than the header and trailer)")
         if at + bsize > total:
-            raise ValueError(f"{where}: the file ends inside the block ({total - at} of {bsize} bytes)")
+            raise bad(f"the file ends inside the block ({total - at} of {bsize} bytes)")
         crc, isize = struct.unpack_from("<II", raw, at + bsize - 8)
         blocks.append((at, extra_end, at + bsize - 8, crc, isize))
         at += bsize
     return blocks
+
+
+def _bgzf_front(source, slab_bytes: Optional[int], who: str):
+    """What both inflates start from: (the source's bytes, read once; its name; its blocks, walked once; ``slab_bytes`` checked)."""
+    if slab_bytes is not None and int(slab_bytes) < 1:
+        raise ValueError(f"{who}: slab_bytes must be positive")
+    raw, name = _source_bytes(source)
+    return raw, name, _bgzf_blocks(raw, name), None if slab_bytes is None else int(slab_bytes)
+
+
+def _slab_groups(blocks, slab_bytes: Optional[int]):
+    """(first, one past the last) block of every slab: a slab holds at least ``slab_bytes`` inflated bytes (everything for
+    None) and at least one block; trailing empty blocks go with the slab before."""
+    first = 0
+    while first < len(blocks):
+        last, size = first, 0
+        while last < len(blocks) and (slab_bytes is None or size < slab_bytes or last == first):
+            size += blocks[last][4]
+            last += 1
+        while last < len(blocks) and blocks[last][4] == 0:  # (the end-of-file marker and its like)
+            last += 1
+        yield first, last
+        first = last
+
+
+def _whole_or_slabs(slabs, slab_bytes: Optional[int], empty):
+    """The generator itself where slabs were asked for, else the one slab of the whole stream (``empty()`` for no block)."""
+    if slab_bytes is not None:
+        return slabs
+    slabs = list(slabs)
+    return slabs[0] if slabs else empty()
 
 
 def _host_buffer(n: int) -> np.ndarray:
@@ -130,27 +181,35 @@ def _host_buffer(n: int) -> np.ndarray:
     return t.numpy()[: int(n)]
 
 
-def _inflate_group(raw: memoryview, blocks, first_index: int, name: str, pool) -> np.ndarray:
-    starts = np.zeros(len(blocks) + 1, dtype=np.int64)
-    np.cumsum([b[4] for b in blocks], out=starts[1:])
-    out = _host_buffer(int(starts[-1]))
+def _inflate_block(raw: memoryview, name: str, index: int, block) -> bytes:
+    """One block through zlib, its length and CRC32 checked."""
+    at, lo, hi, crc, isize = block
+    where = _block_where(name, index, at)
+    try:
+        data = zlib.decompress(raw[lo:hi], wbits=-15)
+    except zlib.error as exc:
+        raise _does_not_inflate(where, exc) from None
+    if len(data) != isize:
+        raise _length_mismatch(where, isize, len(data))
+    if zlib.crc32(data) != crc:
+        raise _crc_mismatch(where)
+    return data
 
-    def one(k):
-        at, lo, hi, crc, isize = blocks[k]
-        where = f"{name}: BGZF block {first_index + k} at file offset {at}"
-        try:
-            data = zlib.decompress(raw[lo:hi], wbits=-15)
-        except zlib.error as exc:
-            raise ValueError(f"{where}: the deflate stream does not inflate ({exc})") from None
-        if len(data) != isize:
-            raise ValueError(f"{where}: length mismatch (ISIZE says {isize}, the data inflates to {len(data)})")
-        if zlib.crc32(data) != crc:
-            raise ValueError(f"{where}: CRC32 mismatch")
-        out[starts[k]: starts[k + 1]] = np.frombuffer(data, dtype=np.uint8)
 
-    for _ in pool.map(one, range(len(blocks))):
-        pass
-    return out
+def _inflate_slabs(raw: memoryview, name: str, blocks, threads: Optional[int], slab_bytes: Optional[int]) -> Iterator[np.ndarray]:
+    threads = _default_threads() if threads is None else max(1, int(threads))
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        for first, last in _slab_groups(blocks, slab_bytes):
+            starts = np.zeros(last - first + 1, dtype=np.int64)
+            np.cumsum([b[4] for b in blocks[first:last]], out=starts[1:])
+            out = _host_buffer(int(starts[-1]))
+
+            def one(k):
+                out[starts[k - first]: starts[k - first + 1]] = np.frombuffer(_inflate_block(raw, name, k, blocks[k]), dtype=np.uint8)
+
+            for _ in pool.map(one, range(first, last)):
+                pass
+            yield out
 
 
 def inflate_bgzf(source, threads: Optional[int] = None, slab_bytes: Optional[int] = None):
@@ -162,30 +221,10 @@ def inflate_bgzf(source, threads: Optional[int] = None, slab_bytes: Optional[int
     a mismatch or a file that ends inside a block; a missing end-of-file marker block is accepted.
 
     With ``slab_bytes``: a generator of such arrays, each of about that many inflated bytes (at least one block), cut at
-    BGZF block boundaries."""
-    threads = _default_threads() if threads is None else max(1, int(threads))
-    if slab_bytes is None:
-        slabs = list(_inflate_slabs(source, threads, None))
-        return slabs[0] if slabs else _host_buffer(0)
-    if int(slab_bytes) < 1:
-        raise ValueError("inflate_bgzf: slab_bytes must be positive")
-    return _inflate_slabs(source, threads, int(slab_bytes))
-
-
-def _inflate_slabs(source, threads: int, slab_bytes: Optional[int]) -> Iterator[np.ndarray]:
-    raw, name = _source_bytes(source)
-    blocks = _bgzf_blocks(raw, name)
-    with ThreadPoolExecutor(max_workers=threads) as pool:
-        first = 0
-        while first < len(blocks):
-            last, size = first, 0
-            while last < len(blocks) and (slab_bytes is None or size < slab_bytes or last == first):
-                size += blocks[last][4]
-                last += 1
-            while last < len(blocks) and blocks[last][4] == 0:  # (the end-of-file marker and its like go with the slab before)
-                last += 1
-            yield _inflate_group(raw, blocks[first:last], first, name, pool)
-            first = last
+    BGZF block boundaries (`_slab_groups`).  The block headers are walked, and their errors raised, at the call; a block is
+    inflated and checked when its slab is asked for."""
+    raw, name, blocks, slab_bytes = _bgzf_front(source, slab_bytes, "inflate_bgzf")
+    return _whole_or_slabs(_inflate_slabs(raw, name, blocks, threads, slab_bytes), slab_bytes, lambda: _host_buffer(0))
 
 
 # --------------------------------------------------------------------------------------------
@@ -250,38 +289,16 @@ def inflate_blocks_device(comp_t, table_t, out_t, want_status: bool = False):
     return status, _report(back)
 
 
-def _bgzf_error(name: str, index: int, block, report: dict) -> ValueError:
-    """The host path's words (`_inflate_group`) for a block the device refused."""
-    where = f"{name}: BGZF block {index} at file offset {block[0]}"
+def _bgzf_error(where: str, isize: int, report: dict) -> ValueError:
+    """The host path's words (`_inflate_block`) for a block the device refused."""
     code, why = report["status"] & 0xFF, report["status"] >> 8
     if code == BGZF_ERR_STREAM:
-        return ValueError(f"{where}: the deflate stream does not inflate ({_STREAM_REASON_TEXT.get(why, f'reason {why}')})")
+        return _does_not_inflate(where, _STREAM_REASON_TEXT.get(why, f"reason {why}"))
     if code == BGZF_ERR_LENGTH:
-        return ValueError(f"{where}: length mismatch (ISIZE says {block[4]}, the data inflates to {report['produced']})")
+        return _length_mismatch(where, isize, report["produced"])
     if code == BGZF_ERR_CRC:
-        return ValueError(f"{where}: CRC32 mismatch")
+        return _crc_mismatch(where)
     return ValueError(f"{where}: its row of the block table does not fit the buffers (status {report['status']})")
-
-
-def _slab_groups(blocks, slab_bytes: Optional[int]):
-    """(first, one past the last) block of every slab: the rule of `_inflate_slabs`."""
-    first = 0
-    while first < len(blocks):
-        last, size = first, 0
-        while last < len(blocks) and (slab_bytes is None or size < slab_bytes or last == first):
-            size += blocks[last][4]
-            last += 1
-        while last < len(blocks) and blocks[last][4] == 0:  # (the end-of-file marker and its like go with the slab before)
-            last += 1
-        yield first, last
-        first = last
-
-
-def _device_of(device):
-    import torch
-
-    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
-    return dev if dev.index is not None else torch.device(f"cuda:{_dp._device_index()}")
 
 
 def _inflate_slabs_device(raw: memoryview, name: str, blocks, dev, slab_bytes: Optional[int]):
@@ -289,7 +306,7 @@ def _inflate_slabs_device(raw: memoryview, name: str, blocks, dev, slab_bytes: O
 
     for index, block in enumerate(blocks):
         if block[4] > BGZF_MAX_ISIZE:
-            raise ValueError(f"{name}: BGZF block {index} at file offset {block[0]}: length mismatch (ISIZE says {block[4]}, a BGZF block "
+            raise ValueError(f"{_block_where(name, index, block[0])}: length mismatch (ISIZE says {block[4]}, a BGZF block "
                              f"holds at most {BGZF_MAX_ISIZE} bytes; inflate=\"host\" reads a file that breaks this rule)")
     for first, last in _slab_groups(blocks, slab_bytes):
         group = blocks[first:last]
@@ -304,7 +321,8 @@ def _inflate_slabs_device(raw: memoryview, name: str, blocks, dev, slab_bytes: O
             out = torch.empty(int(table[-1, 2] + table[-1, 4]), dtype=torch.uint8, device=dev)
             _, report = inflate_blocks_device(up[head:], up[:head].view(torch.int64), out)  # (synchronises: `staged` may go)
         if report["block"] >= 0:
-            raise _bgzf_error(name, first + report["block"], group[report["block"]], report)
+            bad = group[report["block"]]
+            raise _bgzf_error(_block_where(name, first + report["block"], bad[0]), bad[4], report)
         yield out
 
 
@@ -319,25 +337,27 @@ def inflate_bgzf_device(source, device=None, slab_bytes: Optional[int] = None):
     With ``slab_bytes``: a generator of such tensors, cut at BGZF block boundaries by the rule of `inflate_bgzf`."""
     import torch
 
-    dev = _device_of(device)
-    if slab_bytes is not None and int(slab_bytes) < 1:
-        raise ValueError("inflate_bgzf_device: slab_bytes must be positive")
-    raw, name = _source_bytes(source)
-    slabs = _inflate_slabs_device(raw, name, _bgzf_blocks(raw, name), dev, None if slab_bytes is None else int(slab_bytes))
-    if slab_bytes is not None:
-        return slabs
-    slabs = list(slabs)
-    return slabs[0] if slabs else torch.empty(0, dtype=torch.uint8, device=dev)
+    dev = _dp._device(device)
+    raw, name, blocks, slab_bytes = _bgzf_front(source, slab_bytes, "inflate_bgzf_device")
+    return _whole_or_slabs(_inflate_slabs_device(raw, name, blocks, dev, slab_bytes), slab_bytes,
+                           lambda: torch.empty(0, dtype=torch.uint8, device=dev))
 
 
-class _Inline:
-    """A pool of the calling thread (for `_inflate_group` over a block or two)."""
-    map = staticmethod(map)
+def _uploaded(slabs, dev):
+    """Host slabs as device tensors, each uploaded asynchronously from its pinned array."""
+    import torch
+
+    for slab in slabs:
+        up = torch.from_numpy(slab).to(dev, non_blocking=True)
+        copied = torch.cuda.current_stream(dev).record_event()
+        yield up
+        copied.synchronize()  # (the pinned `slab` outlives its upload: it stays bound here until the copy has run)
 
 
 def _header_from_leading_blocks(raw: memoryview, name: str, blocks):
-    """(contigs, the offset of the first record) from a host inflate of as many leading blocks as the header covers."""
-    head, k = np.empty(0, dtype=np.uint8), 0
+    """(contigs, the offset of the first record) from a host inflate, into ordinary memory, of as many leading blocks as the
+    header covers."""
+    head, k = b"", 0
     while True:
         try:
             _, contigs, entry0 = parse_bam_header(head)
@@ -347,7 +367,7 @@ def _header_from_leading_blocks(raw: memoryview, name: str, blocks):
                 raise ValueError(f"{name}: {exc}") from None
         except ValueError as exc:
             raise ValueError(f"{name}: {exc}") from None
-        head = np.concatenate([head, _inflate_group(raw, blocks[k: k + 1], k, name, _Inline)])
+        head += _inflate_block(raw, name, k, blocks[k])
         k += 1
 
 
@@ -444,8 +464,8 @@ def walk_records_device(bytes_t, entry0: int, n_ref: int, segment_bytes: Optiona
     return offsets[: report["records"]], report
 
 
-_FIELD_DTYPES = (("tid", "int32"), ("pos", "int32"), ("end", "int32"), ("isize", "int32"), ("flag", "int16"), ("mapq", "uint8"),
-                 ("mate_same", "uint8"), ("qlen", "int32"))
+# the arrays `rocco_hip_bam_record_fields` writes, in its order, with the names of their torch dtypes
+_FIELD_DTYPES = tuple((name, _rt._tensor_dtype(name, dtype)) for name, dtype in (("tid", np.int32),) + _rt._RECORD_FIELDS + (_rt._QLEN_FIELD,))
 
 
 def record_fields_device(bytes_t, offsets_t, n_ref: int):
@@ -485,68 +505,44 @@ def decode_records_device(bytes_t, entry0: int, n_ref: int, segment_bytes: Optio
 def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT_SLAB_BYTES, segment_bytes: Optional[int] = None,
                         threads: Optional[int] = None, guess_mode: int = 1, report: Optional[dict] = None, inflate: str = "host"):
     """A whole BAM file as (`AlignmentFileRecords` whose records carry ``qlen`` and are CUDA tensors, ``name`` the path; the
-    number of records without a contig).  Slab by slab: `inflate_bgzf` yields about ``slab_bytes`` inflated bytes, they are
-    uploaded, walked and decoded on the device; a slab's bytes behind its last complete record are carried in front of the
-    next slab; the per-contig arrays are views of the seven concatenated arrays.  ``names``: keep these contigs only.
-    ``report`` (a dict) receives the walk's totals.
-
-    ``inflate="device"``: the slabs come from `inflate_bgzf_device` and are inflated where they are consumed; the carry is a
-    device tensor and the inflated bytes never visit the host.  The header alone is read on the host, from an inflate of the
-    leading blocks it covers.  The decoded arrays are the same in both modes."""
+    number of records without a contig).  The file is read and its block headers are walked once; the header comes first, from
+    a host inflate of the leading blocks it covers (so a file with a bad header reports the header, whatever else is wrong
+    with it).  Then slab by slab: about ``slab_bytes`` inflated bytes arrive as a uint8 tensor on the device -- inflated on the
+    host and uploaded (``inflate="host"``, on ``threads`` threads) or inflated where they are consumed (``inflate="device"``:
+    the inflated bytes never visit the host) -- and are walked and decoded there; a slab's bytes behind its last complete
+    record are carried, on the device, in front of the next slab; the per-contig arrays are views of the seven concatenated
+    arrays.  ``names``: keep these contigs only.  ``report`` (a dict) receives the walk's totals.  The decoded arrays are the
+    same in both modes."""
     import torch
 
     path = os.fspath(path)
     if inflate not in ("host", "device"):
         raise ValueError(f"read_alignment_file: inflate must be \"host\" or \"device\", not {inflate!r}")
-    on_device = inflate == "device"
-    dev = _device_of(device)
-    contigs, n_ref = None, 0
-    if on_device:
-        raw, _ = _source_bytes(path)
-        blocks = _bgzf_blocks(raw, path)
-        header = _header_from_leading_blocks(raw, path, blocks)
-        slabs = _inflate_slabs_device(raw, path, blocks, dev, max(1, int(slab_bytes)))
-        empty, join = torch.empty(0, dtype=torch.uint8, device=dev), torch.cat
+    dev = _dp._device(device)
+    raw, _, blocks, slab_bytes = _bgzf_front(path, max(1, int(slab_bytes)), "read_alignment_file")
+    contigs, entry0 = _header_from_leading_blocks(raw, path, blocks)
+    if inflate == "device":
+        slabs = _inflate_slabs_device(raw, path, blocks, dev, slab_bytes)
     else:
-        slabs = inflate_bgzf(path, threads=threads, slab_bytes=max(1, int(slab_bytes)))
-        empty, join = np.empty(0, dtype=np.uint8), np.concatenate
-    carry = empty
-    parts, counts, last_key, n_records, consumed = [], None, -1, 0, 0
+        slabs = _uploaded(_inflate_slabs(raw, path, blocks, threads, slab_bytes), dev)
+    n_ref = len(contigs)
+    carry = empty = torch.empty(0, dtype=torch.uint8, device=dev)  # (what the walk has not consumed yet, in front of the next slab)
+    parts, counts, last_key, n_records, consumed = [], np.zeros(n_ref + 1, dtype=np.int64), -1, 0, 0
     totals = {"records": 0, "segments": 0, "wrong_guesses": 0, "repair_rounds": 0, "slabs": 0}
-    pending = None
 
-    def with_last(it):
-        previous = None
+    def with_last(it):  # (the header needs a block, so there is a slab)
+        previous = next(it)
         for item in it:
-            if previous is not None:
-                yield previous, False
+            yield previous, False
             previous = item
-        yield (previous if previous is not None else empty), True
+        yield previous, True
 
     for slab, is_last in with_last(slabs):
-        data = join([carry, slab]) if carry.shape[0] else slab
-        entry0 = 0
-        if contigs is None and on_device:
-            if data.shape[0] < header[1] and not is_last:  # (the header straddles slabs)
-                carry = data
-                continue
-            contigs, entry0 = header
-            n_ref = len(contigs)
-            counts = np.zeros(n_ref + 1, dtype=np.int64)
-        elif contigs is None:
-            try:
-                _, contigs, entry0 = parse_bam_header(data)
-            except _HeaderCutShort as exc:
-                if is_last:
-                    raise ValueError(f"{path}: {exc}") from None
-                carry = data
-                continue
-            except ValueError as exc:
-                raise ValueError(f"{path}: {exc}") from None
-            n_ref = len(contigs)
-            counts = np.zeros(n_ref + 1, dtype=np.int64)
-        bytes_t = data if on_device else torch.from_numpy(data).to(dev, non_blocking=True)
-        fields, firsts, rep = decode_records_device(bytes_t, entry0, n_ref, segment_bytes, guess_mode, path, whole=is_last,
+        data = torch.cat([carry, slab]) if carry.shape[0] else slab
+        if data.shape[0] < entry0 and not is_last:  # (the header straddles slabs)
+            carry = data
+            continue
+        fields, firsts, rep = decode_records_device(data, entry0, n_ref, segment_bytes, guess_mode, path, whole=is_last,
                                                     first_record=n_records, first_byte=consumed)
         slab_counts = np.diff(np.asarray(firsts, dtype=np.int64))
         present = np.flatnonzero(slab_counts)
@@ -560,15 +556,9 @@ def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT
         for key in ("records", "segments", "wrong_guesses", "repair_rounds"):
             totals[key] += rep[key]
         totals["slabs"] += 1
-        if rep["end_offset"] < data.shape[0]:
-            carry = data[rep["end_offset"]:].clone() if on_device else data[rep["end_offset"]:].copy()
-        else:
-            carry = empty
+        carry = data[rep["end_offset"]:].clone() if rep["end_offset"] < data.shape[0] else empty
         consumed += rep["end_offset"]
-        pending = bytes_t  # (the upload's source `data` lives until the next slab's synchronising call has returned)
-    del pending
-    if contigs is None:
-        raise ValueError(f"{path}: BAM header: the file is empty")
+        entry0 = 0
     if report is not None:
         report.update(totals)
     whole = {name: (torch.cat([p[name] for p in parts]) if len(parts) > 1 else parts[0][name]) for name, _ in _FIELD_DTYPES}
@@ -579,10 +569,8 @@ def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT
         if keep is not None and contig not in keep:
             continue
         lo, hi = int(firsts[k]), int(firsts[k + 1])
-        r = object.__new__(AlignmentRecords)  # (the kernel checked every value: no second pass over the arrays)
-        for field in ("pos", "end", "isize", "flag", "mapq", "mate_same", "qlen"):
-            setattr(r, field, whole[field][lo:hi])
-        records[contig] = r
+        # (the kernel checked every value: no second pass over the arrays)
+        records[contig] = AlignmentRecords._of(*[whole[field][lo:hi] for field in AlignmentRecords.__slots__])
     return AlignmentFileRecords(contigs, records, name=path), int(counts[n_ref])
 
 

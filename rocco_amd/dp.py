@@ -49,6 +49,11 @@ def _device_index(device=None) -> int:
     return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
+def _device(device=None):
+    """The CUDA device ``device`` names as a ``torch.device`` that always has an index: the current one where it names none."""
+    return _torch().device(f"cuda:{_device_index(device)}")
+
+
 def _is_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 

@@ -39,7 +39,7 @@ def assemble_chrom_matrix_device(interval_matrix: Sequence, vals_matrix: Sequenc
     K = len(interval_matrix)
     if K == 0:
         raise ValueError("no tracks")
-    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
+    dev = _dp._device(device)
 
     def to_dev(a, dtype):
         if _dp._is_tensor(a):
@@ -101,7 +101,7 @@ def bigwig_dense_fill_device(starts, ends, vals, const_scale: float = 1.0, round
     import torch
 
     _native.load()
-    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
+    dev = _dp._device(device)
 
     def to_dev(a, dtype, np_dtype):
         if _dp._is_tensor(a):
@@ -149,6 +149,12 @@ POSITION_LIMIT = 1 << 31          # the BAM format's own limit on a position
 EXACT_COUNT_LIMIT = 1 << 24       # float32 holds every integer up to here: the reference's float sums are exact below it
 _RECORD_FIELDS = (("pos", np.int32), ("end", np.int32), ("isize", np.int32), ("flag", np.uint16), ("mapq", np.uint8),
                   ("mate_same", np.uint8))
+_QLEN_FIELD = ("qlen", np.int32)  # the optional seventh array of `AlignmentRecords`
+
+
+def _tensor_dtype(name: str, dtype) -> str:
+    """The torch dtype (by name) of a record field: its own, ``flag`` as the int16 bit pattern (torch has few operators for uint16)."""
+    return "int16" if name == "flag" else np.dtype(dtype).name
 
 
 class CountOptions(ctypes.Structure):
@@ -176,13 +182,16 @@ class AlignmentRecords:
     rocco/native/ccounts_backend.c:812-816 and 1046-1050.  Only the whole-file probes (DESIGN.md section 0 row f7) read it;
     it is ``None`` unless given."""
 
-    __slots__ = tuple(name for name, _ in _RECORD_FIELDS) + ("qlen",)
+    __slots__ = tuple(name for name, _ in _RECORD_FIELDS + (_QLEN_FIELD,))
 
     def __init__(self, pos, end, isize, flag, mapq, mate_same, *, qlen=None):
-        given = dict(pos=pos, end=end, isize=isize, flag=flag, mapq=mapq, mate_same=mate_same)
+        given = dict(pos=pos, end=end, isize=isize, flag=flag, mapq=mapq, mate_same=mate_same, qlen=qlen)
         length = None
-        for name, dtype in _RECORD_FIELDS:
+        for name, dtype in _RECORD_FIELDS + (_QLEN_FIELD,):
             a = given[name]
+            if a is None and name == "qlen":
+                self.qlen = None
+                continue
             if _dp._is_tensor(a):
                 kind = str(a.dtype).replace("torch.", "")
                 if (kind != np.dtype(dtype).name and not (name == "flag" and kind == "int16")) or a.dim() != 1:
@@ -217,24 +226,17 @@ class AlignmentRecords:
             elif n != length:
                 raise ValueError(f"AlignmentRecords: `{name}` has {n} entries, `pos` has {length}")
             setattr(self, name, a)
-        self.qlen = None
-        if qlen is not None:
-            if _dp._is_tensor(qlen):
-                if str(qlen.dtype) != "torch.int32" or qlen.dim() != 1:
-                    raise TypeError("AlignmentRecords: `qlen` must be a one-dimensional int32 tensor")
-                qlen = qlen.contiguous()
-            else:
-                qlen = np.asarray(qlen)
-                if qlen.ndim != 1:
-                    raise ValueError("AlignmentRecords: `qlen` must be one-dimensional")
-                if qlen.dtype.kind not in "iu":
-                    raise TypeError(f"AlignmentRecords: `qlen` must hold integers, not {qlen.dtype}")
-                if qlen.size and (int(qlen.min()) < np.iinfo(np.int32).min or int(qlen.max()) > np.iinfo(np.int32).max):
-                    raise ValueError("AlignmentRecords: `qlen` does not fit int32")
-                qlen = np.ascontiguousarray(qlen, dtype=np.int32)
-            if int(qlen.shape[0]) != length:
-                raise ValueError(f"AlignmentRecords: `qlen` has {int(qlen.shape[0])} entries, `pos` has {length}")
-            self.qlen = qlen
+
+    @classmethod
+    def _of(cls, pos, end, isize, flag, mapq, mate_same, qlen=None) -> "AlignmentRecords":
+        """Unchecked: for arrays that come from checked records or from the decoding kernel (no second pass over them)."""
+        out = object.__new__(cls)
+        out.pos, out.end, out.isize, out.flag, out.mapq, out.mate_same, out.qlen = pos, end, isize, flag, mapq, mate_same, qlen
+        return out
+
+    def _arrays(self) -> list:
+        """The seven arrays in the order `_of` takes them (``qlen`` may be None)."""
+        return [getattr(self, name) for name in self.__slots__]
 
     @classmethod
     def from_numpy(cls, pos, end, isize, flag, mapq, mate_same) -> "AlignmentRecords":
@@ -250,18 +252,15 @@ class AlignmentRecords:
 
     def to(self, device) -> "AlignmentRecords":
         """The same records with every array on ``device``."""
-        import torch
+        return AlignmentRecords._of(*[None if a is None else _as_tensor(name, a).to(device)
+                                      for name, a in zip(self.__slots__, self._arrays())])
 
-        out = object.__new__(AlignmentRecords)
-        for name, _ in _RECORD_FIELDS:
-            a = getattr(self, name)
-            if not _dp._is_tensor(a):
-                a = torch.from_numpy(a.view(np.int16) if name == "flag" else a)
-            setattr(out, name, a.to(device))
-        out.qlen = None
-        if self.qlen is not None:
-            out.qlen = (self.qlen if _dp._is_tensor(self.qlen) else torch.from_numpy(self.qlen)).to(device)
-        return out
+
+def _as_tensor(name: str, a):
+    """A record array as a tensor where it lies (a host ``flag`` as its int16 bit pattern)."""
+    import torch
+
+    return a if _dp._is_tensor(a) else torch.from_numpy(a.view(np.int16) if name == "flag" else a)
 
 
 def _compute_native_scale_factor(norm_method: str, effective_genome_size: float, step: int, mapped_reads: int,
@@ -316,17 +315,12 @@ def _records_on_device(records_list: Sequence[AlignmentRecords], dev) -> Tuple[A
         offsets.append(offsets[-1] + len(records))
     if len(records_list) == 1:
         return records_list[0].to(dev), offsets
-    out = object.__new__(AlignmentRecords)
-    for name, dtype in _RECORD_FIELDS:
-        buf = torch.empty(offsets[-1], dtype=torch.int16 if name == "flag" else getattr(torch, np.dtype(dtype).name), device=dev)
+    bufs = []
+    for name, dtype in _RECORD_FIELDS:  # (`qlen` is not carried along: no entry point over several tracks reads it)
+        bufs.append(torch.empty(offsets[-1], dtype=getattr(torch, _tensor_dtype(name, dtype)), device=dev))
         for k, records in enumerate(records_list):
-            a = getattr(records, name)
-            if not _dp._is_tensor(a):
-                a = torch.from_numpy(a.view(np.int16) if name == "flag" else a)
-            buf[offsets[k]: offsets[k + 1]].copy_(a)
-        setattr(out, name, buf)
-    out.qlen = None
-    return out, offsets
+            bufs[-1][offsets[k]: offsets[k + 1]].copy_(_as_tensor(name, getattr(records, name)))
+    return AlignmentRecords._of(*bufs), offsets
 
 
 def _record_args(records_list, cat=None, offsets=None, dev=None):
@@ -339,11 +333,7 @@ def _record_args(records_list, cat=None, offsets=None, dev=None):
 
 
 def _records_slice(records: AlignmentRecords, lo: int, hi: int) -> AlignmentRecords:
-    out = object.__new__(AlignmentRecords)
-    for name, _ in _RECORD_FIELDS:
-        setattr(out, name, getattr(records, name)[lo:hi])
-    out.qlen = None if records.qlen is None else records.qlen[lo:hi]
-    return out
+    return AlignmentRecords._of(*[None if a is None else a[lo:hi] for a in records._arrays()])
 
 
 def _count_concatenated(cat: AlignmentRecords, offsets: Sequence[int], regions: Sequence, options_list: Sequence,
@@ -397,13 +387,10 @@ def count_alignment_records_batch_device(records_list: Sequence[AlignmentRecords
     (``lengths[k]`` bins where given: the reference's countBufferLength).  ``into``: float32 CUDA tensors that stand for
     the reference's used count buffer: the returned tensors hold their values plus the counts (one float addition per
     bin); the tensors given are read, not changed.  Raises RuntimeError beyond 2**24."""
-    import torch
-
     K = len(records_list)
     if K == 0 or len(regions) != K or len(options_list) != K:
         raise ValueError("one region and one set of options per track are required")
-    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
-    cat, offsets = _records_on_device(records_list, dev)
+    cat, offsets = _records_on_device(records_list, _dp._device(device))
     views, maxima = _count_concatenated(cat, offsets, regions, options_list, lengths, into)
     _check_exact_counts(maxima)
     return views
@@ -424,13 +411,8 @@ def count_alignment_region_from_records(records: AlignmentRecords, start: int, e
 def alignment_chrom_range_from_records(records: AlignmentRecords, chrom_size: int, flag_exclude: int = 0) -> Tuple[int, int]:
     """``ccounts_getChromRange`` (rocco/native/ccounts_backend.c:1666-1705): (pos of the first record ``flag_exclude``
     passes, end of the LAST one in file order among the records reaching into the contig's last 2 Mb); 0 where none."""
-    import torch
-
     lib = _native.load()
-    if _dp._is_tensor(records.pos):
-        dev = records.pos.device
-    else:
-        dev = torch.device(f"cuda:{_dp._device_index()}")
+    dev = _device_for([records])
     r = records.to(dev)
     start, end = ctypes.c_longlong(0), ctypes.c_longlong(0)
     _native.check(lib.rocco_hip_alignment_chrom_range(
@@ -491,10 +473,7 @@ def bam_chrom_reads_from_records_batch(records_list: Sequence[AlignmentRecords],
     intervals_out, vals_out = [None] * K, [None] * K
     if K == 0:
         return intervals_out, vals_out
-    import torch
-
-    given = next((r.pos.device for r in records_list if _dp._is_tensor(r.pos)), None)
-    cat, offsets = _records_on_device(records_list, given if given is not None else torch.device(f"cuda:{_dp._device_index()}"))
+    cat, offsets = _records_on_device(records_list, _device_for(records_list))
     live, regions, options = [], [], []
     for k, metadata in enumerate(metadata_list):
         chrom_start, chrom_end = alignment_chrom_range_from_records(_records_slice(cat, offsets[k], offsets[k + 1]), chrom_size,
@@ -586,7 +565,7 @@ def count_alignment_intervals_batch_device(records_by_file: Sequence[dict], chro
         for contig in contigs:
             if contig not in records:
                 raise ValueError("chromosome not found in alignment header")
-    dev = torch.device(device) if device is not None else torch.device(f"cuda:{_dp._device_index()}")
+    dev = _dp._device(device)
     if P == 0:
         return torch.zeros((0, F), dtype=torch.int32, device=dev)
     C = len(contigs)
@@ -738,10 +717,9 @@ def alignment_read_length_from_records(file, min_reads: int = 32, max_iterations
 
 
 def _device_for(tracks):
-    import torch
-
+    """The device the first track on a device names, else the current one."""
     given = next((r.pos.device for r in tracks if _dp._is_tensor(r.pos)), None)
-    return given if given is not None else torch.device(f"cuda:{_dp._device_index()}")
+    return given if given is not None else _dp._device()
 
 
 def record_flag_facts_device(records_list: Sequence[AlignmentRecords], cat=None, offsets=None) -> Tuple[list, list]:

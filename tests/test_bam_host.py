@@ -173,3 +173,30 @@ def test_header_constants_agree_with_the_c_header():
     assert int(defined["ROCCO_BAM_GUESS_DEPTH"]) == bx.GUESS_DEPTH and int(defined["ROCCO_BAM_SEGMENT_BYTES"]) == bx.DEFAULT_SEGMENT_BYTES
     for name in ("BLOCK_SIZE", "TRUNCATED", "SIZES", "READ_NAME", "REF_ID", "CIGAR_SEQ", "POSITION", "END", "CG_TAG", "ORDER", "OFFSET"):
         assert int(defined[f"ROCCO_BAM_ERR_{name}"]) == getattr(bx, f"ERR_{name}")
+
+
+def test_one_slab_rule():
+    """`_slab_groups`, the one statement of where slabs are cut: every block once and in order, every group but the last at least
+    ``slab_bytes`` inflated bytes, and `inflate_bgzf` yields one slab of each group's inflated size."""
+    from rocco_amd import bam
+
+    want, _ = bx.inflate(bx.bam_bytes("blocks"))
+    empty = bx.bgzf_block(b"")
+    middle = bx.bgzf_compress(want[:3000], cuts=(700, 1400), eof=False) + empty + empty + bx.bgzf_compress(want[3000:9000], cuts=(5000,))
+    for raw in (bx.bam_bytes("blocks"), middle):
+        blocks = bam._bgzf_blocks(memoryview(raw), "<bytes>")
+        sizes = [b[4] for b in blocks]
+        for slab_bytes in (None, 1, 1000, 70000):
+            groups = list(bam._slab_groups(blocks, slab_bytes))
+            assert [k for first, last in groups for k in range(first, last)] == list(range(len(blocks)))
+            assert all(last > first for first, last in groups)
+            inflated = [sum(sizes[first:last]) for first, last in groups]
+            if slab_bytes is None:
+                assert len(groups) == 1
+                slabs = [bam.inflate_bgzf(raw)]
+            else:
+                assert all(n >= slab_bytes for n in inflated[:-1])
+                slabs = list(bam.inflate_bgzf(raw, slab_bytes=slab_bytes))
+            assert [int(s.size) for s in slabs] == inflated
+    groups = list(bam._slab_groups(bam._bgzf_blocks(memoryview(middle), "<bytes>"), 1))
+    assert (2, 5) in groups and groups[-1][1] - groups[-1][0] == 2  # (the empty blocks and the end-of-file marker go with the slab before)

@@ -150,6 +150,32 @@ def test_records_carry_an_optional_query_length():
     assert rt._records_slice(with_length, 1, 2).qlen.tolist() == [50] and rt._records_slice(plain, 0, 1).qlen is None
 
 
+def test_unchecked_constructor_round_trips_and_keeps_the_query_length():
+    six = (np.array([1, 5, 9]), np.array([51, 55, 59]), np.array([0, 0, 0]), np.array([0, 16, 0]), np.array([30, 30, 0]), np.array([0, 0, 1]))
+    checked = AlignmentRecords.with_query_length(*six, np.array([50, 36, 20]))
+    names = ("pos", "end", "isize", "flag", "mapq", "mate_same", "qlen")
+    made = AlignmentRecords._of(*[getattr(checked, name) for name in names])
+    assert type(made) is AlignmentRecords and len(made) == 3 and all(getattr(made, name) is getattr(checked, name) for name in names)
+    part = rt._records_slice(made, 1, 3)
+    for name in names:
+        got, want = getattr(part, name), getattr(checked, name)[1:3]
+        assert got.dtype == want.dtype and got.tolist() == want.tolist(), name
+    assert part.qlen.tolist() == [36, 20]
+    assert AlignmentRecords._of(*[getattr(checked, name) for name in names[:6]]).qlen is None
+
+
+def test_query_length_errors_word_for_word():
+    six = (np.array([1, 5]), np.array([51, 55]), np.array([0, 0]), np.array([0, 16]), np.array([30, 30]), np.array([0, 0]))
+    for bad, error, text in ((np.array([[50, 50]]), ValueError, "AlignmentRecords: `qlen` must be one-dimensional"),
+                             (np.array([50.0, 50.0]), TypeError, "AlignmentRecords: `qlen` must hold integers, not float64"),
+                             (np.array([50, 2 ** 31]), ValueError, "AlignmentRecords: `qlen` does not fit int32"),
+                             (np.array([50, -2 ** 31 - 1]), ValueError, "AlignmentRecords: `qlen` does not fit int32"),
+                             (np.array([50, 50, 50]), ValueError, "AlignmentRecords: `qlen` has 3 entries, `pos` has 2")):
+        with pytest.raises(error) as info:
+            AlignmentRecords(*six, qlen=bad)
+        assert str(info.value) == text
+
+
 def test_probes_name_a_missing_query_length():
     six = (np.array([1, 5]), np.array([51, 55]), np.array([0, 0]), np.array([0, 16]), np.array([30, 30]), np.array([0, 0]))
     file = AlignmentFileRecords([("chrA", 10000)], {"chrA": AlignmentRecords(*six)}, name="sample.bam")

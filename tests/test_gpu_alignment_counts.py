@@ -301,3 +301,19 @@ def test_device_tensors_in(gpu, gold):
     assert got.cpu().numpy().tobytes() == arrays["c_big_paired_counts"].tobytes()
     with pytest.raises(TypeError, match="int32 tensor"):
         AlignmentRecords(tensors[0].to(torch.int64), *tensors[1:])
+
+
+def test_a_device_named_without_an_index(gpu):
+    """``device="cuda"`` names the current device: the same counts as with the indexed device."""
+    import torch
+
+    from rocco_amd.readtracks import AlignmentRecords, count_alignment_records_batch_device
+
+    pos = np.arange(12, dtype=np.int64) * 37 + 5
+    records = AlignmentRecords(pos, pos + 50, np.zeros(12, dtype=np.int64), np.where(np.arange(12) % 2, 16, 0), np.full(12, 30), np.zeros(12, dtype=np.int64))
+    region, options = [(0, 600, 25)], [dict(read_length=50)]
+    with torch.cuda.device(gpu):
+        (loose,) = count_alignment_records_batch_device([records], region, options, device="cuda")
+    (indexed,) = count_alignment_records_batch_device([records], region, options, device=gpu)
+    assert loose.device == indexed.device == gpu and loose.shape[0] == 24 and float(indexed.sum()) > 0
+    assert torch.equal(loose, indexed)

@@ -196,6 +196,41 @@ def test_corrupt_bam_files_raise_the_same_text(gpu, tmp_path):
             bam.read_alignment_file(path, device=gpu, inflate=mode)
 
 
+def test_doubly_corrupt_bam_files_read_the_same_in_both_modes(gpu, tmp_path):
+    """The header is read first in both modes: a file that is broken in its header and in a later block reports the header
+    whatever the slab size, and a block under the header reports that block."""
+    from rocco_amd import bam
+
+    data, _ = bx.inflate(bx.bam_bytes("mixed"))
+    _, contigs, entry0 = bx.header(data)
+    cuts = range(2000, len(data), 2000)
+    sizes = [len(bx.bgzf_block(data[at: at + 2000])) for at in range(0, len(data), 2000)]
+    assert len(sizes) >= 3 and entry0 > 100  # (the header spans three 50-byte blocks)
+
+    def flipped(raw, sizes, block, trailer_byte):
+        out = bytearray(raw)
+        out[sum(sizes[: block + 1]) + trailer_byte] ^= 1  # (-8: the low byte of CRC32, -4: of ISIZE)
+        return bytes(out)
+
+    bad_magic = b"BAM\x02" + data[4:]
+    bad_n_ref = bytearray(data)
+    struct.pack_into("<i", bad_n_ref, entry0 - sum(8 + len(name) + 1 for name, _ in contigs) - 4, -3)
+    small = [len(bx.bgzf_block(data[at: at + 50])) for at in range(0, len(data), 50)]
+    variants = {"a": (flipped(bx.bgzf_compress(bad_magic, cuts=cuts), sizes, 1, -8), "BAM header: the magic"),
+                "b": (flipped(bx.bgzf_compress(bytes(bad_n_ref), cuts=cuts), sizes, len(sizes) - 1, -4), "BAM header: n_ref is negative (-3)"),
+                "c": (flipped(bx.bgzf_compress(data, cuts=range(50, len(data), 50)), small, 1, -8),
+                      f"BGZF block 1 at file offset {small[0]}: CRC32 mismatch")}
+    path = str(tmp_path / "bad.bam")
+    for label, (raw, words) in variants.items():
+        with open(path, "wb") as handle:
+            handle.write(raw)
+        for how in ({}, {"slab_bytes": 6000}, {"slab_bytes": 1}):
+            assert read_both(gpu, path, **how) is None, (label, how)
+            with pytest.raises(ValueError) as info:
+                bam.read_alignment_file(path, device=gpu, **how)
+            assert words in str(info.value), (label, how)
+
+
 def test_default_inflate_device_serves_the_reference_results(gpu, tmp_path, monkeypatch):
     """With DEFAULT_INFLATE = "device" and an empty cache, `get_bam_chrom_reads` on `mixed` and `blocks` returns what the
     reference returned for them (the golden results of test_gpu_bam_reader.py)."""

@@ -15,12 +15,18 @@ Timed with HIP events around each entry point (the bytes in HBM before; every en
 synchronise), one warm-up + `reps` repetitions, the median; bytes per second are the stream's bytes over that time.
   inflate   rocco_amd.bam.inflate_bgzf (wall clock, its default thread pool) over the same stream compressed by Python's
             zlib at level 1 into 65 280-byte BGZF blocks; `--inflate-records` bounds its share of the stream.
-No speed bar: the parent commit reads no BAM file, and the reference's htslib does not travel to the GPU machine."""
+  reader    rocco_amd.bam.read_alignment_file (wall clock between two device synchronisations) over a temporary file: a BAM
+            header for the 25 contigs in front of the whole stream, compressed as above; in both inflate modes, at the default
+            slab size and at 32 MiB slabs (many carries and joins).  It uses public names only, so `--legs reader` times the
+            package of any commit that has the reader: the bar for a change to the reader is, per line, a median no more than
+            the earlier commit's median times (1 + its own (max - min) / median).
+No speed bar for the kernels: the reference's htslib does not travel to the GPU machine."""
 import argparse
 import os
 import statistics
 import struct
 import sys
+import tempfile
 import time
 import zlib
 from concurrent.futures import ThreadPoolExecutor
@@ -71,13 +77,42 @@ def timed(torch, call, reps):
     return statistics.median(times), min(times), max(times), result
 
 
+def reader_leg(torch, bam, stream, records, threads, reps):
+    header = b"BAM\1" + struct.pack("<ii", 0, N_REF) + b"".join(
+        struct.pack("<i", len(name) + 1) + name + b"\0" + struct.pack("<i", 1 << 30) for name in (b"chr%d" % k for k in range(N_REF)))
+    with tempfile.TemporaryDirectory() as folder:
+        path = os.path.join(folder, "bench.bam")
+        with open(path, "wb") as handle:
+            handle.write(bgzf(np.concatenate([np.frombuffer(header, dtype=np.uint8), stream]), threads))
+            handle.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
+        print(f"reader: {os.path.getsize(path)} compressed bytes, {len(header) + stream.size} inflated, {records} records")
+        for mode in ("host", "device"):
+            for slab_bytes in (None, 32 << 20):
+                how = {} if slab_bytes is None else {"slab_bytes": slab_bytes}
+                times = []
+                for rep in range(reps + 1):  # one warm-up
+                    torch.cuda.synchronize()
+                    begin = time.perf_counter()
+                    file, unplaced = bam.read_alignment_file(path, inflate=mode, **how)
+                    torch.cuda.synchronize()
+                    if rep >= 1:
+                        times.append(time.perf_counter() - begin)
+                    assert len(file.records["chr0"]) == records and unplaced == 0
+                    del file
+                med = statistics.median(times)
+                print(f"reader inflate={mode} slab_bytes={'default' if slab_bytes is None else slab_bytes}: median {med * 1e3:.1f} ms "
+                      f"(min {min(times) * 1e3:.1f}, max {max(times) * 1e3:.1f}) = {stream.size / med / 1e9:.2f} GB/s of inflated bytes")
+
+
 def main():
     parser = argparse.ArgumentParser()
+    parser.add_argument("--legs", default="kernels,reader", help="of kernels (walk, fields, inflate) and reader")
     parser.add_argument("--records", type=int, default=20_000_000)
     parser.add_argument("--inflate-records", type=int, default=4_000_000)
     parser.add_argument("--wrong-guess-records", type=int, default=1_000_000)
     parser.add_argument("--reps", type=int, default=5)
     args = parser.parse_args()
+    legs = set(args.legs.split(","))
     import torch
 
     from rocco_amd import bam
@@ -88,6 +123,10 @@ def main():
     records, n_bytes = repeats * 4096, int(stream.size)
     print(f"device {torch.cuda.get_device_name(0)}; {records} records, {n_bytes} inflated bytes ({n_bytes / records:.1f} per record), "
           f"segment {bam.DEFAULT_SEGMENT_BYTES} bytes, guess depth {bam.GUESS_DEPTH}, {args.reps} repetitions after one warm-up")
+    if "reader" in legs:
+        reader_leg(torch, bam, stream, records, max(1, min(16, len(os.sched_getaffinity(0)))), args.reps)
+    if "kernels" not in legs:
+        return
     bytes_t = torch.from_numpy(stream).to("cuda:0")
     head = bytes_t[: min(repeats, max(args.wrong_guess_records // 4096, 1)) * len(block)]
     for mode, label, data in ((1, "walk", bytes_t), (0, "walk, every guess wrong (guess_mode 0)", head)):
