@@ -896,6 +896,37 @@ int rocco_hip_bgzf_inflate_host(rocco_hip_solver *solver, const uint8_t *comp, s
                                 uint8_t *out, size_t n_out, int32_t *status_out, int64_t *report_out);
 void rocco_hip_bgzf_shape(int *shape_out);
 
+/* ---- the grid caps of the record and select kernels -----------------------------------------------------------------
+ * Every kernel behind the data front end caps its grid; past cap x unit a workgroup takes several units in turn (a grid
+ * stride).  The caps are stated here once, the .hip files are built to them, and rocco_hip_launch_caps hands them to the
+ * tests, which size themselves from them to reach a second turn (tests/test_gpu_launch_turns.py).  A "unit" is what one
+ * workgroup takes per turn.
+ *
+ * The select (select.hip) has no fixed cap: a counting pass has about ROCCO_SELECT_GRID_TARGET workgroups for a group of
+ * up to 48 vectors, dealt to the vectors by length.  Vector v of n_v values has chunks = ceil(n_v / ROCCO_SELECT_CHUNK_VALUES)
+ * and gets
+ *     blocks = min(chunks, floor(ROCCO_SELECT_GRID_TARGET * n_v / group_total) + 1)      (the product and quotient in double)
+ * workgroups, group_total = the sum of the group's n_v; workgroup j of the vector counts its chunks j, j + blocks, ... into
+ * ONE LDS histogram.  A vector is in its second turn when blocks < chunks. */
+#define ROCCO_SELECT_GRID_TARGET 1024      /* unit: one chunk of ROCCO_SELECT_CHUNK_VALUES values of one vector (select_count_kernel) */
+#define ROCCO_SELECT_CHUNK_VALUES 16384    /* values of a chunk */
+#define ROCCO_SELECT_THREADS 256           /* threads of a counting workgroup */
+#define ROCCO_BH_MAX_GRID 2048             /* unit: ROCCO_BH_THREADS sorted p-values (bh_last_passing_kernel) */
+#define ROCCO_BH_THREADS 256
+#define ROCCO_COUNT_THREADS 256            /* threads per workgroup of count.hip's kernels */
+#define ROCCO_CHROM_RANGE_MAX_GRID 2048    /* unit: ROCCO_COUNT_THREADS records (chrom_range_kernel) */
+#define ROCCO_COUNT_TAIL_MAX_GRID 4096     /* unit: ROCCO_COUNT_THREADS bins (count_tail_kernel) */
+#define ROCCO_COUNT_INTERVALS_THREADS 256  /* threads per workgroup of interval_count.hip's kernels */
+#define ROCCO_INTERVAL_FACTS_MAX_GRID 2048 /* unit: ROCCO_COUNT_INTERVALS_THREADS records (interval_track_facts_kernel) */
+#define ROCCO_FRAGMENT_MAX_GRID 2048       /* unit: ROCCO_FRAGMENT_THREADS records (record_flag_facts_kernel, template_length_kernel); ROCCO_FRAGMENT_DENSITY_RECORDS records (chunk_density_kernel) */
+#define ROCCO_BAM_MAX_GRID 4096            /* unit: one segment (bam_guess_kernel); ROCCO_BAM_THREADS segments (bam_walk_kernel, bam_emit_kernel); ROCCO_BAM_THREADS records (bam_fields_kernel) */
+/* rocco_hip_launch_caps: out[0 .. ROCCO_LAUNCH_CAPS) = ROCCO_SELECT_GRID_TARGET, ROCCO_SELECT_CHUNK_VALUES, ROCCO_SELECT_THREADS,
+ * ROCCO_BH_MAX_GRID, ROCCO_BH_THREADS, ROCCO_CHROM_RANGE_MAX_GRID, ROCCO_COUNT_TAIL_MAX_GRID, ROCCO_COUNT_THREADS,
+ * ROCCO_INTERVAL_FACTS_MAX_GRID, ROCCO_COUNT_INTERVALS_THREADS, ROCCO_FRAGMENT_MAX_GRID, ROCCO_FRAGMENT_THREADS,
+ * ROCCO_FRAGMENT_DENSITY_RECORDS, ROCCO_FRAGMENT_DENSITY_WINDOW, ROCCO_BAM_MAX_GRID, ROCCO_BAM_THREADS. */
+#define ROCCO_LAUNCH_CAPS 16
+void rocco_hip_launch_caps(int *out);
+
 /* ---- synthetic signal matrices (benchmark / test support, device-resident) -------------------
  * Fills a row-major [K][n] matrix with the counter-based synthetic tracks described in
  * DESIGN.md section 7 (5-decimal background + planted peaks with per-sample dropout); the same

@@ -319,10 +319,18 @@ PROTOTYPES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
       ctypes.c_void_p, c_ll_p]),
     ("rocco_hip_bgzf_shape", None, [c_int_p]),
+    # (no reference line: the grid caps of the record and select kernels, for the tests that go past one launch's first turn)
+    ("rocco_hip_launch_caps", None, [c_int_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t,
       ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]),
 ]
+
+# the entries of rocco_hip_launch_caps, in its order (include/rocco_hip.h: ROCCO_LAUNCH_CAPS)
+LAUNCH_CAP_NAMES = (
+    "select_grid_target", "select_chunk_values", "select_threads", "bh_max_grid", "bh_threads", "chrom_range_max_grid",
+    "count_tail_max_grid", "count_threads", "interval_facts_max_grid", "count_intervals_threads", "fragment_max_grid",
+    "fragment_threads", "fragment_density_records", "fragment_density_window", "bam_max_grid", "bam_threads")
 
 class _Library:
     """The loaded library with one policy in front of every status-returning entry point: a device allocation of the
@@ -387,6 +395,14 @@ def load() -> _Library:
         fn.argtypes = argtypes
     _lib = _Library(lib)
     return _lib
+
+
+def launch_caps() -> dict:
+    """`rocco_hip_launch_caps`: the grid caps of the record and select kernels and the threads that go with them; past
+    cap x unit a workgroup takes several units in turn.  No device is touched."""
+    caps = (ctypes.c_int * len(LAUNCH_CAP_NAMES))()
+    load().rocco_hip_launch_caps(caps)
+    return {name: int(value) for name, value in zip(LAUNCH_CAP_NAMES, caps)}
 
 
 def last_error() -> str:

@@ -1706,6 +1706,18 @@ void rocco_hip_bgzf_shape(int *shape_out)
     shape_out[3] = ROCCO_BGZF_STREAM_REASONS;
 }
 
+void rocco_hip_launch_caps(int *out)
+{
+    const int caps[] = {ROCCO_SELECT_GRID_TARGET,      ROCCO_SELECT_CHUNK_VALUES,     ROCCO_SELECT_THREADS,           ROCCO_BH_MAX_GRID,
+                        ROCCO_BH_THREADS,              ROCCO_CHROM_RANGE_MAX_GRID,    ROCCO_COUNT_TAIL_MAX_GRID,      ROCCO_COUNT_THREADS,
+                        ROCCO_INTERVAL_FACTS_MAX_GRID, ROCCO_COUNT_INTERVALS_THREADS, ROCCO_FRAGMENT_MAX_GRID,        ROCCO_FRAGMENT_THREADS,
+                        ROCCO_FRAGMENT_DENSITY_RECORDS, ROCCO_FRAGMENT_DENSITY_WINDOW, ROCCO_BAM_MAX_GRID,            ROCCO_BAM_THREADS};
+    static_assert(sizeof(caps) / sizeof(caps[0]) == ROCCO_LAUNCH_CAPS, "rocco_hip.h states the count");
+    for (int k = 0; k < ROCCO_LAUNCH_CAPS; ++k) {
+        out[k] = caps[k];
+    }
+}
+
 int rocco_hip_synth_matrix(rocco_hip_solver *solver, void *matrix_dev, int dtype, size_t K, size_t n,
                            size_t row_stride, uint64_t seed, void *stream)
 {

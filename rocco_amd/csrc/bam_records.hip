@@ -34,10 +34,10 @@ namespace {
 
 constexpr int kThreads = ROCCO_BAM_THREADS;
 constexpr int kWave = 64;
-constexpr int kMaxGrid = 4096;
+constexpr int kMaxGrid = ROCCO_BAM_MAX_GRID;  // workgroups of a launch at most
 constexpr long long kNone = -1;
 
-static_assert(kThreads == 256 && kBamGuessDepth >= 1, "rocco_hip.h states the shape");
+static_assert(kThreads == 256 && kBamGuessDepth >= 1 && kMaxGrid > 0, "rocco_hip.h states the shape");
 
 unsigned bam_grid_for(long long items, int per_group)
 {

@@ -30,8 +30,10 @@ namespace rocco {
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = ROCCO_COUNT_THREADS;
 constexpr int kRecsPerThread = 2;
+constexpr int kRangeMaxGrid = ROCCO_CHROM_RANGE_MAX_GRID;  // workgroups of chrom_range_kernel at most
+constexpr int kTailMaxGrid = ROCCO_COUNT_TAIL_MAX_GRID;    // workgroups of count_tail_kernel at most
 constexpr int kChunk = kThreads * kRecsPerThread;  // records one workgroup aggregates at a time
 constexpr int kWindow = 1024;                      // bins of the LDS window
 constexpr int kScanItems = 8;
@@ -44,7 +46,7 @@ constexpr int kMaxGrid = ROCCO_COUNT_MAX_GRID;     // workgroups of one counting
 #endif
 
 static_assert(kChunk == ROCCO_COUNT_CHUNK_RECORDS && kScanTile == ROCCO_COUNT_SCAN_TILE && kWindow == ROCCO_COUNT_WINDOW_BINS &&
-                  kMaxGrid > 0,
+                  kMaxGrid > 0 && kThreads == 256 && kRangeMaxGrid > 0 && kTailMaxGrid > 0,
               "rocco_hip.h states the shape");
 
 // chunk_first[k]: the first chunk of track k among all chunks (K + 1 entries).  A workgroup takes chunks blockIdx.x,
@@ -445,7 +447,7 @@ int launch_alignment_chrom_range(const int32_t *pos_dev, const int32_t *end_dev,
     ROCCO_HIP_TRY(hipMemcpyAsync(result, init, sizeof(init), hipMemcpyHostToDevice, stream));
     const long long tail_start = chrom_len > 2000000LL ? chrom_len - 2000000LL : 0;  // tailCushion (:1684)
     const size_t blocks = (n + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(chrom_range_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kThreads), 0, stream,
+    hipLaunchKernelGGL(chrom_range_kernel, dim3((unsigned)(blocks < (size_t)kRangeMaxGrid ? blocks : (size_t)kRangeMaxGrid)), dim3(kThreads), 0, stream,
                        (const int *)pos_dev, (const int *)end_dev, (const unsigned short *)flag_dev, (long long)n,
                        (long long)chrom_len, tail_start, flag_exclude, result);
     hipLaunchKernelGGL(chrom_range_fetch_kernel, dim3(1), dim3(1), 0, stream, (const int *)pos_dev, (const int *)end_dev, result,
@@ -472,7 +474,7 @@ int launch_alignment_count_tail(const float *counts_dev, size_t n, double norm_s
     const unsigned long long init[2] = {~0ULL, 0ULL};
     ROCCO_HIP_TRY(hipMemcpyAsync(support, init, sizeof(init), hipMemcpyHostToDevice, stream));
     const size_t blocks = (n + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(count_tail_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kThreads), 0, stream, counts_dev,
+    hipLaunchKernelGGL(count_tail_kernel, dim3((unsigned)(blocks < (size_t)kTailMaxGrid ? blocks : (size_t)kTailMaxGrid)), dim3(kThreads), 0, stream, counts_dev,
                        (long long)n, norm_scale, scale_by_step, step, const_scale, const_scale >= 0.0 ? 1 : 0,
                        numpy_pow10(round_digits), round_digits, vals_out_dev, support);
     ROCCO_HIP_TRY(hipGetLastError());

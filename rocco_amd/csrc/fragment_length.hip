@@ -34,9 +34,10 @@ constexpr int kWaves = kThreads / kWave;
 constexpr int kDensityRecords = ROCCO_FRAGMENT_DENSITY_RECORDS;  // records a workgroup aggregates at a time
 constexpr int kDensityWindow = ROCCO_FRAGMENT_DENSITY_WINDOW;    // cells of its LDS window
 constexpr int kMaxBlockSize = ROCCO_FRAGMENT_MAX_BLOCK_SIZE;
-constexpr int kMaxGrid = 2048;
+constexpr int kMaxGrid = ROCCO_FRAGMENT_MAX_GRID;  // workgroups of a record pass at most
 
-static_assert(kThreads == 256 && kDensityRecords % kThreads == 0 && kDensityWindow % kThreads == 0, "rocco_hip.h states the shape");
+static_assert(kThreads == 256 && kDensityRecords % kThreads == 0 && kDensityWindow % kThreads == 0 && kMaxGrid > 0,
+              "rocco_hip.h states the shape");
 static_assert((size_t)kMaxBlockSize * 2 * sizeof(int) + 256 <= 160 * 1024, "two int32 arrays of a block fit one CU's LDS");
 
 // mapped[t]: records of track t with flag & 4 == 0 (what hts_idx_get_stat reports as mapped for a contig);

@@ -31,15 +31,16 @@ namespace rocco {
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = ROCCO_COUNT_INTERVALS_THREADS;
 constexpr int kWave = 64;
 constexpr int kWavesPerGroup = kThreads / kWave;
 constexpr int kUnit = 256;                       // candidate records of one work unit
 constexpr int kRecsPerLane = kUnit / kWave;
 constexpr int kMaxGrid = ROCCO_COUNT_INTERVALS_MAX_GRID;  // workgroups of the counting launch
+constexpr int kFactsMaxGrid = ROCCO_INTERVAL_FACTS_MAX_GRID;  // workgroups of interval_track_facts_kernel at most
 
 static_assert(kUnit == ROCCO_COUNT_INTERVALS_UNIT && kWavesPerGroup == ROCCO_COUNT_INTERVALS_WAVES_PER_GROUP && kMaxGrid > 0 &&
-                  kUnit % kWave == 0,
+                  kUnit % kWave == 0 && kThreads == 256 && kFactsMaxGrid > 0,
               "rocco_hip.h states the shape");
 
 // facts[2 t]: L of track t; facts[2 t + 1]: 1 when some pos is smaller than the one before it
@@ -232,7 +233,7 @@ int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_
         ROCCO_HIP_TRY(hipMemsetAsync(out_dev, 0, pairs * sizeof(int), stream));
         if (records > 0) {
             const long long blocks = (records + kThreads - 1) / kThreads;
-            hipLaunchKernelGGL(interval_track_facts_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kThreads), 0, stream,
+            hipLaunchKernelGGL(interval_track_facts_kernel, dim3((unsigned)(blocks < kFactsMaxGrid ? blocks : kFactsMaxGrid)), dim3(kThreads), 0, stream,
                                (const int *)pos_dev, (const int *)end_dev, rec_offsets, (int)T, facts_dev);
         }
         hipLaunchKernelGGL(interval_bounds_kernel, dim3((unsigned)((pairs + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,

@@ -28,11 +28,15 @@ namespace rocco {
 
 namespace {
 
-constexpr int kChunk = 16384;     // values a workgroup of a counting pass takes at a time
-constexpr int kGridTarget = 1024; // workgroups of a counting pass: two per CU at 64 KB of LDS each, twice over
+constexpr int kChunk = ROCCO_SELECT_CHUNK_VALUES;     // values a workgroup of a counting pass takes at a time
+constexpr int kGridTarget = ROCCO_SELECT_GRID_TARGET; // workgroups of a counting pass: two per CU at 64 KB of LDS each, twice over
+constexpr int kCountThreads = ROCCO_SELECT_THREADS;   // threads of a counting workgroup (eight loads in flight each)
+constexpr int kBhThreads = ROCCO_BH_THREADS, kBhMaxGrid = ROCCO_BH_MAX_GRID;
 constexpr int kCounters = 16384;  // histogram counters per vector: 1 slot x 2^14 buckets, or up to 16 slots x 2^10
 constexpr int kFirstBits = 14, kLaterBits = 10, kPasses = 6;
 static_assert(kFirstBits + (kPasses - 1) * kLaterBits == 64, "the passes cover the key");
+static_assert(kCountThreads == 256 && kChunk % (8 * kCountThreads) == 0 && kBhThreads == 256 && kGridTarget > 0 && kBhMaxGrid > 0,
+              "rocco_hip.h states the shape");
 static_assert((1 << kFirstBits) <= kCounters && kSelectRanksMax * (1 << kLaterBits) <= kCounters, "a vector's histogram");
 
 constexpr unsigned long long kMagnitude = 0x7FFFFFFFFFFFFFFFULL, kInfBits = 0x7FF0000000000000ULL;
@@ -416,7 +420,7 @@ int launch_bh_last_passing_rank(const double *sorted_dev, size_t m, double fdr, 
         return ROCCO_HIP_OK;
     }
     const size_t want = (m + 255) / 256;
-    const unsigned grid = (unsigned)(want < 2048 ? want : 2048);
+    const unsigned grid = (unsigned)(want < (size_t)kBhMaxGrid ? want : (size_t)kBhMaxGrid);
     hipLaunchKernelGGL(bh_last_passing_kernel, dim3(grid), dim3(256), 0, stream, sorted_dev, (long long)m, fdr, rank_out_dev);
     ROCCO_HIP_TRY(hipGetLastError());
     return ROCCO_HIP_OK;
