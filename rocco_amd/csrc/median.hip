@@ -503,7 +503,8 @@ __global__ __launch_bounds__(256) void order_statistic_kernel(const T *__restric
     out[j] = has_nan ? __longlong_as_double(0x7FF8000000000000LL) : found;
 }
 
-// np.mean(matrix, axis=0): the rows are added one after the other, then one division by K
+// np.mean(matrix, axis=0): the rows are added one after the other onto the reduction's initial +0.0 (so a column of
+// -0.0 gives +0.0; every other value is unchanged by it), then one division by K
 template <typename T>
 __global__ __launch_bounds__(256) void column_mean_kernel(const T *__restrict__ m, int K, long long n, long long stride,
                                                          double *__restrict__ out)
@@ -512,8 +513,8 @@ __global__ __launch_bounds__(256) void column_mean_kernel(const T *__restrict__ 
     if (j >= n) {
         return;
     }
-    double acc = (double)m[j];
-    for (int a = 1; a < K; ++a) {
+    double acc = 0.0;
+    for (int a = 0; a < K; ++a) {
         acc += (double)m[(long long)a * stride + j];
     }
     out[j] = acc / (double)K;
@@ -600,7 +601,8 @@ __global__ __launch_bounds__(256) void trimmed_mean_kernel(const T *__restrict__
         const double v = (double)m[(long long)a * stride + j];
         count += (v < lo || v > hi) ? 0.0 : 1.0;
     }
-    out[j] = trimmed_pairwise(m + j, stride, K, lo, hi) / count;
+    // np.sum adds the pairwise sum onto its initial +0.0: kept values that are all -0.0 sum to +0.0
+    out[j] = (0.0 + trimmed_pairwise(m + j, stride, K, lo, hi)) / count;
 }
 
 // np.power(x, p) of rocco/rocco.py:255,304: NumPy's loop squares for p == 2 (exact); every other exponent goes to its
