@@ -693,6 +693,51 @@ int rocco_hip_alignment_count_tail_f64(rocco_hip_solver *solver, const float *co
                                        int scale_by_step, double step, double const_scale, int round_digits,
                                        double *vals_out_dev, int64_t *first_out, int64_t *last_out, void *stream);
 
+/* ---- K files of one chromosome -> its count matrix in one device pass -------------
+ * What generate_chrom_matrix does over BAM inputs once the files are decoded (rocco/readtracks.py:439-518 per file,
+ * 601-633 over the files), with two waits for the device per call, whatever K is, and nothing as long as the
+ * chromosome crossing the bus.
+ *
+ * rocco_hip_alignment_chrom_range_batch: rocco_hip_alignment_chrom_range (ccounts_getChromRange, rocco/native/
+ *   ccounts_backend.c:1666-1705, as rocco/readtracks.py:439-446 calls it per file) for K tracks concatenated as the batch
+ *   counter takes them (rec_offsets_host: K + 1 entries): range_out_host[2 k] = pos of track k's first record in file order
+ *   that flag_exclude passes, range_out_host[2 k + 1] = end of its LAST record in file order among those reaching into
+ *   the last 2 000 000 bp; 0 where there is none.  One launch, one copy of 2 K int64, one wait.
+ * rocco_hip_track_supports: rocco_hip_count_alignment_records_batch (same arguments, accumulate = 0) and, queued behind it
+ *   without a wait, the positive support of rocco/readtracks.py:492-512 for every track: support_out_host[2 k] / [2 k + 1] =
+ *   first / last bin of track k whose SCALED value float64(count) * norm_scale_host[k], / step when scale_by_step,
+ *   * const_scale when const_scale >= 0 (in that order), is > 0; -1 / -1 where none is (a zero or negative scale, an
+ *   underflow: a positive count alone does not decide it).  max_magnitude_out_host as the counter's.  One wait, at the end.
+ * rocco_hip_track_matrix_fill: rocco/readtracks.py:505-518 per track and 614-633 over the tracks in one launch: writes
+ *   every element of the n_rows x m matrix (float64, or float32 for out_dtype = 1: np.asarray(vals, dtype=float32))
+ *   exactly once.  rows_dev: int64 [n_rows][ROCCO_TRACK_MATRIX_ROW_WORDS] = offset of the row's counts in counts_dev, its
+ *   bins, the grid index of its bin 0 (count_start / step), the grid indices of the first and last bin of its support,
+ *   the bits of its float64 norm_scale.  segs_dev: int64 [n_segs][2] = grid index and column of the first bin of each of
+ *   the disjoint, ascending segments whose bins, end to end, are the m columns (segs_dev[1] = 0).  Element (k, j): with g
+ *   the grid index of column j, np.round(scaled value of bin g - origin_k, round_digits) where g lies in row k's support,
+ *   else +0.0.  A bin outside [0, bins) or outside counts_len is never read, whatever the tables say.  No wait: the
+ *   tables and the matrix are the caller's, ordered by the stream.
+ * rocco_hip_track_matrix_shape: out[0..3] = threads of a workgroup, elements of one row a workgroup writes at a time,
+ *   workgroups of one launch at most (past cap x unit elements a workgroup takes several units in turn; the supports
+ *   kernel shares the cap), words of a row of rows_dev. */
+#define ROCCO_TRACK_MATRIX_THREADS 256
+#define ROCCO_TRACK_MATRIX_UNIT 1024
+#define ROCCO_TRACK_MATRIX_MAX_GRID 2048
+#define ROCCO_TRACK_MATRIX_ROW_WORDS 6
+int rocco_hip_alignment_chrom_range_batch(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                          const uint16_t *flag_dev, const int64_t *rec_offsets_host, size_t K, int64_t chrom_len,
+                                          int flag_exclude, int64_t *range_out_host, void *stream);
+int rocco_hip_track_supports(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
+                             const uint16_t *flag_dev, const uint8_t *mapq_dev, const uint8_t *mate_same_dev,
+                             const int64_t *rec_offsets_host, size_t K, const rocco_hip_count_options *options_host,
+                             const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host,
+                             const double *norm_scale_host, int scale_by_step, double step, double const_scale, float *out_dev,
+                             int64_t *max_magnitude_out_host, int64_t *support_out_host, void *stream);
+int rocco_hip_track_matrix_fill(rocco_hip_solver *solver, const float *counts_dev, size_t counts_len, const int64_t *rows_dev,
+                                size_t n_rows, const int64_t *segs_dev, size_t n_segs, size_t m, int scale_by_step, double step,
+                                double const_scale, int round_digits, int out_dtype, void *matrix_out_dev, void *stream);
+void rocco_hip_track_matrix_shape(int *out);
+
 /* ---- decoded alignment records -> one count per (interval, file) ------------------
  * The counting half of the reference's post-hoc scoring for records already decoded (the six arrays above).
  *

@@ -279,6 +279,21 @@ PROTOTYPES = [
     ("rocco_hip_alignment_count_tail_f64", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double,
       ctypes.c_int, ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_void_p]),
+    # row f9 (csrc/count.hip, csrc/track_matrix.hip): ccounts_getChromRange per file, rocco/readtracks.py:439-446, K files at once
+    ("rocco_hip_alignment_chrom_range_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_int,
+      c_ll_p, ctypes.c_void_p]),
+    # the counting and the positive support of every file, rocco/readtracks.py:475-512
+    ("rocco_hip_track_supports", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      c_ll_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+      ctypes.c_double, ctypes.c_double, ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_void_p]),
+    # trim and np.round per file, union / zeros / scatter over the files: rocco/readtracks.py:505-518, 601-633
+    ("rocco_hip_track_matrix_fill", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_size_t, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    # (no reference line: threads, unit, grid cap and row words of the fill, for the tests)
+    ("rocco_hip_track_matrix_shape", None, [c_int_p]),
     # count_alignment_intervals, rocco/_hts_counts.c:571-836 (raw_count_matrix and the null counts of rocco/scores.py)
     ("rocco_hip_count_alignment_intervals_batch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

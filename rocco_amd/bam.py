@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import logging
 import multiprocessing
 import os
 import struct
@@ -664,3 +665,102 @@ def get_bam_chrom_reads(bam_file: str, chromosome: str, chrom_sizes_file: str, s
                                             min_mapping_score=min_mapping_score, flag_include=flag_include, flag_exclude=flag_exclude,
                                             center_reads=center_reads, const_scale=const_scale, round_digits=round_digits,
                                             scale_by_step=scale_by_step, bam_file=bam_file, chromosome=chromosome)
+
+
+# --------------------------------------------------------------------------------------------
+# K files of one chromosome -> its count matrix in one device pass
+# --------------------------------------------------------------------------------------------
+
+class _HeldRecords(logging.Filter):
+    """Keeps the records the module's logger would emit, for `logger.handle` to emit later in the reference's order."""
+
+    def __init__(self):
+        super().__init__()
+        self.records = []
+
+    def filter(self, record):
+        self.records.append(record)
+        return False
+
+
+def generate_chrom_matrix_device(chromosome: str, input_files: list, chrom_sizes_file: str, step: int, const_scale: float = 1.0,
+                                 round_digits: int = 5, scale_by_step: bool = False, effective_genome_size: float = -1,
+                                 norm_method: str = "RPGC", min_mapping_score: int = 10, flag_include=None, flag_exclude: int = 3844,
+                                 extend_reads: int = -1, center_reads: bool = False, ignore_for_norm=None, scale_factor: float = 1.0,
+                                 num_processors: int = -1, low_memory: bool = False):
+    """The reference's ``generate_chrom_matrix`` over BAM files (rocco/readtracks.py:521-633, same keywords) with the matrix
+    left on the device: returns (starts as a host ``int`` array, count matrix as a CUDA tensor), or ``(None, None)``.  Per
+    file, in file order, what ``get_bam_chrom_reads`` does before it counts -- its two FileNotFoundErrors and its
+    chromosome ValueError for the first offending file, the metadata through `_get_bam_count_metadata` (its cache, its log
+    lines), the decoded file from `_cached_file`, the warning for a header without the contig --; everything after that
+    for all files at once (`rocco_amd.readtracks.bam_chrom_matrix_from_records_batch`: two waits for the device per call,
+    nothing as long as the chromosome on the bus).  The log records of the call are the reference's, in its order: they are
+    held while the files are worked on together and emitted file by file afterwards.  This is the function to bind behind
+    ``rocco_amd.rocco.generate_chrom_matrix``."""
+    track_types = {_rt._get_track_type(input_file) for input_file in input_files}
+    if len(track_types) != 1:
+        raise ValueError("All input files must share the same type.")
+    if next(iter(track_types)) != "bam":
+        raise ValueError("rocco_amd.bam.generate_chrom_matrix reads BAM files: bigWig inputs go through "
+                         "rocco_amd.readtracks.generate_chrom_matrix")
+    threads = max((os.cpu_count() or 2) - 1, 1) if (num_processors is None or int(num_processors) < 1) else int(num_processors)
+    if ignore_for_norm is None:
+        ignore_for_norm = ["chrX", "chrY", "chrM"]
+    K = len(input_files)
+    before, records_list, metadata_list, present, chrom_size = [[] for _ in range(K)], [], [], [], 0
+    held = _HeldRecords()
+    logger.addFilter(held)
+    try:
+        for k, bam_file in enumerate(input_files):
+            if not os.path.exists(bam_file):
+                raise FileNotFoundError(f"BAM file not found: {bam_file}")
+            if not os.path.exists(chrom_sizes_file):
+                raise FileNotFoundError(f"Chromosome sizes file not found: {chrom_sizes_file}")
+            sizes = _rt.get_chroms_and_sizes(chrom_sizes_file)
+            if chromosome not in sizes:
+                raise ValueError(f"Chromosome {chromosome} not found in chromosome sizes file: {chrom_sizes_file}")
+            chrom_size = int(sizes[chromosome])
+            metadata = _get_bam_count_metadata(bam_file, step=step, norm_method=norm_method, effective_genome_size=effective_genome_size,
+                                               ignore_for_norm=ignore_for_norm, flag_exclude=flag_exclude, extend_reads=extend_reads,
+                                               num_processors=threads, scale_factor=scale_factor)
+            file = _cached_file(bam_file)
+            if chromosome not in file.records:
+                logger.warning("Chromosome %s not found in BAM file: %s. Returning (None,None).", chromosome, bam_file)
+            else:
+                present.append(k)
+                records_list.append(file.records[chromosome])
+                metadata_list.append(metadata)
+            before[k], held.records = held.records, []
+    except BaseException:
+        logger.removeFilter(held)
+        for record in [r for records in before for r in records] + held.records:
+            logger.handle(record)  # (an error cut the call short: what was logged up to it is not lost)
+        raise
+    logger.removeFilter(held)
+    names = [input_files[k] for k in present]
+    starts, matrix, file_logs, has_data = _rt._bam_matrix_batch(records_list, chrom_size, step, metadata_list, min_mapping_score,
+                                                                flag_include, flag_exclude, center_reads, const_scale, round_digits,
+                                                                scale_by_step, low_memory, names, chromosome)
+    after = dict(zip(present, file_logs))
+    live = dict(zip(present, has_data))
+    for k in range(K):
+        for record in before[k]:
+            logger.handle(record)
+        _rt._emit(after.get(k, ()))
+    _rt._emit(_rt._excluded_records(input_files, [live.get(k, False) for k in range(K)], chromosome))
+    return starts, matrix
+
+
+def generate_chrom_matrix(chromosome: str, input_files: list, chrom_sizes_file: str, step: int, const_scale: float = 1.0,
+                          round_digits: int = 5, scale_by_step: bool = False, effective_genome_size: float = -1,
+                          norm_method: str = "RPGC", min_mapping_score: int = 10, flag_include=None, flag_exclude: int = 3844,
+                          extend_reads: int = -1, center_reads: bool = False, ignore_for_norm=None, scale_factor: float = 1.0,
+                          num_processors: int = -1, low_memory: bool = False):
+    """`generate_chrom_matrix_device` with the reference's signature and return value (rocco/readtracks.py:521-633): NumPy
+    ``(common_intervals.astype(int), count_matrix)``, or ``(None, None)``."""
+    starts, matrix = generate_chrom_matrix_device(chromosome, input_files, chrom_sizes_file, step, const_scale, round_digits, scale_by_step,
+                                                  effective_genome_size, norm_method, min_mapping_score, flag_include, flag_exclude,
+                                                  extend_reads, center_reads, ignore_for_norm, scale_factor, num_processors, low_memory)
+    if starts is None:
+        return None, None
+    return starts.astype(int), matrix.cpu().numpy()

@@ -1511,6 +1511,77 @@ int rocco_hip_alignment_count_tail_f64(rocco_hip_solver *solver, const float *co
                                        first_out, last_out, solver->dev_misc.ptr, (hipStream_t)stream);
 }
 
+// ccounts_getChromRange per file (rocco/readtracks.py:439-446), K files in one launch
+int rocco_hip_alignment_chrom_range_batch(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                          const uint16_t *flag_dev, const int64_t *rec_offsets_host, size_t K, int64_t chrom_len,
+                                          int flag_exclude, int64_t *range_out_host, void *stream)
+{
+    if (solver == nullptr || K == 0 || K >= (size_t)0x7fffffff || rec_offsets_host == nullptr || range_out_host == nullptr ||
+        chrom_len < 0) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (rec_offsets_host[K] > rec_offsets_host[0] && (pos_dev == nullptr || end_dev == nullptr || flag_dev == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, chrom_range_batch_scratch_bytes(K)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_alignment_chrom_range_batch(pos_dev, end_dev, flag_dev, rec_offsets_host, K, chrom_len, flag_exclude,
+                                              range_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+// the counting and the positive support of every file (rocco/readtracks.py:475-512), one wait
+int rocco_hip_track_supports(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
+                             const uint16_t *flag_dev, const uint8_t *mapq_dev, const uint8_t *mate_same_dev,
+                             const int64_t *rec_offsets_host, size_t K, const rocco_hip_count_options *options_host,
+                             const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host,
+                             const double *norm_scale_host, int scale_by_step, double step, double const_scale, float *out_dev,
+                             int64_t *max_magnitude_out_host, int64_t *support_out_host, void *stream)
+{
+    if (solver == nullptr || K == 0 || K >= (size_t)0x7fffffff || rec_offsets_host == nullptr || options_host == nullptr ||
+        regions_host == nullptr || out_offsets_host == nullptr || norm_scale_host == nullptr || out_dev == nullptr ||
+        max_magnitude_out_host == nullptr || support_out_host == nullptr) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (rec_offsets_host[K] > rec_offsets_host[0] &&
+        (pos_dev == nullptr || end_dev == nullptr || isize_dev == nullptr || flag_dev == nullptr || mapq_dev == nullptr ||
+         mate_same_dev == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    const size_t bytes = track_supports_scratch_bytes(rec_offsets_host, K, options_host, regions_host, out_offsets_host);
+    if (const int rc = enter_record_call(solver, bytes); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_track_supports(pos_dev, end_dev, isize_dev, flag_dev, mapq_dev, mate_same_dev, rec_offsets_host, K, options_host,
+                                 regions_host, out_offsets_host, norm_scale_host, scale_by_step, step, const_scale, out_dev,
+                                 max_magnitude_out_host, support_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+// the trim and np.round per file (rocco/readtracks.py:505-518) and the union, zeros and scatter over the files (601-633)
+int rocco_hip_track_matrix_fill(rocco_hip_solver *solver, const float *counts_dev, size_t counts_len, const int64_t *rows_dev,
+                                size_t n_rows, const int64_t *segs_dev, size_t n_segs, size_t m, int scale_by_step, double step,
+                                double const_scale, int round_digits, int out_dtype, void *matrix_out_dev, void *stream)
+{
+    if (solver == nullptr || counts_dev == nullptr || rows_dev == nullptr || segs_dev == nullptr || matrix_out_dev == nullptr ||
+        n_rows == 0 || n_segs == 0 || m == 0 || n_rows >= (size_t)0x7fffffff || n_segs >= (size_t)0x7fffffff ||
+        m >= ((size_t)1 << 40) || round_digits > 22 || round_digits < -22 || (out_dtype != 0 && out_dtype != 1)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device));
+    (void)hipGetLastError();
+    return launch_track_matrix_fill(counts_dev, counts_len, rows_dev, n_rows, segs_dev, n_segs, m, scale_by_step, step, const_scale,
+                                    round_digits, out_dtype, matrix_out_dev, (hipStream_t)stream);
+}
+
+// (no reference line: the sizes at which track_matrix.hip's kernel changes path, for the tests)
+void rocco_hip_track_matrix_shape(int *out)
+{
+    out[0] = ROCCO_TRACK_MATRIX_THREADS;
+    out[1] = ROCCO_TRACK_MATRIX_UNIT;
+    out[2] = ROCCO_TRACK_MATRIX_MAX_GRID;
+    out[3] = ROCCO_TRACK_MATRIX_ROW_WORDS;
+}
+
 int rocco_hip_count_alignment_intervals_batch(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
                                               const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mapq_dev,
                                               const uint8_t *mate_same_dev, const int64_t *rec_offsets_host, size_t F, size_t C,

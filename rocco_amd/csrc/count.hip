@@ -6,6 +6,8 @@
 //   ccounts_getChromRange (rocco/native/ccounts_backend.c:1666-1705): first start / last end of a contig
 //   the tail of get_bam_chrom_reads (rocco/readtracks.py:492-517): scaling, positive support, np.round
 // A record is six integers (pos, end = bam_endpos, isize, flag, mapq, mate on the same contig), in file order.
+// For the K files of a chromosome at once (row f9): the ranges of all tracks in one launch, and the positive support of every
+// track queued behind the counting (launch_track_supports); the matrix they lead to is written by track_matrix.hip.
 //
 // Counting is integer work: +1 / -1 into an int32 difference array with integer atomics (the result does not depend on
 // scheduling), an int32 prefix sum, one conversion to float32.  The reference adds +-1.0f into float cells and runs a
@@ -16,6 +18,7 @@
 // aggregates its records in an LDS window of bins anchored at the lowest bin its records touch, and flushes the
 // non-zero cells with one global atomic each; indices past the window (the far end of a long fragment) go to global
 // memory directly.  The prefix sum is reduce-then-scan over tiles (three launches, no waiting between workgroups).
+#include "count_tail.h"
 #include "kernels.h"
 #include "record_cells.h"
 #include "record_layouts.h"
@@ -34,6 +37,7 @@ constexpr int kThreads = ROCCO_COUNT_THREADS;
 constexpr int kRecsPerThread = 2;
 constexpr int kRangeMaxGrid = ROCCO_CHROM_RANGE_MAX_GRID;  // workgroups of chrom_range_kernel at most
 constexpr int kTailMaxGrid = ROCCO_COUNT_TAIL_MAX_GRID;    // workgroups of count_tail_kernel at most
+constexpr int kMatrixMaxGrid = ROCCO_TRACK_MATRIX_MAX_GRID;  // workgroups of track_supports_kernel at most
 constexpr int kChunk = kThreads * kRecsPerThread;  // records one workgroup aggregates at a time
 constexpr int kWindow = 1024;                      // bins of the LDS window
 constexpr int kScanItems = 8;
@@ -301,14 +305,7 @@ __global__ __launch_bounds__(kThreads) void count_tail_kernel(const float *__res
 {
     unsigned long long first = ~0ULL, last = 0;
     for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
-        double v = (double)counts[i];
-        v = v * norm_scale;
-        if (scale_by_step) {
-            v = v / step;
-        }
-        if (apply_const) {
-            v = v * const_scale;
-        }
+        const double v = count_tail_value(counts[i], norm_scale, scale_by_step, step, apply_const, const_scale);
         if (v > 0.0) {
             first = (unsigned long long)i < first ? (unsigned long long)i : first;
             last = (unsigned long long)i + 1;
@@ -316,6 +313,76 @@ __global__ __launch_bounds__(kThreads) void count_tail_kernel(const float *__res
         out[i] = round_like_numpy(v, pow10, digits);
     }
     wave_first_last(first, last, support);
+}
+
+// ---- K tracks at once -------------------------------------------------------------------
+// chrom_range_kernel for K tracks: a workgroup takes units of kThreads records of one track (unit_first: K + 1 ascending
+// entries), in a grid stride.  first[k] / last[k] as result[0] / result[1] there, record indices into the concatenated arrays.
+__global__ __launch_bounds__(kThreads) void chrom_range_batch_kernel(const int *__restrict__ pos, const int *__restrict__ end,
+                                                                    const unsigned short *__restrict__ flag,
+                                                                    const long long *__restrict__ rec_offsets,
+                                                                    const long long *__restrict__ unit_first, int K, long long total_units,
+                                                                    long long chrom_len, long long tail_start, int flag_exclude,
+                                                                    unsigned long long *__restrict__ first_out,
+                                                                    unsigned long long *__restrict__ last_out)
+{
+    for (long long unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
+        const int k = find_slot(unit_first, K, unit);
+        const long long i = rec_offsets[k] + (unit - unit_first[k]) * kThreads + threadIdx.x;
+        unsigned long long first = ~0ULL, last = 0;
+        if (i < rec_offsets[k + 1] && (flag[i] & flag_exclude) == 0) {
+            const long long p = pos[i], e = end[i] > p + 1 ? end[i] : p + 1;
+            if (p < chrom_len && e > 0) {
+                first = (unsigned long long)i;
+            }
+            if (p < chrom_len && e > tail_start) {
+                last = (unsigned long long)i + 1;
+            }
+        }
+        wave_first_last(first, last, first_out + k, last_out + k);
+    }
+}
+
+// range[2 k] = pos of track k's first record, range[2 k + 1] = end of its last one (0: none), as chrom_range_fetch_kernel
+__global__ __launch_bounds__(kThreads) void chrom_range_batch_fetch_kernel(const int *__restrict__ pos, const int *__restrict__ end,
+                                                                          const unsigned long long *__restrict__ first,
+                                                                          const unsigned long long *__restrict__ last, int K,
+                                                                          long long *__restrict__ range)
+{
+    const int k = blockIdx.x * kThreads + threadIdx.x;
+    if (k < K) {
+        range[2 * k] = first[k] != ~0ULL ? (long long)pos[first[k]] : 0;
+        range[2 * k + 1] = last[k] != 0 ? (long long)end[last[k] - 1] : 0;
+    }
+}
+
+// the support of count_tail_kernel for K tracks, without its values: first[k] / last[k] = lowest index / highest index + 1
+// of a bin of track k whose scaled value is > 0.  A workgroup takes units of kSupportUnit bins of one track in a grid stride.
+constexpr int kSupportPerThread = 4;
+constexpr int kSupportUnit = kThreads * kSupportPerThread;
+
+__global__ __launch_bounds__(kThreads) void track_supports_kernel(const float *__restrict__ counts, const SupportTrack *__restrict__ tracks,
+                                                                 const long long *__restrict__ unit_first, int K, long long total_units,
+                                                                 int scale_by_step, double step, double const_scale, int apply_const,
+                                                                 unsigned long long *__restrict__ first_out,
+                                                                 unsigned long long *__restrict__ last_out)
+{
+    for (long long unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
+        const int k = find_slot(unit_first, K, unit);
+        const SupportTrack t = tracks[k];
+        const float *__restrict__ track_counts = counts + t.counts_offset;
+        const long long base = (unit - unit_first[k]) * kSupportUnit;
+        unsigned long long first = ~0ULL, last = 0;
+#pragma unroll
+        for (int j = 0; j < kSupportPerThread; ++j) {
+            const long long i = base + (long long)j * kThreads + threadIdx.x;
+            if (i < t.n_bins && count_tail_value(track_counts[i], t.norm_scale, scale_by_step, step, apply_const, const_scale) > 0.0) {
+                first = (unsigned long long)i < first ? (unsigned long long)i : first;
+                last = (unsigned long long)i + 1;
+            }
+        }
+        wave_first_last(first, last, first_out + k, last_out + k);
+    }
 }
 
 struct CountPlan {
@@ -368,6 +435,39 @@ int make_plan(const int64_t *rec_offsets, size_t K, const rocco_hip_count_option
     return ROCCO_HIP_OK;
 }
 
+// Queues the counting of `plan` on `stream` and waits for nothing: the caller keeps `plan` until the stream has taken its
+// vectors, fetches *max_dev_out (K ints in the scratch buffer) and synchronises.
+int queue_count(const CountPlan &plan, const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
+                const uint16_t *flag_dev, const uint8_t *mapq_dev, const uint8_t *mate_same_dev, size_t K, int accumulate,
+                float *out_dev, void *scratch_dev, hipStream_t stream, int **max_dev_out)
+{
+    char *sc = (char *)scratch_dev;
+    CountTrack *tracks = (CountTrack *)(sc + plan.at.tracks);
+    int *chunk_first = (int *)(sc + plan.at.chunk_first), *tile_first = (int *)(sc + plan.at.tile_first);
+    int *max_dev = (int *)(sc + plan.at.maxima), *tile_sums = (int *)(sc + plan.at.tile_sums), *delta = (int *)(sc + plan.at.delta);
+    ROCCO_HIP_TRY(hipMemcpyAsync(tracks, plan.tracks.data(), K * sizeof(CountTrack), hipMemcpyHostToDevice, stream));
+    ROCCO_HIP_TRY(hipMemcpyAsync(chunk_first, plan.chunk_first.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+    ROCCO_HIP_TRY(hipMemcpyAsync(tile_first, plan.tile_first.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+    // the difference arrays and, in front of them, the per-track maxima and the tile sums: the tail of the layout
+    ROCCO_HIP_TRY(hipMemsetAsync(max_dev, 0, plan.at.bytes - plan.at.maxima, stream));
+    const int chunks = plan.chunk_first[K], tiles = plan.tile_first[K];
+    if (chunks > 0) {
+        const int grid = chunks < kMaxGrid ? chunks : kMaxGrid;
+        hipLaunchKernelGGL(count_records_kernel, dim3((unsigned)grid), dim3(kThreads), 0, stream, (const int *)pos_dev,
+                           (const int *)end_dev, (const int *)isize_dev, (const unsigned short *)flag_dev,
+                           (const unsigned char *)mapq_dev, (const unsigned char *)mate_same_dev, tracks, (int)K, chunk_first,
+                           chunks, delta);
+    }
+    hipLaunchKernelGGL(tile_sum_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, stream, tracks, (int)K, tile_first, delta,
+                       tile_sums);
+    hipLaunchKernelGGL(tile_offsets_kernel, dim3((unsigned)K), dim3(kThreads), 0, stream, tile_first, tile_sums);
+    hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, stream, tracks, (int)K, tile_first, delta,
+                       tile_sums, accumulate, out_dev, max_dev);
+    ROCCO_HIP_TRY(hipGetLastError());
+    *max_dev_out = max_dev;
+    return ROCCO_HIP_OK;
+}
+
 }  // namespace
 
 size_t count_alignment_scratch_bytes(const int64_t *rec_offsets_host, size_t K, const rocco_hip_count_options *options_host,
@@ -396,29 +496,12 @@ int launch_count_alignment_records(const int32_t *pos_dev, const int32_t *end_de
     // the copies below read this call's host vectors (plan's going up, `maxima` coming back): no return before the stream has
     // taken them
     const int queued = queue_then_drain(stream, [&]() -> int {
-        char *sc = (char *)scratch_dev;
-        CountTrack *tracks = (CountTrack *)(sc + plan.at.tracks);
-        int *chunk_first = (int *)(sc + plan.at.chunk_first), *tile_first = (int *)(sc + plan.at.tile_first);
-        int *max_dev = (int *)(sc + plan.at.maxima), *tile_sums = (int *)(sc + plan.at.tile_sums), *delta = (int *)(sc + plan.at.delta);
-        ROCCO_HIP_TRY(hipMemcpyAsync(tracks, plan.tracks.data(), K * sizeof(CountTrack), hipMemcpyHostToDevice, stream));
-        ROCCO_HIP_TRY(hipMemcpyAsync(chunk_first, plan.chunk_first.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-        ROCCO_HIP_TRY(hipMemcpyAsync(tile_first, plan.tile_first.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-        // the difference arrays and, in front of them, the per-track maxima and the tile sums: the tail of the layout
-        ROCCO_HIP_TRY(hipMemsetAsync(max_dev, 0, plan.at.bytes - plan.at.maxima, stream));
-        const int chunks = plan.chunk_first[K], tiles = plan.tile_first[K];
-        if (chunks > 0) {
-            const int grid = chunks < kMaxGrid ? chunks : kMaxGrid;
-            hipLaunchKernelGGL(count_records_kernel, dim3((unsigned)grid), dim3(kThreads), 0, stream, (const int *)pos_dev,
-                               (const int *)end_dev, (const int *)isize_dev, (const unsigned short *)flag_dev,
-                               (const unsigned char *)mapq_dev, (const unsigned char *)mate_same_dev, tracks, (int)K, chunk_first,
-                               chunks, delta);
+        int *max_dev = nullptr;
+        if (const int q = queue_count(plan, pos_dev, end_dev, isize_dev, flag_dev, mapq_dev, mate_same_dev, K, accumulate, out_dev,
+                                      scratch_dev, stream, &max_dev);
+            q != ROCCO_HIP_OK) {
+            return q;
         }
-        hipLaunchKernelGGL(tile_sum_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, stream, tracks, (int)K, tile_first, delta,
-                           tile_sums);
-        hipLaunchKernelGGL(tile_offsets_kernel, dim3((unsigned)K), dim3(kThreads), 0, stream, tile_first, tile_sums);
-        hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, stream, tracks, (int)K, tile_first, delta,
-                           tile_sums, accumulate, out_dev, max_dev);
-        ROCCO_HIP_TRY(hipGetLastError());
         ROCCO_HIP_TRY(hipMemcpyAsync(maxima.data(), max_dev, K * sizeof(int), hipMemcpyDeviceToHost, stream));
         ROCCO_HIP_TRY(hipStreamSynchronize(stream));  // the scratch buffer is the solver's; the maxima are the caller's guard
         return ROCCO_HIP_OK;
@@ -428,6 +511,125 @@ int launch_count_alignment_records(const int32_t *pos_dev, const int32_t *end_de
     }
     for (size_t k = 0; k < K; ++k) {
         max_magnitude_out_host[k] = maxima[k];
+    }
+    return ROCCO_HIP_OK;
+}
+
+size_t track_supports_scratch_bytes(const int64_t *rec_offsets_host, size_t K, const rocco_hip_count_options *options_host,
+                                    const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host)
+{
+    const size_t counting = count_alignment_scratch_bytes(rec_offsets_host, K, options_host, regions_host, out_offsets_host);
+    return counting == 0 ? 0 : counting + SupportsLayout(K).bytes;
+}
+
+int launch_track_supports(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev, const uint16_t *flag_dev,
+                          const uint8_t *mapq_dev, const uint8_t *mate_same_dev, const int64_t *rec_offsets_host, size_t K,
+                          const rocco_hip_count_options *options_host, const rocco_hip_count_region *regions_host,
+                          const int64_t *out_offsets_host, const double *norm_scale_host, int scale_by_step, double step,
+                          double const_scale, float *out_dev, int64_t *max_magnitude_out_host, int64_t *support_out_host,
+                          void *scratch_dev, hipStream_t stream)
+{
+    CountPlan plan;
+    const int rc = make_plan(rec_offsets_host, K, options_host, regions_host, out_offsets_host, plan);
+    if (rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    const SupportsLayout at(K);
+    std::vector<SupportTrack> tracks(K);
+    std::vector<long long> unit_first(K + 1, 0);
+    for (size_t k = 0; k < K; ++k) {
+        tracks[k] = SupportTrack{(long long)out_offsets_host[k], (long long)regions_host[k].n_bins, norm_scale_host[k]};
+        unit_first[k + 1] = unit_first[k] + ((long long)regions_host[k].n_bins + kSupportUnit - 1) / kSupportUnit;
+    }
+    std::vector<int> maxima(K, 0);
+    std::vector<unsigned long long> support(2 * K, 0);  // first[K] then last[K], as the layout keeps them
+    const int queued = queue_then_drain(stream, [&]() -> int {
+        int *max_dev = nullptr;
+        if (const int q = queue_count(plan, pos_dev, end_dev, isize_dev, flag_dev, mapq_dev, mate_same_dev, K, 0, out_dev, scratch_dev,
+                                      stream, &max_dev);
+            q != ROCCO_HIP_OK) {
+            return q;
+        }
+        char *sc = (char *)scratch_dev + plan.at.bytes;  // behind the counter's regions
+        SupportTrack *tracks_dev = (SupportTrack *)(sc + at.tracks);
+        long long *unit_first_dev = (long long *)(sc + at.unit_first);
+        unsigned long long *first_dev = (unsigned long long *)(sc + at.first), *last_dev = (unsigned long long *)(sc + at.last);
+        ROCCO_HIP_TRY(hipMemcpyAsync(tracks_dev, tracks.data(), K * sizeof(SupportTrack), hipMemcpyHostToDevice, stream));
+        ROCCO_HIP_TRY(hipMemcpyAsync(unit_first_dev, unit_first.data(), (K + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+        ROCCO_HIP_TRY(hipMemsetAsync(first_dev, 0xff, K * sizeof(unsigned long long), stream));
+        ROCCO_HIP_TRY(hipMemsetAsync(last_dev, 0, K * sizeof(unsigned long long), stream));
+        const long long units = unit_first[K];
+        hipLaunchKernelGGL(track_supports_kernel, dim3((unsigned)(units < (long long)kMatrixMaxGrid ? units : (long long)kMatrixMaxGrid)),
+                           dim3(kThreads), 0, stream, (const float *)out_dev, tracks_dev, unit_first_dev, (int)K, units, scale_by_step,
+                           step, const_scale, const_scale >= 0.0 ? 1 : 0, first_dev, last_dev);
+        ROCCO_HIP_TRY(hipGetLastError());
+        ROCCO_HIP_TRY(hipMemcpyAsync(maxima.data(), max_dev, K * sizeof(int), hipMemcpyDeviceToHost, stream));
+        ROCCO_HIP_TRY(hipMemcpyAsync(support.data(), first_dev, K * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        ROCCO_HIP_TRY(hipMemcpyAsync(support.data() + K, last_dev, K * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        ROCCO_HIP_TRY(hipStreamSynchronize(stream));  // the one wait of this call: the scratch buffer is the solver's
+        return ROCCO_HIP_OK;
+    });
+    if (queued != ROCCO_HIP_OK) {
+        return queued;
+    }
+    for (size_t k = 0; k < K; ++k) {
+        max_magnitude_out_host[k] = maxima[k];
+        const bool any = support[K + k] != 0;
+        support_out_host[2 * k] = any ? (int64_t)support[k] : -1;
+        support_out_host[2 * k + 1] = any ? (int64_t)support[K + k] - 1 : -1;
+    }
+    return ROCCO_HIP_OK;
+}
+
+size_t chrom_range_batch_scratch_bytes(size_t K) { return RangeBatchLayout(K).bytes; }
+
+int launch_alignment_chrom_range_batch(const int32_t *pos_dev, const int32_t *end_dev, const uint16_t *flag_dev,
+                                       const int64_t *rec_offsets_host, size_t K, int64_t chrom_len, int flag_exclude,
+                                       int64_t *range_out_host, void *scratch_dev, hipStream_t stream)
+{
+    const int rc = check_record_tracks(rec_offsets_host, K, "alignment_chrom_range_batch");
+    if (rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    for (size_t k = 0; k < 2 * K; ++k) {
+        range_out_host[k] = 0;
+    }
+    const RangeBatchLayout at(K);
+    std::vector<long long> rec_offsets(rec_offsets_host, rec_offsets_host + K + 1), unit_first(K + 1, 0);
+    for (size_t k = 0; k < K; ++k) {
+        unit_first[k + 1] = unit_first[k] + (rec_offsets[k + 1] - rec_offsets[k] + kThreads - 1) / kThreads;
+    }
+    const long long units = unit_first[K];
+    if (units == 0) {
+        return ROCCO_HIP_OK;
+    }
+    std::vector<long long> range(2 * K, 0);
+    const int queued = queue_then_drain(stream, [&]() -> int {
+        char *sc = (char *)scratch_dev;
+        long long *rec_offsets_dev = (long long *)(sc + at.rec_offsets), *unit_first_dev = (long long *)(sc + at.unit_first);
+        unsigned long long *first_dev = (unsigned long long *)(sc + at.first), *last_dev = (unsigned long long *)(sc + at.last);
+        long long *range_dev = (long long *)(sc + at.range);
+        ROCCO_HIP_TRY(hipMemcpyAsync(rec_offsets_dev, rec_offsets.data(), (K + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+        ROCCO_HIP_TRY(hipMemcpyAsync(unit_first_dev, unit_first.data(), (K + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+        ROCCO_HIP_TRY(hipMemsetAsync(first_dev, 0xff, K * sizeof(unsigned long long), stream));
+        ROCCO_HIP_TRY(hipMemsetAsync(last_dev, 0, K * sizeof(unsigned long long), stream));
+        const long long tail_start = chrom_len > 2000000LL ? chrom_len - 2000000LL : 0;  // tailCushion (:1684)
+        hipLaunchKernelGGL(chrom_range_batch_kernel, dim3((unsigned)(units < (long long)kRangeMaxGrid ? units : (long long)kRangeMaxGrid)),
+                           dim3(kThreads), 0, stream, (const int *)pos_dev, (const int *)end_dev, (const unsigned short *)flag_dev,
+                           rec_offsets_dev, unit_first_dev, (int)K, units, (long long)chrom_len, tail_start, flag_exclude, first_dev,
+                           last_dev);
+        hipLaunchKernelGGL(chrom_range_batch_fetch_kernel, dim3((unsigned)((K + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
+                           (const int *)pos_dev, (const int *)end_dev, first_dev, last_dev, (int)K, range_dev);
+        ROCCO_HIP_TRY(hipGetLastError());
+        ROCCO_HIP_TRY(hipMemcpyAsync(range.data(), range_dev, 2 * K * sizeof(long long), hipMemcpyDeviceToHost, stream));
+        ROCCO_HIP_TRY(hipStreamSynchronize(stream));  // the one wait of this call
+        return ROCCO_HIP_OK;
+    });
+    if (queued != ROCCO_HIP_OK) {
+        return queued;
+    }
+    for (size_t k = 0; k < 2 * K; ++k) {
+        range_out_host[k] = range[k];
     }
     return ROCCO_HIP_OK;
 }

@@ -330,6 +330,26 @@ int launch_alignment_chrom_range(const int32_t *pos_dev, const int32_t *end_dev,
 int launch_alignment_count_tail(const float *counts_dev, size_t n, double norm_scale, int scale_by_step, double step,
                                 double const_scale, int round_digits, double *vals_out_dev, int64_t *first_out,
                                 int64_t *last_out, void *scratch_dev, hipStream_t stream);
+// K tracks in one launch; range_out_host: 2 K values
+size_t chrom_range_batch_scratch_bytes(size_t K);
+int launch_alignment_chrom_range_batch(const int32_t *pos_dev, const int32_t *end_dev, const uint16_t *flag_dev,
+                                       const int64_t *rec_offsets_host, size_t K, int64_t chrom_len, int flag_exclude,
+                                       int64_t *range_out_host, void *scratch_dev, hipStream_t stream);
+// the counting and, behind it, every track's positive support; 0: a track's region or offset is invalid
+size_t track_supports_scratch_bytes(const int64_t *rec_offsets_host, size_t K, const rocco_hip_count_options *options_host,
+                                    const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host);
+int launch_track_supports(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev, const uint16_t *flag_dev,
+                          const uint8_t *mapq_dev, const uint8_t *mate_same_dev, const int64_t *rec_offsets_host, size_t K,
+                          const rocco_hip_count_options *options_host, const rocco_hip_count_region *regions_host,
+                          const int64_t *out_offsets_host, const double *norm_scale_host, int scale_by_step, double step,
+                          double const_scale, float *out_dev, int64_t *max_magnitude_out_host, int64_t *support_out_host,
+                          void *scratch_dev, hipStream_t stream);
+
+// ---- track_matrix.hip -------------------------------------------------------------------------
+// out_dtype: 0 float64, 1 float32; queues one launch and waits for nothing
+int launch_track_matrix_fill(const float *counts_dev, size_t counts_len, const int64_t *rows_dev, size_t n_rows, const int64_t *segs_dev,
+                             size_t n_segs, size_t m, int scale_by_step, double step, double const_scale, int round_digits,
+                             int out_dtype, void *matrix_out_dev, hipStream_t stream);
 
 // ---- interval_count.hip -----------------------------------------------------------------------
 // 0: the shape is out of range

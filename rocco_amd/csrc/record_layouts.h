@@ -32,6 +32,42 @@ struct CountLayout {
     }
 };
 
+// launch_alignment_chrom_range_batch: the K + 1 record offsets and unit offsets, per track the first / last index, the 2 K
+// values that go back
+struct RangeBatchLayout {
+    size_t rec_offsets, unit_first, first, last, range, bytes;
+    explicit RangeBatchLayout(size_t K)
+    {
+        Layout lay;
+        rec_offsets = lay.at((K + 1) * sizeof(long long));
+        unit_first = lay.at((K + 1) * sizeof(long long));
+        first = lay.at(K * sizeof(unsigned long long));
+        last = lay.at(K * sizeof(unsigned long long));
+        range = lay.at(2 * K * sizeof(long long));
+        bytes = lay.bytes();
+    }
+};
+
+// a track of track_supports_kernel: where its counts lie in the counter's output, how many, its file's norm_scale
+struct SupportTrack {
+    long long counts_offset, n_bins;
+    double norm_scale;
+};
+
+// launch_track_supports, behind the counter's own layout: the tracks, their K + 1 unit offsets, per track first / last
+struct SupportsLayout {
+    size_t tracks, unit_first, first, last, bytes;
+    explicit SupportsLayout(size_t K)
+    {
+        Layout lay;
+        tracks = lay.at(K * sizeof(SupportTrack));
+        unit_first = lay.at((K + 1) * sizeof(long long));
+        first = lay.at(K * sizeof(unsigned long long));
+        last = lay.at(K * sizeof(unsigned long long));
+        bytes = lay.bytes();
+    }
+};
+
 // launch_count_alignment_intervals: T tracks, `pairs` (interval, file) pairs, hipcub's scan over pairs + 1 unit counts
 struct IntervalLayout {
     size_t rec_offsets, facts, cand_lo, cand_n, units, unit_first, scan, bytes;

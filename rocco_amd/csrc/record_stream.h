@@ -49,10 +49,10 @@ __device__ __forceinline__ int wave_min(int v)
     return v;
 }
 
-// a thread's lowest index (~0: none) and highest index + 1 (0: none) over its wavefront, then into result[0] / result[1]
+// a thread's lowest index (~0: none) and highest index + 1 (0: none) over its wavefront, then into *first_out / *last_out
 // with one atomic each
 __device__ __forceinline__ void wave_first_last(unsigned long long first, unsigned long long last,
-                                                unsigned long long *__restrict__ result)
+                                                unsigned long long *__restrict__ first_out, unsigned long long *__restrict__ last_out)
 {
     for (int off = warpSize / 2; off > 0; off >>= 1) {
         const unsigned long long f = __shfl_xor(first, off), l = __shfl_xor(last, off);
@@ -61,12 +61,19 @@ __device__ __forceinline__ void wave_first_last(unsigned long long first, unsign
     }
     if ((threadIdx.x & (warpSize - 1)) == 0) {
         if (first != ~0ULL) {
-            atomicMin(&result[0], first);
+            atomicMin(first_out, first);
         }
         if (last != 0) {
-            atomicMax(&result[1], last);
+            atomicMax(last_out, last);
         }
     }
+}
+
+// ... into result[0] / result[1]
+__device__ __forceinline__ void wave_first_last(unsigned long long first, unsigned long long last,
+                                                unsigned long long *__restrict__ result)
+{
+    wave_first_last(first, last, result, result + 1);
 }
 
 // T in [1, 2^31), offsets from 0 upwards, every track with fewer than 2^31 records

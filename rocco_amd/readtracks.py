@@ -336,17 +336,11 @@ def _records_slice(records: AlignmentRecords, lo: int, hi: int) -> AlignmentReco
     return AlignmentRecords._of(*[None if a is None else a[lo:hi] for a in records._arrays()])
 
 
-def _count_concatenated(cat: AlignmentRecords, offsets: Sequence[int], regions: Sequence, options_list: Sequence,
-                        lengths: Optional[Sequence[int]] = None, into=None) -> Tuple[list, list]:
-    """`rocco_hip_count_alignment_records_batch` over device records already concatenated.  Returns (one float32 view per
-    track, the largest magnitude the kernels saw per track: `max_magnitude_out_host`); the caller applies the 2**24 guard."""
-    import torch
-
-    lib = _native.load()
-    K = len(offsets) - 1
+def _count_tables(K: int, regions: Sequence, options_list: Sequence, lengths: Optional[Sequence[int]] = None):
+    """The per-track arrays of the counting entry points: (options, regions, the offset of every track's counts in one
+    float32 buffer -- each a multiple of four --, the length of that buffer)."""
     if K <= 0 or len(regions) != K or len(options_list) != K:
         raise ValueError("one region and one set of options per track are required")
-    cat, rec_offsets, dev = _record_args(None, cat, offsets)
     opts = (CountOptions * K)()
     regs = (CountRegion * K)()
     out_offsets = (ctypes.c_longlong * K)()
@@ -364,6 +358,19 @@ def _count_concatenated(cat: AlignmentRecords, offsets: Sequence[int], regions: 
         regs[k] = CountRegion(start, end, step, bins)
         out_offsets[k] = total_bins
         total_bins += (bins + 3) // 4 * 4
+    return opts, regs, out_offsets, total_bins
+
+
+def _count_concatenated(cat: AlignmentRecords, offsets: Sequence[int], regions: Sequence, options_list: Sequence,
+                        lengths: Optional[Sequence[int]] = None, into=None) -> Tuple[list, list]:
+    """`rocco_hip_count_alignment_records_batch` over device records already concatenated.  Returns (one float32 view per
+    track, the largest magnitude the kernels saw per track: `max_magnitude_out_host`); the caller applies the 2**24 guard."""
+    import torch
+
+    lib = _native.load()
+    K = len(offsets) - 1
+    opts, regs, out_offsets, total_bins = _count_tables(K, regions, options_list, lengths)
+    cat, rec_offsets, dev = _record_args(None, cat, offsets)
     out = torch.zeros(total_bins, dtype=torch.float32, device=dev)
     views = [out[out_offsets[k]: out_offsets[k] + regs[k].n_bins] for k in range(K)]
     if into is not None:
@@ -513,6 +520,179 @@ def bam_chrom_reads_from_records(records: AlignmentRecords, chrom_size: int, ste
                                                          flag_exclude, center_reads, const_scale, round_digits, scale_by_step,
                                                          [bam_file], chromosome)
     return intervals[0], vals[0]
+
+
+# --------------------------------------------------------------------------------------------
+# K files of one chromosome -> its count matrix in one device pass (csrc/track_matrix.hip)
+# --------------------------------------------------------------------------------------------
+
+def track_matrix_shape() -> dict:
+    """`rocco_hip_track_matrix_shape`: the threads of a workgroup of the fill, the elements of a row it writes at a time, the
+    workgroups of one launch at most, the words of a row of its table.  No device is touched."""
+    shape = (ctypes.c_int * 4)()
+    _native.load().rocco_hip_track_matrix_shape(shape)
+    return {"threads": int(shape[0]), "unit": int(shape[1]), "max_grid": int(shape[2]), "row_words": int(shape[3])}
+
+
+def _merge_supports(grid_first, grid_last) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Supports ``[grid_first[k], grid_last[k]]`` (inclusive grid indices: start // step) merged into disjoint, ascending
+    segments: (grid index of every segment's first bin, column of that bin, number of columns).  Supports that overlap or
+    touch (``last + 1 == first``) form one segment; disjoint ones leave a gap -- the columns, laid end to end, are
+    ``np.unique(np.concatenate([arange(first, last + 1) ...]))``."""
+    first, last = np.asarray(grid_first, dtype=np.int64), np.asarray(grid_last, dtype=np.int64)
+    if first.ndim != 1 or first.shape != last.shape or first.size == 0 or np.any(last < first):
+        raise ValueError("supports must be non-empty [first, last] pairs")
+    order = np.argsort(first, kind="stable")
+    first, last = first[order], last[order]
+    reach = np.maximum.accumulate(last)             # the furthest bin of the supports up to this one
+    opens = np.ones(first.size, dtype=bool)
+    opens[1:] = first[1:] > reach[:-1] + 1          # a gap in front of this support: a segment begins
+    seg_first = first[opens]
+    seg_last = reach[np.append(np.flatnonzero(opens)[1:] - 1, first.size - 1)]
+    lengths = seg_last - seg_first + 1
+    seg_col = np.zeros(seg_first.size, dtype=np.int64)
+    np.cumsum(lengths[:-1], out=seg_col[1:])
+    return seg_first, seg_col, int(lengths.sum())
+
+
+def _segment_starts(seg_grid: np.ndarray, seg_col: np.ndarray, m: int, step: int) -> np.ndarray:
+    """The locus starts of the columns of `_merge_supports`' segments (an ``int`` array, as the reference returns it)."""
+    grid = np.arange(m, dtype=np.int64) + np.repeat(seg_grid - seg_col, np.diff(np.append(seg_col, m)))
+    return (grid * int(step)).astype(int)
+
+
+def _chrom_ranges_batch(cat: AlignmentRecords, offsets: Sequence[int], chrom_size: int, flag_exclude: int) -> list:
+    """`rocco_hip_alignment_chrom_range_batch`: [(chrom_start, chrom_end)] of K tracks already concatenated, one wait."""
+    K = len(offsets) - 1
+    cat, rec_offsets, dev = _record_args(None, cat, offsets)
+    ranges = (ctypes.c_longlong * (2 * K))()
+    _native.check(_native.load().rocco_hip_alignment_chrom_range_batch(
+        _native.solver_for(dev.index).handle, cat.pos.data_ptr(), cat.end.data_ptr(), cat.flag.data_ptr(), rec_offsets, K,
+        int(chrom_size), max(0, int(flag_exclude)) & 0xFFFF, ranges, _dp._stream_ptr(cat.pos)), "rocco_hip_alignment_chrom_range_batch")
+    return [(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(K)]
+
+
+def _emit(records: Sequence[tuple]) -> None:
+    """Log records collected during batched work, now, in their order: (level, message, args)."""
+    for level, message, args in records:
+        logger.log(level, message, *args)
+
+
+def _excluded_records(names: Sequence[str], has_data: Sequence[bool], chromosome: str) -> list:
+    """rocco/readtracks.py:601-613: one warning per file without data, in file order, and the last one when none has any."""
+    out = [(logging.WARNING, f"No data found for {name} in chromosome {chromosome}. Excluding this track for {chromosome}.", ())
+           for name, live in zip(names, has_data) if not live]
+    if not any(has_data):
+        out.append((logging.WARNING, f"No data found in the files {str(list(names))} for chromosome {chromosome}. Returning (None,None).", ()))
+    return out
+
+
+def _bam_matrix_batch(records_list, chrom_size, step, metadata_list, min_mapping_score, flag_include, flag_exclude, center_reads,
+                      const_scale, round_digits, scale_by_step, low_memory, names, chromosome):
+    """The work of `bam_chrom_matrix_from_records_batch` with its log records collected, not emitted: returns (starts or None,
+    matrix_t or None, the records of every file in the order the reference emits them for that file, whether it has data)."""
+    import torch
+
+    K = len(records_list)
+    chrom_size, step = int(chrom_size), int(step)
+    file_logs = [[] for _ in range(K)]
+    has_data = [False] * K
+    if K == 0:
+        return None, None, file_logs, has_data
+    lib = _native.load()
+    cat, offsets = _records_on_device(records_list, _device_for(records_list))
+    ranges = _chrom_ranges_batch(cat, offsets, chrom_size, flag_exclude)  # (the first of the call's two waits)
+    live, regions, options, scales = [], [], [], []
+    for k, (metadata, (chrom_start, chrom_end)) in enumerate(zip(metadata_list, ranges)):
+        if chrom_end <= chrom_start:
+            file_logs[k].append((logging.WARNING, "No mapped reads found in BAM file: %s for chromosome: %s. Returning (None,None).",
+                                 (names[k], chromosome)))
+            regions.append((0, 1, 1))  # (its place in the concatenated records stays; one bin nobody reads)
+            options.append(_count_options(0))
+            scales.append(0.0)
+            continue
+        live.append(k)
+        regions.append(_count_window(chrom_start, chrom_end, chrom_size, step) + (step,))
+        options.append(_count_options(int(metadata["read_length"]), one_read_per_bin=1 if center_reads else 0,
+                                      flag_include=max(0, int(flag_include or 0)), flag_exclude=max(0, int(flag_exclude)),
+                                      extend_bp=max(0, int(metadata["resolved_extend_bp"])),
+                                      paired_end_mode=1 if bool(metadata["paired_end_mode"]) else 0,
+                                      min_mapping_quality=max(0, int(min_mapping_score))))
+        scales.append(float(metadata["norm_scale"]))
+    if not live:
+        return None, None, file_logs, has_data
+    opts, regs, out_offsets, total_bins = _count_tables(K, regions, options)
+    cat, rec_offsets, dev = _record_args(None, cat, offsets)
+    counts = torch.empty(total_bins, dtype=torch.float32, device=dev)  # (the counter writes every bin a later kernel reads)
+    maxima, supports = (ctypes.c_longlong * K)(), (ctypes.c_longlong * (2 * K))()
+    solver, stream = _native.solver_for(dev.index), _dp._stream_ptr(counts)
+    _native.check(lib.rocco_hip_track_supports(
+        solver.handle, cat.pos.data_ptr(), cat.end.data_ptr(), cat.isize.data_ptr(), cat.flag.data_ptr(), cat.mapq.data_ptr(),
+        cat.mate_same.data_ptr(), rec_offsets, K, ctypes.cast(opts, ctypes.c_void_p), ctypes.cast(regs, ctypes.c_void_p), out_offsets,
+        (ctypes.c_double * K)(*scales), 1 if scale_by_step else 0, float(step), float(const_scale), counts.data_ptr(), maxima,
+        supports, stream), "rocco_hip_track_supports")  # (the second wait)
+    _check_exact_counts([int(maxima[k]) if k in live else 0 for k in range(K)])
+    rows = []
+    for k in live:
+        if scale_by_step:
+            file_logs[k].append((logging.INFO, f"Dividing `vals` by step size (bp): {step}", ()))
+        if const_scale >= 0 and const_scale == 0:
+            file_logs[k].append((logging.WARNING, "You are scaling the values by 0.", ()))
+        first, last = int(supports[2 * k]), int(supports[2 * k + 1])
+        if first < 0:
+            file_logs[k].append((logging.WARNING, "No non-zero values found in BAM file: %s for chromosome: %s. Returning (None,None).",
+                                 (names[k], chromosome)))
+            continue
+        has_data[k] = True
+        origin = regions[k][0] // step  # (count_start is a multiple of step: every track lies on one grid)
+        rows.append((int(out_offsets[k]), int(regs[k].n_bins), origin, origin + first, origin + last, scales[k]))
+    if not rows:
+        return None, None, file_logs, has_data
+    seg_grid, seg_col, m = _merge_supports([r[3] for r in rows], [r[4] for r in rows])
+    words = track_matrix_shape()["row_words"]
+    table = np.zeros(len(rows) * words + 2 * seg_grid.size, dtype=np.int64)
+    body = table[: len(rows) * words].reshape(len(rows), words)
+    body[:, :5] = np.asarray([r[:5] for r in rows], dtype=np.int64)
+    body[:, 5] = np.asarray([r[5] for r in rows], dtype=np.float64).view(np.int64)
+    table[len(rows) * words:] = np.stack([seg_grid, seg_col], axis=1).reshape(-1)
+    table_t = torch.from_numpy(table).to(dev)  # (at most K rows and K segments go up; nothing as long as the chromosome)
+    matrix = torch.empty((len(rows), m), dtype=torch.float32 if low_memory else torch.float64, device=dev)
+    _native.check(lib.rocco_hip_track_matrix_fill(
+        solver.handle, counts.data_ptr(), total_bins, table_t.data_ptr(), len(rows), table_t[len(rows) * words:].data_ptr(),
+        int(seg_grid.size), m, 1 if scale_by_step else 0, float(step), float(const_scale), int(round_digits), 1 if low_memory else 0,
+        matrix.data_ptr(), stream), "rocco_hip_track_matrix_fill")
+    return _segment_starts(seg_grid, seg_col, m, step), matrix, file_logs, has_data
+
+
+def bam_chrom_matrix_from_records_batch(records_list: Sequence[AlignmentRecords], chrom_size: int, step: int,
+                                        metadata_list: Sequence[dict], min_mapping_score: int = 10, flag_include=None,
+                                        flag_exclude: int = 3844, center_reads: bool = False, const_scale: float = 1.0,
+                                        round_digits: int = 5, scale_by_step: bool = False, low_memory: bool = False,
+                                        bam_files: Optional[Sequence[str]] = None, chromosome: str = ""):
+    """K decoded files of one chromosome to the reference's ``(common_intervals, count_matrix)`` in one device pass: what
+    ``generate_chrom_matrix`` does over BAM inputs after the metadata lookup (rocco/readtracks.py:439-518 per file, 601-633
+    over the files).  The ranges of all files come from one launch, the counting and the positive supports from one launch
+    series, and one kernel writes every element of the matrix once -- two waits for the device whatever K is, and neither
+    the values nor the starts of a track visit the host.  Returns (starts, matrix_t): the starts as a host ``int`` array
+    (built from at most K segments), the matrix as a CUDA tensor [K', m] (float64, float32 with ``low_memory``) of the K'
+    files that have data, bit for bit the reference's; ``(None, None)`` when no file has data.  The reference's log records
+    for the call are emitted after the batched work, in the reference's order: per file "No mapped reads...", the
+    ``Dividing `vals` by step size`` line, "You are scaling the values by 0.", "No non-zero values..."; then one "No data
+    found for ... Excluding..." per file without data and, when none has any, "No data found in the files ...".  RuntimeError
+    beyond 2**24 (`_check_exact_counts`)."""
+    K = len(records_list)
+    if len(metadata_list) != K:
+        raise ValueError("one metadata dict per file is required")
+    names = list(bam_files) if bam_files is not None else [""] * K
+    if len(names) != K:
+        raise ValueError("one file name per file is required")
+    starts, matrix, file_logs, has_data = _bam_matrix_batch(records_list, chrom_size, step, metadata_list, min_mapping_score,
+                                                            flag_include, flag_exclude, center_reads, const_scale, round_digits,
+                                                            scale_by_step, low_memory, names, chromosome)
+    for records in file_logs:
+        _emit(records)
+    _emit(_excluded_records(names, has_data, chromosome))
+    return starts, matrix
 
 
 # --------------------------------------------------------------------------------------------
