@@ -58,6 +58,7 @@ _ERROR_TEXT = {
 # ROCCO_BGZF_* of include/rocco_hip.h
 BGZF_THREADS, BGZF_TABLE_COLUMNS, BGZF_MAX_ISIZE, BGZF_STREAM_REASONS = 64, 5, 65536, 12
 BGZF_ERR_STREAM, BGZF_ERR_LENGTH, BGZF_ERR_CRC, BGZF_ERR_TABLE = range(1, 5)
+BGZF_MAX_GRID = 1 << 20  # workgroups of an inflate launch at most: block i + BGZF_MAX_GRID is the next turn of block i's workgroup
 _STREAM_REASON_TEXT = {
     1: "invalid block type", 2: "invalid stored block lengths", 3: "too many length or distance symbols", 4: "invalid code lengths set",
     5: "invalid bit length repeat", 6: "invalid code -- missing end-of-block", 7: "invalid literal/lengths set", 8: "invalid distances set",

@@ -24,7 +24,7 @@ namespace {
 
 constexpr int kWave = ROCCO_BGZF_THREADS;
 constexpr int kStage = 512;  // bytes of the compressed span kept in LDS in front of the bit reader
-constexpr long long kMaxGrid = 1 << 20;
+constexpr long long kMaxGrid = ROCCO_BGZF_MAX_GRID;  // workgroups of a launch at most: a later block is a workgroup's next turn
 
 static_assert(kWave == 64 && kCrcChunks == kWave, "one lane per CRC chunk; rocco_hip.h states the shape");
 

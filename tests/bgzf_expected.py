@@ -1,8 +1,10 @@
 """The cases the BGZF inflate of csrc/bgzf_inflate.hip / csrc/inflate_core.h is held against (note
 (29)), and what each of them must give.  Pure Python and NumPy: a BGZF writer over `zlib.compressobj`, a bit writer for
 streams zlib's compressor never emits, three case lists (valid files, corrupt files one per acceptance rule, seeded
-mutations), and the expected outcome of a block, which is the existing host path's: the bytes where
-`zlib.decompress(span, wbits=-15)` succeeds with the stated length and CRC32, else which of the three checks refused it."""
+mutations), a scanner that takes the census of what a stream makes a decoder do (`scan`, `census`) with the hand-assembled
+streams that fill its holes (`census_streams`), and the expected outcome of a block, which is the existing host path's: the
+bytes where `zlib.decompress(span, wbits=-15)` succeeds with the stated length and CRC32, else which of the three checks
+refused it -- and for a refused stream zlib's own reason (`stream_reason`)."""
 import struct
 import zlib
 
@@ -101,20 +103,35 @@ class Bits:
         self.code(lit[257 + ls]).value(length - LENGTH_BASE[ls], LENGTH_EXTRA[ls])
         return self.code(dist[ds]).value(distance - DIST_BASE[ds], DIST_EXTRA[ds])
 
+    def pair(self, length_symbol: int, length_extra: int, distance_symbol: int, distance_extra: int, lit=FIXED_LIT, dist=FIXED_DIST):
+        """A match stated by its two symbols (0 .. 28, 0 .. 29) and the values of their extra bits: also 258 as 27 with 31."""
+        assert 0 <= length_extra < 1 << LENGTH_EXTRA[length_symbol] and 0 <= distance_extra < 1 << DIST_EXTRA[distance_symbol]
+        self.code(lit[257 + length_symbol]).value(length_extra, LENGTH_EXTRA[length_symbol])
+        return self.code(dist[distance_symbol]).value(distance_extra, DIST_EXTRA[distance_symbol])
+
     def end(self, lit=FIXED_LIT):
         return self.code(lit[256])
 
     def header(self, final: int, kind: int):
         return self.value(final, 1).value(kind, 2)
 
-    def dynamic(self, final: int, lit_lengths, dist_lengths, ops=None, hlit=None, hdist=None):
+    def stored(self, final: int, data: bytes):
+        """A whole stored block: the header, the padding to a byte, LEN, NLEN and the bytes."""
+        self.header(final, 0).align().value(len(data), 16).value(~len(data) & 0xFFFF, 16)
+        for byte in data:
+            self.value(byte, 8)
+        return self
+
+    def dynamic(self, final: int, lit_lengths, dist_lengths, ops=None, hlit=None, hdist=None, cl_lengths=None):
         """A dynamic block's header.  The code-length code is a complete one over all 19 symbols (0 .. 12 in 4 bits, 13 .. 18
-        in 5); `ops`: the (symbol, extra value) sequence that states the lengths -- every length on its own where None."""
-        cl = canonical(CL_LENGTHS)
+        in 5), or the one with `cl_lengths`; `ops`: the (symbol, extra value) sequence that states the lengths -- every length
+        on its own where None."""
+        cl_lengths = CL_LENGTHS if cl_lengths is None else cl_lengths
+        cl = canonical(cl_lengths)
         self.header(final, 2).value((len(lit_lengths) if hlit is None else hlit) - 257, 5)
         self.value((len(dist_lengths) if hdist is None else hdist) - 1, 5).value(19 - 4, 4)
         for symbol in CODE_LENGTH_ORDER:
-            self.value(CL_LENGTHS[symbol], 3)
+            self.value(cl_lengths[symbol], 3)
         for symbol, extra in (ops if ops is not None else [(v, 0) for v in list(lit_lengths) + list(dist_lengths)]):
             self.code(cl[symbol]).value(extra, {16: 2, 17: 3, 18: 7}.get(symbol, 0))
         return self
@@ -191,6 +208,330 @@ def hand_streams():
     return out
 
 
+# ---- hand-assembled streams for what no other valid case makes a decoder do (`census` below says what that is) -------------------
+LANE_LENGTHS = (3, 63, 64, 65, 66, 67, 127, 128, 129, 257, 258)  # around one and two passes of 64 lanes, and the longest
+LANE_DISTANCES = (1, 2, 3, 5, 63, 64, 65, 127, 128, 129, 257, 258, 259)
+PAIR_ORDER = "ssffddsdfs"  # stored, fixed, dynamic: every ordered pair of block kinds once
+STAGE_OFFSETS = (-8, -7, -6, -5, -4, -3, 0, 2)  # of a stored LEN word, from a staging window's edge
+MAX_STORED = 0x10000 - 26 - 5  # the longest stored block `block` takes: 26 bytes of frame, 5 of stored header
+
+
+def stage_bytes() -> int:
+    """kStage of csrc/bgzf_inflate.hip: the bytes of a span that the kernel keeps in LDS in front of its bit reader."""
+    import os
+    import re
+
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rocco_amd", "csrc", "bgzf_inflate.hip")
+    with open(path) as handle:
+        (value,) = re.findall(r"constexpr int kStage = (\d+);", handle.read())
+    return int(value)
+
+
+def stage_edges():
+    """[(span offset of a stored LEN word, LEN)] of the staging streams: STAGE_OFFSETS around the first and the second window
+    edge with an empty stored block; 1 and 2 stored bytes where the bytes handed back reach below a window just staged."""
+    at = []
+    for edge in (stage_bytes(), 2 * stage_bytes()):
+        at += [(edge + off, 0) for off in STAGE_OFFSETS] + [(edge - 6, 1), (edge - 5, 2)]
+    return at
+
+
+def _skewed_literals(n: int, seed: int, first: int) -> bytes:
+    """n bytes of the 13 values first, first + 1, ...: each once, then value k with probability 2^-(k + 1) (its code has k + 1 bits)."""
+    picks = np.minimum(np.random.default_rng(seed).geometric(0.5, size=n - 13) - 1, 12)
+    return bytes(range(first, first + 13)) + bytes((first + picks).astype(np.uint8))
+
+
+def _reach(distance: int):
+    symbol = max(k for k in range(30) if DIST_BASE[k] <= distance)
+    return symbol, distance - DIST_BASE[symbol]
+
+
+_more_streams = None
+
+
+def census_streams():
+    """[(label, deflate data, the bytes zlib inflates it to)], built once: the streams `census` needs beside `hand_streams()`."""
+    global _more_streams
+    if _more_streams is not None:
+        return _more_streams
+    out = []
+    add = lambda label, cdata: out.append((label, cdata, zlib.decompress(cdata, wbits=-15)))
+    ones = lambda n: (1 << n) - 1
+
+    # long codes: literals in 1 .. 13 bits, 256 in 14, length symbols 27 and 28 (284, 285) in 15; distance symbols 0 .. 13 in
+    # 1 .. 14 bits (0 .. 11 used), 28 and 29 in 15.  32 768 literals, then 258 as 284 + 31 at 32 768 (15 + 5 + 15 + 13 = 48 bits)
+    lit = lengths(286, **{f"s{65 + k}": k + 1 for k in range(13)}, s256=14, s284=15, s285=15)
+    dist = list(range(1, 15)) + [0] * 14 + [15, 15]
+    lc, dc = canonical(lit), canonical(dist)
+    bits = Bits().dynamic(1, lit, dist)
+    for byte in _skewed_literals(32768, 71, 65):
+        bits.literal(byte, lc)
+    bits.pair(27, 31, 29, 8191, lc, dc).pair(28, 0, 29, 8191, lc, dc)  # 258 through 284 and through 285 at 32 768
+    bits.pair(27, 30, 29, 0, lc, dc).pair(27, 0, 28, 8191, lc, dc)  # 257 at 24 577, 227 at 24 576
+    for symbol in range(12):
+        for extra in sorted({0, ones(DIST_EXTRA[symbol])}):
+            bits.pair(27, (5 * symbol + extra) % 32, symbol, extra, lc, dc)
+    add("long codes: 15 bits on 284 and 285 and on distances 28 and 29, a 48-bit symbol last", bits.pair(27, 31, 29, 8191, lc, dc).end(lc).bytes())
+
+    # a second pair of sets: 15 bits on length symbols 20 and 26 (277, 283), distance symbols 26 .. 29 in 13, 14, 15, 15 bits
+    lit = lengths(284, **{f"s{97 + k}": k + 1 for k in range(13)}, s256=14, s277=15, s283=15)
+    dist = list(range(1, 13)) + [0] * 14 + [13, 14, 15, 15]
+    lc, dc = canonical(lit), canonical(dist)
+    bits = Bits().dynamic(1, lit, dist)
+    for byte in _skewed_literals(16384, 73, 97):
+        bits.literal(byte, lc)
+    for symbol in list(range(12)) + [26, 27]:
+        for extra in sorted({0, ones(DIST_EXTRA[symbol])}):
+            bits.pair(20, 15 if extra else 0, symbol, extra, lc, dc).pair(26, 0 if extra else 31, symbol, extra, lc, dc)
+    add("long codes: 15 bits on 277 and 283, distances 26 and 27 in 13 and 14 bits", bits.end(lc).bytes())
+
+    # the code-length code with lengths 1 .. 7 (the only complete one: 1 2 3 4 5 6 7 7, on the symbols 0 1 2 3 5 16 17 18):
+    # a 1, b 2, c 3, 256 .. 259 in 5 bits (a 5 and a 16 that repeats it three times), two distance codes of 1 bit
+    lit, dist = lengths(260, s97=1, s98=2, s99=3, s256=5, s257=5, s258=5, s259=5), [1, 1]
+    lc, dc = canonical(lit), canonical(dist)
+    cl = lengths(19, s0=1, s1=2, s2=3, s3=4, s5=5, s16=6, s17=7, s18=7)
+    ops = [(18, 97 - 11), (1, 0), (2, 0), (3, 0), (18, 138 - 11), (17, 10 - 3), (17, 7 - 3), (0, 0), (5, 0), (16, 0), (1, 0), (1, 0)]
+    bits = Bits().dynamic(1, lit, dist, ops=ops, cl_lengths=cl).literal(97, lc).literal(98, lc).literal(99, lc)
+    add("a code-length code with lengths 1 to 7", bits.match(3, 2, lc, dc).match(5, 1, lc, dc).end(lc).bytes())
+
+    # the fixed code: every length symbol with its extra bits all zeros and all ones (258 as 284 + 31 among them)
+    bits = Bits().header(1, 1)
+    for byte in random_bytes(300, 72):
+        bits.literal(byte)
+    turn = 0
+    for symbol in range(29):
+        for extra in sorted({0, ones(LENGTH_EXTRA[symbol])}):
+            bits.pair(symbol, extra, *_reach((1, 2, 3, 4, 7, 64, 100, 259, 300)[turn % 9]))
+            turn += 1
+    add("every length symbol at both ends of its extra bits", bits.end().bytes())
+
+    # ... and every distance symbol, behind 32 768 literals
+    bits = Bits().header(1, 1)
+    for byte in random_bytes(32768, 74):
+        bits.literal(byte)
+    turn = 0
+    for symbol in range(30):
+        for extra in sorted({0, ones(DIST_EXTRA[symbol])}):
+            bits.pair((0, 20, 28, 7)[turn % 4], 0, symbol, extra)
+            turn += 1
+    add("every distance symbol at both ends of its extra bits", bits.end().bytes())
+
+    # the lane copies: per distance one stream; every length behind `distance` fresh literals (the whole source was written
+    # since the last fence), then the same match again (its source is the first copy's bytes, or lies below them)
+    for distance in LANE_DISTANCES:
+        fresh = random_bytes(distance * len(LANE_LENGTHS), 500 + distance)
+        bits = Bits().header(1, 1)
+        for k, length in enumerate(LANE_LENGTHS):
+            for byte in fresh[k * distance: (k + 1) * distance]:
+                bits.literal(byte)
+            bits.match(length, distance).match(length, distance)
+        add(f"lane copies at distance {distance}: lengths {', '.join(map(str, LANE_LENGTHS))}, each twice", bits.end().bytes())
+
+    # all nine ordered pairs of block kinds in one stream, the second stored block empty
+    lit, one = lengths(258, s97=1, s256=2, s257=2), [1]
+    lc, dc = canonical(lit), canonical(one)
+    payloads = [b"hello", b"", b"xyz", b"pq"]
+    bits = Bits()
+    for k, kind in enumerate(PAIR_ORDER):
+        final = int(k == len(PAIR_ORDER) - 1)
+        if kind == "s":
+            bits.stored(final, payloads.pop(0))
+        elif kind == "f":
+            bits.header(final, 1).literal(48 + k).literal(200 + k).match(4 + k, 2).end()
+        else:
+            bits.dynamic(final, lit, one).literal(97, lc).match(3, 1, lc, dc).end(lc)
+    add("every ordered pair of block kinds: " + PAIR_ORDER, bits.bytes())
+
+    stored = lambda n: Bits().header(1, 0).align().value(n, 16).value(~n & 0xFFFF, 16).bytes()
+    add(f"the largest stored block: {MAX_STORED} bytes", stored(MAX_STORED) + random_bytes(MAX_STORED, 75))
+
+    # the staging window: literals of a fixed block, a stored block of 0 .. 2 bytes whose LEN word begins at span offset
+    # `at` (3 + 8 (at - 2) + 7 + 3 bits stand in front of it, padded to 8 at), a final fixed block
+    for at, n in stage_edges():
+        bits = Bits().header(0, 1)
+        for byte in np.random.default_rng(at).integers(0, 144, size=at - 2).tolist():  # (8 bits each)
+            bits.literal(byte)
+        bits.end().stored(0, b"<>"[:n]).header(1, 1)
+        for byte in b"behind the stored block":
+            bits.literal(byte)
+        add(f"a stored block of {n} bytes with LEN at span offset {at} (windows of {stage_bytes()} bytes)", bits.match(10, 5).end().bytes())
+    _more_streams = out
+    return out
+
+
+# ---- the census: what a stream makes a decoder do ----------------------------------------------------------------------------------
+def _decoder(code_lengths):
+    """(table, mask): table[the stream's next bits & mask] = symbol << 4 | code length, 0 where no code of the set begins."""
+    codes = canonical(code_lengths)
+    width = max((n for _, n in codes.values()), default=1)
+    table = np.zeros(1 << width, dtype=np.int64)
+    for symbol, (code, n) in codes.items():
+        table[int(format(code, f"0{n}b")[::-1], 2):: 1 << n] = symbol << 4 | n
+    return table.tolist(), (1 << width) - 1
+
+
+_FIXED_DECODERS = []
+
+
+def scan(cdata: bytes, trace=None):
+    """Walks a raw deflate stream that zlib accepts.  Returns (blocks, produced): per deflate block -- per code set -- a dict of
+    `kind` (s, f, d), `lit_bits` and `dist_bits` (the code lengths of the decoded literal/length and distance symbols),
+    `lengths` and `distances` ({(symbol, the value of its extra bits)}), `cl_bits` (the code-length code's lengths), `copies`
+    ({(length, distance)}), `repeats` (those that follow the same match directly), `widest` (the bits of its longest length and
+    distance symbol, extra bits included), `stored` ((the span offset of the LEN word, LEN) or None); and the bytes the stream
+    inflates to.  `trace`: a list that receives (what, first bit, one past its last)
+    of the fields a span can be cut in."""
+    n = len(cdata)
+    b = np.frombuffer(cdata + bytes(8), dtype=np.uint8).astype(np.int64)
+    words = (b[: n + 4] | b[1: n + 5] << 8 | b[2: n + 6] << 16 | b[3: n + 7] << 24).tolist()  # 25 bits from any bit position
+    p, produced, blocks = 0, 0, []
+    note = (lambda what, s, e: trace.append((what, s, e))) if trace is not None else (lambda what, s, e: None)
+
+    def take(k):
+        nonlocal p
+        v = (words[p >> 3] >> (p & 7)) & ((1 << k) - 1)
+        p += k
+        return v
+
+    def symbol_of(table, mask):
+        nonlocal p
+        entry = table[(words[p >> 3] >> (p & 7)) & mask]
+        if not entry:
+            raise ValueError("scan: no code of the set begins here")
+        p += entry & 15
+        return entry >> 4
+
+    final = 0
+    while not final:
+        final, kind = take(1), take(2)
+        block = dict(kind="sfd"[kind], lit_bits=set(), dist_bits=set(), lengths=set(), distances=set(), cl_bits=set(), copies=set(),
+                     repeats=set(), stored=None, widest=0)
+        blocks.append(block)
+        if kind == 0:
+            p += -p % 8
+            note("a stored LEN / NLEN", p, p + 32)
+            size, check = take(16), take(16)
+            if size != ~check & 0xFFFF:
+                raise ValueError("scan: LEN / NLEN")
+            block["stored"] = (p // 8 - 4, size)
+            p += 8 * size
+            produced += size
+        else:
+            if kind == 1:
+                if not _FIXED_DECODERS:
+                    _FIXED_DECODERS.extend([_decoder([8] * 144 + [9] * 112 + [7] * 24 + [8] * 8), _decoder([5] * 32)])
+                lit_lengths, dist_lengths = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8, [5] * 32
+                (lt, lm), (dt, dm) = _FIXED_DECODERS
+            else:
+                note("the HLIT / HDIST / HCLEN word", p, p + 14)
+                nlen, ndist, ncode = take(5) + 257, take(5) + 1, take(4) + 4
+                note("the code-length code's lengths", p, p + 3 * ncode)
+                cl = [0] * 19
+                for k in range(ncode):
+                    cl[CODE_LENGTH_ORDER[k]] = take(3)
+                block["cl_bits"] = {v for v in cl if v}
+                ct, cm = _decoder(cl)
+                stated = []
+                while len(stated) < nlen + ndist:
+                    symbol = symbol_of(ct, cm)
+                    if symbol < 16:
+                        stated.append(symbol)
+                    else:
+                        width = {16: 2, 17: 3, 18: 7}[symbol]
+                        note("a repeat code's extra bits", p, p + width)
+                        stated += [stated[-1] if symbol == 16 else 0] * ({16: 3, 17: 3, 18: 11}[symbol] + take(width))
+                if len(stated) != nlen + ndist:
+                    raise ValueError("scan: a repeat past the lengths")
+                lit_lengths, dist_lengths = stated[:nlen], stated[nlen:]
+                (lt, lm), (dt, dm) = _decoder(lit_lengths), _decoder(dist_lengths)
+            seen, dseen, before = [False] * 288, [False] * 32, None
+            lengths_seen, distances_seen, copies, repeats = block["lengths"], block["distances"], block["copies"], block["repeats"]
+            while True:
+                entry = lt[(words[p >> 3] >> (p & 7)) & lm]
+                if not entry:
+                    raise ValueError("scan: no code of the set begins here")
+                p += entry & 15
+                symbol = entry >> 4
+                seen[symbol] = True
+                if symbol < 256:
+                    produced += 1
+                    before = None
+                    continue
+                if symbol == 256:
+                    break
+                first = p - (entry & 15)
+                symbol -= 257
+                width = LENGTH_EXTRA[symbol]
+                extra = (words[p >> 3] >> (p & 7)) & ((1 << width) - 1)
+                p += width
+                at = p
+                entry = dt[(words[p >> 3] >> (p & 7)) & dm]
+                if not entry:
+                    raise ValueError("scan: no code of the set begins here")
+                p += entry & 15
+                dsymbol = entry >> 4
+                dseen[dsymbol] = True
+                dwidth = DIST_EXTRA[dsymbol]
+                dextra = (words[p >> 3] >> (p & 7)) & ((1 << dwidth) - 1)
+                p += dwidth
+                lengths_seen.add((symbol, extra))
+                distances_seen.add((dsymbol, dextra))
+                copy = (LENGTH_BASE[symbol] + extra, DIST_BASE[dsymbol] + dextra)
+                if copy[1] > produced:
+                    raise ValueError("scan: too far back")
+                copies.add(copy)
+                if copy == before:
+                    repeats.add(copy)
+                before = copy
+                produced += copy[0]
+                block["widest"] = max(block["widest"], p - first)
+                if trace is not None:
+                    trace += [("a length's extra bits", at - width, at), ("a distance code", at, p - dwidth), ("a distance's extra bits", p - dwidth, p),
+                              ("a length and distance symbol", first, p)]
+            block["lit_bits"] = {lit_lengths[k] for k in range(len(lit_lengths)) if seen[k]}
+            block["dist_bits"] = {dist_lengths[k] for k in range(len(dist_lengths)) if dseen[k]}
+        if p > 8 * n:
+            raise ValueError("scan: the stream ends inside a block")
+    return blocks, produced
+
+
+def cut_inside(cdata: bytes, what: str, bits=None) -> bytes:
+    """`cdata` up to the first byte boundary that lies inside a field `what` of `scan`'s trace (one of `bits` bits, if given)."""
+    trace = []
+    scan(cdata, trace)
+    for kind, first, last in trace:
+        cut = first // 8 * 8 + 8
+        if kind == what and first < cut < last and bits in (None, last - first):
+            return cdata[: cut // 8]
+    raise AssertionError(f"no field '{what}' of this stream straddles a byte boundary")
+
+
+def census(streams):
+    """What the raw deflate streams make a decoder do, together: `lit_bits`, `dist_bits`, `cl_bits` (the code lengths decoded),
+    `lengths` and `distances` ({(symbol, "zeros" or "ones")}: a symbol without extra bits counts as both), `through` (the
+    symbols 258 came through: 284, 285), `pairs` (the ordered pairs of block kinds that follow each other inside a stream),
+    `stored` ({(span offset of LEN, LEN)}), `copies` and `repeats` ({(length, distance)}), `widest` (the bits of the longest
+    length and distance symbol), `cl_sets` (the lengths of each code-length code, as frozensets)."""
+    total = dict(lit_bits=set(), dist_bits=set(), cl_bits=set(), lengths=set(), distances=set(), through=set(), pairs=set(), stored=set(),
+                 copies=set(), repeats=set(), widest=0, cl_sets=set())
+    for cdata in streams:
+        blocks, _ = scan(cdata)
+        for block in blocks:
+            total["widest"] = max(total["widest"], block["widest"])
+            total["cl_sets"].add(frozenset(block["cl_bits"]))
+            for name in ("lit_bits", "dist_bits", "cl_bits", "copies", "repeats"):
+                total[name] |= block[name]
+            for name, widths in (("lengths", LENGTH_EXTRA), ("distances", DIST_EXTRA)):
+                total[name] |= {(s, "zeros") for s, extra in block[name] if extra == 0}
+                total[name] |= {(s, "ones") for s, extra in block[name] if extra == (1 << widths[s]) - 1}
+            total["through"] |= {284 for pair in block["lengths"] if pair == (27, 31)} | {285 for s, _ in block["lengths"] if s == 28}
+            if block["stored"] is not None:
+                total["stored"].add(block["stored"])
+        total["pairs"] |= {(a["kind"], b["kind"]) for a, b in zip(blocks, blocks[1:])}
+    return total
+
+
 # ---- the valid files -------------------------------------------------------------------------------------------------------
 _valid = None
 
@@ -218,6 +559,18 @@ def valid_files():
                           packed(contents[kind][:40000], flushes=(1, 1000, 1001, 20000, 39999), flush_mode=getattr(zlib, name)) + EOF_BLOCK))
     for label, cdata, data in hand_streams():
         files.append((f"hand-assembled: {label}", around(cdata, data) + EOF_BLOCK))
+    lanes, edges = [], []
+    for label, cdata, data in census_streams():  # (one file each; the lane copies and the staging sweep as one file of many blocks)
+        if label.startswith("lane copies"):
+            lanes.append(around(cdata, data))
+        elif "with LEN at span offset" in label:
+            edges.append(around(cdata, data))
+        else:
+            files.append((f"hand-assembled: {label}", around(cdata, data) + EOF_BLOCK))
+    files.append((f"hand-assembled: lane copies at the distances {', '.join(map(str, LANE_DISTANCES))}, a block each", b"".join(lanes) + EOF_BLOCK))
+    files.append(("hand-assembled: stored blocks of (LEN bytes) with LEN at the span offsets " +
+                  ", ".join(f"{at} ({n})" for at, n in stage_edges()) + f", a block each; staging windows of {stage_bytes()} bytes",
+                  b"".join(edges) + EOF_BLOCK))
     small = [packed(text_bytes(100 + 7 * (k % 29), 100 + k % 13), level=(1, 6, 9)[k % 3]) if k % 3 else packed(record_bytes(150 + k % 200)[k % 50:])
              for k in range(600)]
     for count in (1, 2, 64, 65, 600):
@@ -287,6 +640,26 @@ def corrupt_blocks():
     return out
 
 
+def cut_blocks():
+    """[(label, one BGZF block that must be refused, ERR_STREAM)]: spans that end inside a field of a sound stream (`cut_inside`;
+    what zlib says of each is the reason `verify` asks of the decoder)."""
+    data = text_bytes(3000, 9)
+    good = deflate(data)
+    out = []
+    for what in ("a distance code", "a distance's extra bits", "a repeat code's extra bits", "the HLIT / HDIST / HCLEN word", "the code-length code's lengths"):
+        out.append((f"the span ends inside {what}", around(cut_inside(good, what), data), ERR_STREAM))
+    (cdata, symbols), = [(cdata, says) for label, cdata, says in census_streams() if label.startswith("every length symbol")]
+    out.append(("the span ends inside a length's extra bits", around(cut_inside(cdata, "a length's extra bits"), symbols), ERR_STREAM))
+    out.append(("the span ends inside a stored LEN / NLEN", around(cut_inside(deflate(data, level=0), "a stored LEN / NLEN"), data), ERR_STREAM))
+    label, cdata, long_data = census_streams()[0]
+    first = len(cut_inside(cdata, "a length and distance symbol", bits=48))  # (the first byte boundary inside the first such symbol)
+    for k in (0, 1, 4):
+        out.append((f"the long-code stream cut at the byte boundary {k + 1} of its first 48-bit symbol", around(cdata[: first + k], long_data), ERR_STREAM))
+    for k in (1, 2, 8):  # (its last symbol is one of 48 bits, the end-of-block code behind it one of 14)
+        out.append((f"the long-code stream cut {k} bytes short", around(cdata[:-k], long_data), ERR_STREAM))
+    return out
+
+
 def corrupt_files():
     """[(label, the bytes of a BGZF file, the index of the block that must be refused, the check that refuses it)], built once:
     every corrupt block between two sound ones, then the bad block first, in the middle and last in files of 3 and 65."""
@@ -304,6 +677,7 @@ def corrupt_files():
                 files.append((f"a {name} error {where} of {count} blocks", b"".join(body) + (EOF_BLOCK if code != ERR_CRC else b""), at, code))
     two = sound[:2] + [by_code[ERR_CRC], by_code[ERR_STREAM]] + sound[4:6]
     files.append(("a CRC32 error in front of a stream error: the first in file order", b"".join(two), 2, ERR_CRC))
+    files += [(label, sound[0] + bad + sound[1] + EOF_BLOCK, 1, code) for label, bad, code in cut_blocks()]
     _corrupt = files
     return files
 
@@ -343,6 +717,96 @@ def mutation_file():
     return _mutations
 
 
+MUTATIONS_LONG = 2500  # (zlib accepts 4 of the first 1 000 and 13 of these: such a mutation must fall into bits no rule reads)
+_mutations_long = None
+
+
+def mutation_file_long():
+    """One file of MUTATIONS_LONG blocks (its own seed): the same one-byte and one-bit mutations, of the streams of
+    `census_streams()` alone, every one of them."""
+    global _mutations_long
+    if _mutations_long is not None:
+        return _mutations_long
+    rng = np.random.default_rng(2026)
+    bases = [(cdata, data) for _, cdata, data in census_streams()]
+    out = []
+    for _ in range(MUTATIONS_LONG):
+        cdata, data = bases[int(rng.integers(0, len(bases)))]
+        changed = bytearray(cdata)
+        at = int(rng.integers(0, len(changed)))
+        if rng.random() < 0.5:
+            changed[at] ^= 1 << int(rng.integers(0, 8))
+        else:
+            changed[at] = int(rng.integers(0, 256))
+        out.append(around(bytes(changed), data))
+    _mutations_long = b"".join(out)
+    return _mutations_long
+
+
+# ---- the period of the launch-turn test ------------------------------------------------------------------------------------------
+def first_kind(span: bytes) -> str:
+    """The kind of a span's first deflate block: s, f, d (a fixed or a dynamic block begins by building tables), or 3."""
+    return "sfd3"[span[0] >> 1 & 3]
+
+
+def turn_period():
+    """(the bytes of a file of 15 small blocks, the indexes of those refused half-way): the period that the launch-turn test
+    tiles past ROCCO_BGZF_MAX_GRID rows.  A workgroup's next block is row i + cap, so in the tiled table the block at index p of
+    the period is followed, in its workgroup, by the one at (p + cap % 15) % 15.  The blocks are listed below in THAT order
+    and placed accordingly: sound ones of every kind and refused ones of every verdict, and behind each block that is refused
+    half-way -- with tables in LDS that it built and stopped using in mid-stream -- one that builds tables of its own:
+      a dynamic block cut inside a length and distance symbol (both sets built, codes of up to 15 bits) -> a dynamic block
+        whose distance set has one code;
+      a dynamic block cut inside its code lengths (the literal/length table still holds the code-length code) -> a dynamic
+        block with codes too long for the first-level tables (10 and 8 bits), decoded through the counts where the first-level
+        table must hold 0 and not what was there before;
+      a fixed block cut short -> a fixed block."""
+    from math import gcd
+
+    from rocco_amd import bam
+
+    hand = {label: (cdata, data) for label, cdata, data in hand_streams() + census_streams()}
+    text, records = text_bytes(90, 3), record_bytes(60)
+    # literals in 1 .. 13 bits, 256 in 14, 284 in 15, distance symbol 9 in 10
+    lit = lengths(286, **{f"s{65 + k}": k + 1 for k in range(13)}, s256=14, s284=15, s285=15)
+    dist = list(range(1, 15)) + [0] * 14 + [15, 15]
+    lc, dc = canonical(lit), canonical(dist)
+    long_codes = Bits().dynamic(1, lit, dist)
+    for byte in 2 * bytes(range(65, 78)):
+        long_codes.literal(byte, lc)
+    long_codes = long_codes.pair(27, 0, 9, 0, lc, dc).end(lc).bytes()  # (the pair: 15 + 5 + 10 + 3 bits, the end: 14)
+    long_data = zlib.decompress(long_codes, wbits=-15)
+    assert len(long_data) == 26 + 227
+    repeats, repeats_data = hand["repeat codes 16, 17, 18 across the literal/distance boundary"]
+    fixed = deflate(text[:40], strategy=zlib.Z_FIXED)
+    chain = [("s", packed(records, level=0)),
+             ("3", around(Bits().header(1, 3).bytes(), b"abc")),                                                  # refused: block type 3
+             ("d", packed(text, level=9)),
+             ("d", around(long_codes[:-3], long_data)),                                                           # refused half-way
+             ("d", around(*hand["a distance set of one code, used"])),
+             ("d", block(deflate(text), zlib.crc32(text), len(text) - 1)),                                        # refused: length
+             ("f", EOF_BLOCK),                                                                                    # empty
+             ("d", around(cut_inside(repeats, "a repeat code's extra bits"), repeats_data)),                      # refused half-way
+             ("d", around(long_codes, long_data)),
+             ("s", block(deflate(records, level=0), zlib.crc32(records) ^ 0x80, len(records))),                   # refused: CRC32
+             ("d", around(*hand["a literal/length set of one code, an empty distance set"])),
+             ("f", around(fixed[: len(fixed) // 2], text[:40])),                                                  # refused half-way
+             ("f", packed(text[:40], strategy=zlib.Z_FIXED)),
+             ("d", around(*hand["a code-length code with lengths 1 to 7"])),
+             ("d", around(repeats, repeats_data))]
+    half_way = (3, 7, 11)
+    n = len(chain)
+    step = bam.BGZF_MAX_GRID % n
+    assert n % 2 == 1 and gcd(step, n) == 1  # (every block of the period is some workgroup's next after every other turn)
+    blocks, placed = [None] * n, []
+    for j, (kind, one) in enumerate(chain):
+        blocks[j * step % n] = one
+        assert first_kind(one[18:]) == kind, j  # (a block without extra subfields: its deflate data begins at byte 18)
+        if j in half_way:
+            placed.append(j * step % n)
+    return b"".join(blocks), sorted(placed)
+
+
 # ---- what a file must give -----------------------------------------------------------------------------------------------------
 def blocks_of(raw: bytes):
     """`rocco_amd.bam._bgzf_blocks`: (file offset, first byte of the deflate data, one past its last, CRC32, ISIZE) per block."""
@@ -362,6 +826,28 @@ def outcomes(raw: bytes):
             continue
         out.append((ERR_LENGTH, None) if len(data) != isize else ((ERR_CRC, None) if zlib.crc32(data) != crc else (0, data)))
     return out
+
+
+def stream_reason(span: bytes) -> str:
+    """zlib's own words for a span it refuses: the tail of its message behind "data: "."""
+    try:
+        zlib.decompress(span, wbits=-15)
+    except zlib.error as exc:
+        text = str(exc)
+        assert "data: " in text, text
+        return text[text.index("data: ") + 6:]
+    raise AssertionError("zlib accepts this span")
+
+
+def expected_statuses(raw: bytes) -> np.ndarray:
+    """The int32 status word per block: the verdict of `outcomes`, and for a stream error the number of zlib's reason
+    (`rocco_amd.bam._STREAM_REASON_TEXT`) in bits 8 and up."""
+    from rocco_amd import bam
+
+    number = {text: why for why, text in bam._STREAM_REASON_TEXT.items()}
+    rows = blocks_of(raw)
+    return np.asarray([code | (number[stream_reason(raw[rows[k][1]: rows[k][2]])] << 8 if code == ERR_STREAM else 0)
+                       for k, (code, _) in enumerate(outcomes(raw))], dtype=np.int32)
 
 
 def table_of(raw: bytes) -> np.ndarray:
@@ -394,17 +880,26 @@ def guarded_table(raw: bytes):
 
 
 def verify(raw: bytes, table: np.ndarray, status: np.ndarray, out: np.ndarray, label: str = "") -> int:
-    """`status` and `out` (filled with GUARD_BYTE before the call) against `outcomes(raw)`: every block's status code, the bytes
-    of every accepted block, and not one byte changed outside the blocks' ranges.  Returns the index of the first refused
-    block or -1."""
+    """`status` and `out` (filled with GUARD_BYTE before the call) against `outcomes(raw)`: every block's status code, for a
+    stream error the reason in zlib's own words for that span (`stream_reason`; no reason with any other verdict), the bytes of
+    every accepted block, and not one byte changed outside the blocks' ranges.  Returns the index of the first refused block
+    or -1."""
+    from rocco_amd import bam
+
     want = outcomes(raw)
+    rows = blocks_of(raw)
     assert len(want) == table.shape[0] == status.shape[0], label
     inside = np.zeros(out.shape[0], dtype=bool)
     first = -1
     for k, (code, data) in enumerate(want):
         at, isize = int(table[k, 4]), int(table[k, 2])
         inside[at: at + isize] = True
-        assert int(status[k]) & 0xFF == code and (code == ERR_STREAM) == (int(status[k]) >> 8 != 0), (label, k, int(status[k]), code)
+        assert int(status[k]) & 0xFF == code, (label, k, int(status[k]), code)
+        if code == ERR_STREAM:
+            says, zlib_says = bam._STREAM_REASON_TEXT.get(int(status[k]) >> 8), stream_reason(raw[rows[k][1]: rows[k][2]])
+            assert says == zlib_says, (label, k, int(status[k]), says, zlib_says)
+        else:
+            assert int(status[k]) >> 8 == 0, (label, k, int(status[k]), code)
         if code == 0:
             assert out[at: at + isize].tobytes() == data, (label, k)
         elif first < 0:

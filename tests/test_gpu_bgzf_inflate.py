@@ -50,16 +50,28 @@ def test_valid_files_byte_for_byte(gpu):
 
 def test_corrupt_files_raise_the_hosts_errors(gpu):
     """One file per acceptance rule and per place of the bad block: a ValueError with the host's prefix (block index, file
-    offset) and the host's leading words, whole and slab by slab."""
+    offset) and the host's leading words, whole and slab by slab; for a stream error the text between the parentheses is the
+    tail of the host's, zlib's own words for that span."""
+    import re
+
     from rocco_amd import bam
 
+    between = lambda info: re.search(r"the deflate stream does not inflate \((.*)\)$", str(info.value)).group(1)
+    stream_errors = 0
     for label, raw, index, code in gx.corrupt_files():
         pattern = gx.error_pattern(raw, index, code)
-        with pytest.raises(ValueError, match=pattern):
+        with pytest.raises(ValueError, match=pattern) as whole:
             bam.inflate_bgzf_device(raw, device=gpu)
-        with pytest.raises(ValueError, match=pattern):
+        with pytest.raises(ValueError, match=pattern) as by_slab:
             for _ in bam.inflate_bgzf_device(raw, device=gpu, slab_bytes=1):
                 pass
+        if code == gx.ERR_STREAM:
+            with pytest.raises(ValueError, match=pattern) as host:
+                bam.inflate_bgzf(raw)
+            assert "data: " in between(host), label
+            assert between(whole) == between(by_slab) == between(host).split("data: ", 1)[1], label
+            stream_errors += 1
+    assert stream_errors >= 40
     big = gx.block(gx.deflate(b"abc"), 0, 65537) + gx.EOF_BLOCK
     with pytest.raises(ValueError, match=r"BGZF block 0 at file offset 0: length mismatch \(ISIZE says 65537, "):
         bam.inflate_bgzf_device(big, device=gpu)
@@ -87,6 +99,59 @@ def test_mutation_set_in_one_call(gpu):
     raw = gx.mutation_file()
     assert len(gx.blocks_of(raw)) == gx.MUTATIONS
     run_device(gpu, raw, "mutations")
+
+
+def test_long_mutation_set_in_one_call(gpu):
+    """The second mutation set (of the census streams: long codes, every symbol, lane-copy shapes, block-kind pairs, stored
+    blocks on the staging window's edges) as one file: status, reason and bytes block by block against zlib; none excluded."""
+    raw = gx.mutation_file_long()
+    assert len(gx.blocks_of(raw)) == gx.MUTATIONS_LONG
+    run_device(gpu, raw, "long mutations")
+
+
+def test_a_workgroups_later_turns(gpu):
+    """More blocks than ROCCO_BGZF_MAX_GRID workgroups in one call: block i + cap is the next turn of the workgroup that took
+    block i, over the tables, the staging window and the decoder state that block left in LDS.  The table tiles the period of
+    `gx.turn_period()` (15 blocks, ordered by that succession: checked here from the cap) over the same few hundred compressed
+    bytes, every row with an output range of its own between guard bytes.  Expected: zlib's verdicts and reasons of the period,
+    tiled; the bytes of the first period, verified against zlib, in every period; the guards untouched; the first refused row."""
+    import torch
+
+    from rocco_amd import bam
+
+    raw, half_way = gx.turn_period()
+    first, span = gx.guarded_table(raw)
+    period = first.shape[0]
+    step = span - gx.GUARD  # a period's bytes: GUARD in front of each block's range; one more GUARD closes the buffer
+    want = gx.expected_statuses(raw)
+    assert period == 15 and len(raw) < 1500 and int(first[:, 2].max()) < 300
+    assert sorted(set(want.tolist())) == sorted({0, gx.ERR_STREAM | 1 << 8, gx.ERR_STREAM | 12 << 8, gx.ERR_LENGTH, gx.ERR_CRC})
+    # what a workgroup takes after the block at index p of the period: another block, and one that builds tables of its own
+    # (the first a fixed, the others a dynamic block) wherever p was refused half-way -- truncated -- with tables built
+    spans = [raw[int(lo): int(hi)] for lo, hi in first[:, :2]]
+    after = [(p + bam.BGZF_MAX_GRID % period) % period for p in range(period)]
+    assert all(spans[p] != spans[after[p]] for p in range(period)) and len(half_way) == 3
+    for p in half_way:
+        assert int(want[p]) == gx.ERR_STREAM | 12 << 8 and gx.first_kind(spans[p]) in "fd" and len(spans[p]) > 8, p
+        assert int(want[after[p]]) == 0 and gx.first_kind(spans[after[p]]) in "fd", p
+    assert sorted(gx.first_kind(spans[after[p]]) for p in half_way) == ["d", "d", "f"]
+    periods = (bam.BGZF_MAX_GRID + 4000) // period + 1
+    assert periods * period > bam.BGZF_MAX_GRID + 4000
+    table = np.tile(first, (periods, 1, 1))
+    table[:, :, 4] += (np.arange(periods, dtype=np.int64) * step)[:, None]
+    n_out = periods * step + gx.GUARD
+    out = torch.full((n_out,), gx.GUARD_BYTE, dtype=torch.uint8, device=gpu)
+    comp = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(gpu)
+    status, report = bam.inflate_blocks_device(comp, torch.from_numpy(table.reshape(-1, 5)).to(gpu), out, want_status=True)
+    head = out[: step + gx.GUARD].cpu().numpy()
+    refused = int(np.flatnonzero(want)[0])
+    assert gx.verify(raw, first, status[:period].cpu().numpy(), head, "the first period") == refused
+    assert report["block"] == refused and report["status"] == int(want[refused])
+    assert torch.equal(status.view(periods, period), torch.from_numpy(want).to(gpu).expand(periods, period))
+    tiled = out[: periods * step].view(periods, step)
+    different = (tiled != tiled[0]).any(dim=1)
+    assert not bool(different.any()), ("the first period whose bytes differ", int(different.nonzero()[0]))
+    assert bool((out[periods * step:] == gx.GUARD_BYTE).all())
 
 
 def test_rows_outside_the_buffers_are_refused(gpu):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Writes every case of tests/bgzf_expected.py (valid files, corrupt files, the mutation set) as a `.case` file for
+"""Writes every case of tests/bgzf_expected.py (valid files, corrupt files, both mutation sets, the launch-turn period) as a `.case` file for
 tests/tools/bgzf_inflate_san.cpp, the stand-alone sanitizer run of rocco_amd/csrc/inflate_core.h:
 
     python tests/tools/bgzf_inflate_cases.py DIR
@@ -19,7 +19,7 @@ import bgzf_expected as gx  # noqa: E402
 def main():
     out_dir = sys.argv[1]
     os.makedirs(out_dir, exist_ok=True)
-    files = [raw for _, raw in gx.valid_files()] + [raw for _, raw, _, _ in gx.corrupt_files()] + [gx.mutation_file()]
+    files = [raw for _, raw in gx.valid_files()] + [raw for _, raw, _, _ in gx.corrupt_files()] + [gx.mutation_file(), gx.mutation_file_long(), gx.turn_period()[0]]
     for k, raw in enumerate(files):
         table = gx.table_of(raw)
         want = np.asarray([code for code, _ in gx.outcomes(raw)], dtype=np.uint8)
