@@ -942,6 +942,52 @@ int rocco_hip_bgzf_inflate_host(rocco_hip_solver *solver, const uint8_t *comp, s
                                 uint8_t *out, size_t n_out, int32_t *status_out, int64_t *report_out);
 void rocco_hip_bgzf_shape(int *shape_out);
 
+/* ---- the data blocks of a bigWig file -> their inflated bytes (note (31)) -----------------
+ * What libBigWig has zlib's uncompress() do per data block when pyBigWig's intervals() calls bwGetOverlappingIntervals:
+ * check the two header bytes of the zlib stream (RFC 1950), inflate its deflate data, compare the Adler-32 of the bytes with
+ * the four big-endian bytes behind the stream.  The container is walked on the host (rocco_amd/bigwig.py), which states
+ * every block as one row of the block table:
+ *   table_dev: int64 [n_blocks][ROCCO_ZLIB_TABLE_COLUMNS], a row = { the first byte of the zlib stream in comp_dev, one past
+ *   its last, the capacity of its slot (the file's uncompressBufSize), the offset of its slot in out_dev (the host's stride:
+ *   the capacity rounded up to 8), framing }.  Framing 0: a zlib stream.  Framing 1: stored as it is (a file whose
+ *   uncompressBufSize is 0): the span's bytes are copied and produced is the span's length.
+ *
+ * rocco_hip_zlib_inflate: every block is taken by one wavefront of ROCCO_BGZF_THREADS lanes (a grid stride under
+ *   ROCCO_ZLIB_MAX_GRID workgroups).  The header is judged as zlib 1.2.11's inflate() does with wbits = 15: (CMF * 256 + FLG)
+ *   % 31 != 0 is "incorrect header check" (reason 1), CM != 8 "unknown compression method" (2), CINFO > 7 "invalid window
+ *   size" (3), FDICT set is refused (4: zlib would ask for a dictionary).  The deflate data is decoded by the decoder of
+ *   rocco_hip_bgzf_inflate (the same rules, the same reasons) into out_dev[offset, offset + capacity); a second kernel takes
+ *   the Adler-32 of the produced bytes (64 contiguous chunks, one per lane, combined as zlib's adler32_combine does) and
+ *   compares it with the four bytes at the stream's end -- the byte behind the last bit of the final deflate block.  Fewer
+ *   than four bytes there (or fewer than two for the header, or fewer than four behind FDICT) is zlib's "incomplete or
+ *   truncated stream"; bytes behind the Adler-32 are ignored, as uncompress() ignores them.  Every load is bounded by the
+ *   row's span, every store by its slot: a stream that inflates to more than the capacity is followed to its end without
+ *   storing.  A row is refused (ROCCO_BGZF_ERR_TABLE, nothing of it read or written) unless 0 <= first <= last <= n_comp,
+ *   0 <= capacity <= ROCCO_BGZF_MAX_ISIZE, [offset, offset + capacity) lies in [0, n_out) and framing is 0 or 1.
+ *   status_out_dev (optional, int32 per block): 0, ROCCO_BGZF_ERR_STREAM | reason << 8, ROCCO_BGZF_ERR_LENGTH (sound, and
+ *   inflates to MORE than the capacity: produced <= capacity is accepted), ROCCO_BGZF_ERR_TABLE, ROCCO_ZLIB_ERR_HEADER |
+ *   reason << 8, ROCCO_ZLIB_ERR_TRUNCATED or ROCCO_ZLIB_ERR_ADLER; where several hold: header, stream, truncated, length,
+ *   Adler.  produced_out_dev (optional, int64 per block): the bytes the block inflates to (0 where the header or the stream
+ *   is refused).  report_out_host, ROCCO_BGZF_REPORT int64: [0] the first failing block in table order or -1, [1] its
+ *   status, [2] the bytes it inflates to.  The bytes of failing blocks are unspecified inside their own slot.  Synchronises
+ *   once, at its end.  n_blocks = 0 is a valid call.
+ * rocco_hip_zlib_inflate_host: test support, as rocco_hip_bgzf_inflate_host is: the same rows over HOST memory on the
+ *   calling thread, from the same source (csrc/inflate_core.h compiled for the host); solver may be NULL.
+ * rocco_hip_zlib_shape: shape_out[0..4] = ROCCO_BGZF_THREADS, ROCCO_ZLIB_TABLE_COLUMNS, ROCCO_BGZF_MAX_ISIZE,
+ *   ROCCO_ZLIB_HEADER_REASONS, ROCCO_ZLIB_MAX_GRID. */
+#define ROCCO_ZLIB_TABLE_COLUMNS 5
+#define ROCCO_ZLIB_HEADER_REASONS 4
+#define ROCCO_ZLIB_ERR_HEADER 5
+#define ROCCO_ZLIB_ERR_ADLER 6
+#define ROCCO_ZLIB_ERR_TRUNCATED 7
+#define ROCCO_ZLIB_MAX_GRID (1 << 16) /* workgroups of zlib_inflate_kernel and zlib_adler_kernel at most; unit: one data block */
+int rocco_hip_zlib_inflate(rocco_hip_solver *solver, const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks,
+                           uint8_t *out_dev, size_t n_out, int32_t *status_out_dev, int64_t *produced_out_dev, int64_t *report_out_host,
+                           void *stream);
+int rocco_hip_zlib_inflate_host(rocco_hip_solver *solver, const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks,
+                                uint8_t *out, size_t n_out, int32_t *status_out, int64_t *produced_out, int64_t *report_out);
+void rocco_hip_zlib_shape(int *shape_out);
+
 /* ---- the grid caps of the record and select kernels -----------------------------------------------------------------
  * Every kernel behind the data front end caps its grid; past cap x unit a workgroup takes several units in turn (a grid
  * stride).  The caps are stated here once, the .hip files are built to them, and rocco_hip_launch_caps hands them to the

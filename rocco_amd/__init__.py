@@ -59,6 +59,11 @@ from .bam import (  # noqa: F401  (htslib's BGZF reader, bam_read1, bam_endpos, 
     parse_bam_header,
     read_alignment_file,
 )
+from .bigwig import (  # noqa: F401  (the data blocks libBigWig inflates behind pyBigWig's intervals())
+    clear_bigwig_cache,
+    open_bigwig,
+    read_bigwig_blocks,
+)
 from .rocco import (  # noqa: F401
     chrom_solution_to_bed,
     combine_chrom_results,

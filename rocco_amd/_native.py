@@ -334,6 +334,14 @@ PROTOTYPES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
       ctypes.c_void_p, c_ll_p]),
     ("rocco_hip_bgzf_shape", None, [c_int_p]),
+    # row f10 (csrc/bgzf_inflate.hip, csrc/inflate_core.h): zlib's uncompress as libBigWig calls it per data block
+    ("rocco_hip_zlib_inflate", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_zlib_inflate_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_void_p, c_ll_p]),
+    ("rocco_hip_zlib_shape", None, [c_int_p]),
     # (no reference line: the grid caps of the record and select kernels, for the tests that go past one launch's first turn)
     ("rocco_hip_launch_caps", None, [c_int_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,

@@ -1777,6 +1777,43 @@ void rocco_hip_bgzf_shape(int *shape_out)
     shape_out[3] = ROCCO_BGZF_STREAM_REASONS;
 }
 
+int rocco_hip_zlib_inflate(rocco_hip_solver *solver, const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks,
+                           uint8_t *out_dev, size_t n_out, int32_t *status_out_dev, int64_t *produced_out_dev, int64_t *report_out_host,
+                           void *stream)
+{
+    if (solver == nullptr || report_out_host == nullptr || n_blocks >= (size_t)0x7fffffff || n_comp >= ((size_t)1 << 62) ||
+        n_out >= ((size_t)1 << 62) || (n_blocks > 0 && table_dev == nullptr) || (n_comp > 0 && comp_dev == nullptr) ||
+        (n_out > 0 && out_dev == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, zlib_inflate_scratch_bytes(n_blocks)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_zlib_inflate(comp_dev, n_comp, table_dev, n_blocks, out_dev, n_out, status_out_dev, produced_out_dev, report_out_host,
+                               solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_zlib_inflate_host(rocco_hip_solver *solver, const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks,
+                                uint8_t *out, size_t n_out, int32_t *status_out, int64_t *produced_out, int64_t *report_out)
+{
+    (void)solver;
+    if (report_out == nullptr || n_blocks >= (size_t)0x7fffffff || n_comp >= ((size_t)1 << 62) || n_out >= ((size_t)1 << 62) ||
+        (n_blocks > 0 && table == nullptr) || (n_comp > 0 && comp == nullptr) || (n_out > 0 && out == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    zlib_inflate_host_blocks(comp, n_comp, table, n_blocks, out, n_out, status_out, produced_out, report_out);
+    return ROCCO_HIP_OK;
+}
+
+void rocco_hip_zlib_shape(int *shape_out)
+{
+    shape_out[0] = ROCCO_BGZF_THREADS;
+    shape_out[1] = ROCCO_ZLIB_TABLE_COLUMNS;
+    shape_out[2] = ROCCO_BGZF_MAX_ISIZE;
+    shape_out[3] = ROCCO_ZLIB_HEADER_REASONS;
+    shape_out[4] = ROCCO_ZLIB_MAX_GRID;
+}
+
 void rocco_hip_launch_caps(int *out)
 {
     const int caps[] = {ROCCO_SELECT_GRID_TARGET,      ROCCO_SELECT_CHUNK_VALUES,     ROCCO_SELECT_THREADS,           ROCCO_BH_MAX_GRID,

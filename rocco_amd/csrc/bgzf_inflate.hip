@@ -141,7 +141,117 @@ __global__ void bgzf_report_kernel(const unsigned long long *__restrict__ first_
     report[3] = 0;
 }
 
+// ---- zlib framing: the data blocks of a bigWig file (note (31)) ------------------------------------------
+constexpr long long kZlibMaxGrid = ROCCO_ZLIB_MAX_GRID;
+
+// one wavefront per block (grid stride): the header, the stream, the room for the check value, the length; a stored row is
+// copied.  status[i] == 0 with framing 0: the Adler-32 is still to be compared, at comp[ends[i]]
+__global__ __launch_bounds__(kWave) void zlib_inflate_kernel(const uint8_t *__restrict__ comp, long long n_comp,
+                                                            const int64_t *__restrict__ table, long long n_blocks, uint8_t *out,
+                                                            long long n_out, int *__restrict__ status, long long *__restrict__ produced,
+                                                            long long *__restrict__ ends, unsigned long long *__restrict__ first_error)
+{
+    __shared__ InflateTables tables;
+    __shared__ uint8_t stage[kStage];
+    for (long long i = blockIdx.x; i < n_blocks; i += gridDim.x) {
+        int64_t row[ROCCO_ZLIB_TABLE_COLUMNS];
+        for (int k = 0; k < ROCCO_ZLIB_TABLE_COLUMNS; ++k) {
+            row[k] = table[i * ROCCO_ZLIB_TABLE_COLUMNS + k];
+        }
+        int result = ROCCO_BGZF_ERR_TABLE;
+        long long made = 0, end = 0;
+        if (zlib_row_fits(row, n_comp, n_out)) {
+            DeviceInflateExec x = {comp, row[1], stage, row[1], (int)threadIdx.x};
+            result = zlib_block(x, tables, row, out + row[3], &made, &end);
+        }
+        if (threadIdx.x == 0) {
+            status[i] = result;
+            produced[i] = made;
+            ends[i] = end;
+            if (result != 0) {
+                note_first(first_error, i, result);
+            }
+        }
+    }
+}
+
+// one wavefront per sound zlib block: lane c takes chunk c of its produced bytes, the 64 Adler-32s are combined pairwise
+__global__ __launch_bounds__(kWave) void zlib_adler_kernel(const uint8_t *__restrict__ comp, const int64_t *__restrict__ table,
+                                                          long long n_blocks, const uint8_t *__restrict__ out, int *__restrict__ status,
+                                                          const long long *__restrict__ produced, const long long *__restrict__ ends,
+                                                          unsigned long long *__restrict__ first_error)
+{
+    const int lane = threadIdx.x;
+    for (long long i = blockIdx.x; i < n_blocks; i += gridDim.x) {
+        const int64_t *row = table + i * ROCCO_ZLIB_TABLE_COLUMNS;
+        if (status[i] != 0 || row[4] != 0) {  // (a row that does not fit is among them: nothing of it is read)
+            continue;
+        }
+        long long first, length;
+        crc_chunk(produced[i], lane, &first, &length);  // (status 0: produced <= capacity, the chunk lies in the slot)
+        uint32_t adler = adler_of_bytes(out + row[3] + first, length);
+        for (int step = 1; step < kWave; step <<= 1) {
+            const uint32_t adler_right = __shfl_down(adler, step);
+            const long long length_right = __shfl_down(length, step);
+            if ((lane & (2 * step - 1)) == 0) {
+                adler = adler_combine(adler, adler_right, length_right);
+                length += length_right;
+            }
+        }
+        if (lane == 0 && adler != zlib_stated_adler(comp, ends[i])) {  // (status 0: ends + 4 <= the span's end)
+            status[i] = ROCCO_ZLIB_ERR_ADLER;
+            note_first(first_error, i, ROCCO_ZLIB_ERR_ADLER);
+        }
+    }
+}
+
 }  // namespace
+
+size_t zlib_inflate_scratch_bytes(size_t n_blocks) { return ZlibInflateLayout(n_blocks).bytes; }
+
+int launch_zlib_inflate(const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks, uint8_t *out_dev, size_t n_out,
+                        int32_t *status_out_dev, int64_t *produced_out_dev, int64_t *report_out_host, void *scratch_dev, hipStream_t stream)
+{
+    const ZlibInflateLayout at(n_blocks);
+    char *sc = (char *)scratch_dev;
+    int *status = status_out_dev != nullptr ? status_out_dev : (int *)(sc + at.status);
+    long long *produced = produced_out_dev != nullptr ? (long long *)produced_out_dev : (long long *)(sc + at.produced);
+    long long *ends = (long long *)(sc + at.ends), *report = (long long *)(sc + at.report);
+    unsigned long long *first_error = (unsigned long long *)(sc + at.first_error);
+    long long back[ROCCO_BGZF_REPORT] = {-1, 0, 0, 0};
+    if (n_blocks > 0) {
+        const unsigned grid = (unsigned)((long long)n_blocks < kZlibMaxGrid ? (long long)n_blocks : kZlibMaxGrid);
+        const int queued = queue_then_drain(stream, [&]() -> int {
+            ROCCO_HIP_TRY(hipMemsetAsync(first_error, 0xff, sizeof(unsigned long long), stream));
+            hipLaunchKernelGGL(zlib_inflate_kernel, dim3(grid), dim3(kWave), 0, stream, comp_dev, (long long)n_comp, table_dev,
+                               (long long)n_blocks, out_dev, (long long)n_out, status, produced, ends, first_error);
+            ROCCO_HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(zlib_adler_kernel, dim3(grid), dim3(kWave), 0, stream, comp_dev, table_dev, (long long)n_blocks,
+                               (const uint8_t *)out_dev, status, (const long long *)produced, (const long long *)ends, first_error);
+            ROCCO_HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(bgzf_report_kernel, dim3(1), dim3(1), 0, stream, (const unsigned long long *)first_error,
+                               (const long long *)produced, report);
+            ROCCO_HIP_TRY(hipGetLastError());
+            ROCCO_HIP_TRY(hipMemcpyAsync(back, report, sizeof(back), hipMemcpyDeviceToHost, stream));
+            ROCCO_HIP_TRY(hipStreamSynchronize(stream));
+            return ROCCO_HIP_OK;
+        });
+        if (queued != ROCCO_HIP_OK) {
+            return queued;
+        }
+    }
+    for (int k = 0; k < ROCCO_BGZF_REPORT; ++k) {
+        report_out_host[k] = back[k];
+    }
+    return ROCCO_HIP_OK;
+}
+
+void zlib_inflate_host_blocks(const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks, uint8_t *out, size_t n_out,
+                              int32_t *status_out, int64_t *produced_out, int64_t *report_out)
+{
+    zlib_inflate_host(comp, (long long)n_comp, table, (long long)n_blocks, out, (long long)n_out, status_out, produced_out, report_out);
+    report_out[3] = 0;
+}
 
 size_t bgzf_inflate_scratch_bytes(size_t n_blocks) { return BgzfInflateLayout(n_blocks).bytes; }
 

@@ -191,9 +191,12 @@ ROCCO_INFLATE_HD int huff_decode(const H &h, InflateBits &b, int invalid, int *s
 }
 
 // Inflates the span [lo, hi) of the compressed buffer into out[0, isize).  Returns 0, ROCCO_BGZF_ERR_STREAM | why << 8, or
-// ROCCO_BGZF_ERR_LENGTH; *produced_out: the bytes the stream inflates to (where it is sound).
+// ROCCO_BGZF_ERR_LENGTH; *produced_out: the bytes the stream inflates to (where it is sound); *end_out (may be null, as the
+// BGZF callers leave it): where a sound stream ended in the compressed buffer -- the byte behind the last bit of its final
+// block, the bit reader rounded up to a byte (what zlib's framing keeps its check value at).
 template <class X>
-ROCCO_INFLATE_HD int inflate_block(X &x, InflateTables &t, long long lo, long long hi, uint8_t *out, long long isize, long long *produced_out)
+ROCCO_INFLATE_HD int inflate_block(X &x, InflateTables &t, long long lo, long long hi, uint8_t *out, long long isize, long long *produced_out,
+                                   long long *end_out = nullptr)
 {
     const int lane = x.lane();
     InflateBits b = {0, 0, lo, hi};
@@ -374,6 +377,9 @@ ROCCO_INFLATE_HD int inflate_block(X &x, InflateTables &t, long long lo, long lo
         }
     }
     *produced_out = pos;
+    if (end_out != nullptr) {
+        *end_out = b.ip - (b.bits >> 3);  // (the whole bytes still buffered were fetched and not used)
+    }
     return pos == isize ? 0 : ROCCO_BGZF_ERR_LENGTH;
 }
 
@@ -506,6 +512,155 @@ inline void bgzf_inflate_host(const uint8_t *comp, long long n_comp, const int64
         }
         if (status_out != nullptr) {
             status_out[i] = status;
+        }
+        if (status != 0 && report_out[0] < 0) {
+            report_out[0] = i;
+            report_out[1] = status;
+            report_out[2] = produced;
+        }
+    }
+}
+
+// ---- zlib framing (RFC 1950) around the same deflate data: the data blocks of a bigWig file (note (31)) ------
+// Two header bytes, the deflate stream, the Adler-32 of the inflated bytes in four big-endian bytes.  Acceptance is zlib
+// 1.2.11's inflate() with wbits = 15 as uncompress() drives it, in the order in which it would meet the faults.
+constexpr uint32_t kAdlerBase = 65521u;  // the largest prime below 2^16
+constexpr int kAdlerDefer = 5552;        // zlib's NMAX: the bytes whose sums fit 32 bits before a reduction
+enum ZlibHeaderWhy { kZlibHeaderCheck = 1, kZlibMethod, kZlibWindow, kZlibDictionary };
+static_assert(kZlibDictionary == ROCCO_ZLIB_HEADER_REASONS, "rocco_hip.h states the reasons");
+
+// the two header bytes: 0, or ROCCO_ZLIB_ERR_HEADER | why << 8
+ROCCO_INFLATE_HD int zlib_header_status(uint32_t cmf, uint32_t flg)
+{
+    if (((cmf << 8) + flg) % 31u != 0) {
+        return ROCCO_ZLIB_ERR_HEADER | (kZlibHeaderCheck << 8);
+    }
+    if ((cmf & 15u) != 8u) {
+        return ROCCO_ZLIB_ERR_HEADER | (kZlibMethod << 8);
+    }
+    if ((cmf >> 4) > 7u) {
+        return ROCCO_ZLIB_ERR_HEADER | (kZlibWindow << 8);
+    }
+    return (flg & 0x20u) ? ROCCO_ZLIB_ERR_HEADER | (kZlibDictionary << 8) : 0;
+}
+
+// the Adler-32 of n bytes on their own (zlib's adler32 from 1)
+ROCCO_INFLATE_HD uint32_t adler_of_bytes(const uint8_t *p, long long n)
+{
+    uint32_t a = 1, b = 0;
+    while (n > 0) {
+        const int run = n < kAdlerDefer ? (int)n : kAdlerDefer;
+        for (int k = 0; k < run; ++k) {
+            a += p[k];
+            b += a;
+        }
+        a %= kAdlerBase;
+        b %= kAdlerBase;
+        p += run;
+        n -= run;
+    }
+    return (b << 16) | a;
+}
+
+// the Adler-32 of A || B from those of A and B and B's length (zlib's adler32_combine)
+ROCCO_INFLATE_HD uint32_t adler_combine(uint32_t adler_a, uint32_t adler_b, long long len_b)
+{
+    const uint32_t rem = (uint32_t)(len_b % (long long)kAdlerBase);
+    uint32_t sum1 = adler_a & 0xffffu;
+    uint32_t sum2 = (rem * sum1) % kAdlerBase;
+    sum1 += (adler_b & 0xffffu) + kAdlerBase - 1;
+    sum2 += ((adler_a >> 16) & 0xffffu) + ((adler_b >> 16) & 0xffffu) + kAdlerBase - rem;
+    if (sum1 >= kAdlerBase) {
+        sum1 -= kAdlerBase;
+    }
+    if (sum1 >= kAdlerBase) {
+        sum1 -= kAdlerBase;
+    }
+    if (sum2 >= (kAdlerBase << 1)) {
+        sum2 -= kAdlerBase << 1;
+    }
+    if (sum2 >= kAdlerBase) {
+        sum2 -= kAdlerBase;
+    }
+    return sum1 | (sum2 << 16);
+}
+
+// a row of the zlib block table (rocco_hip.h) against the two buffers
+ROCCO_INFLATE_HD bool zlib_row_fits(const int64_t *row, long long n_comp, long long n_out)
+{
+    return row[0] >= 0 && row[0] <= row[1] && row[1] <= n_comp && row[2] >= 0 && row[2] <= ROCCO_BGZF_MAX_ISIZE && row[3] >= 0 &&
+           row[3] <= n_out && row[2] <= n_out - row[3] && (row[4] == 0 || row[4] == 1);
+}
+
+// Everything of a row but its Adler-32: the header, the stream, the room for the check value, the length; a stored row is
+// copied.  Returns the status so far (0: the Adler-32 of out[0, *produced_out) is still to be compared with the four bytes
+// at *end_out; a stored row has none and *end_out is its span's end).  Cooperative, as inflate_block is.
+template <class X>
+ROCCO_INFLATE_HD int zlib_block(X &x, InflateTables &t, const int64_t *row, uint8_t *out, long long *produced_out, long long *end_out)
+{
+    const long long lo = row[0], hi = row[1], capacity = row[2];
+    *produced_out = 0;
+    *end_out = hi;
+    if (row[4] == 1) {
+        for (long long k = x.lane(); k < hi - lo && k < capacity; k += X::kLanes) {
+            out[k] = x.in_raw(lo + k);
+        }
+        *produced_out = hi - lo;
+        return hi - lo > capacity ? ROCCO_BGZF_ERR_LENGTH : 0;
+    }
+    if (hi - lo < 2) {
+        return ROCCO_ZLIB_ERR_TRUNCATED;
+    }
+    if (const int bad = zlib_header_status(x.in_raw(lo), x.in_raw(lo + 1)); bad != 0) {
+        // (zlib reads the dictionary's id before it asks for the dictionary: without its four bytes the input just ends)
+        return (bad >> 8) == kZlibDictionary && hi - lo < 6 ? ROCCO_ZLIB_ERR_TRUNCATED : bad;
+    }
+    const int status = inflate_block(x, t, lo + 2, hi, out, capacity, produced_out, end_out);
+    if ((status & 0xff) == ROCCO_BGZF_ERR_STREAM) {
+        return status;
+    }
+    if (hi - *end_out < 4) {
+        return ROCCO_ZLIB_ERR_TRUNCATED;
+    }
+    return *produced_out > capacity ? ROCCO_BGZF_ERR_LENGTH : 0;
+}
+
+ROCCO_INFLATE_HD uint32_t zlib_stated_adler(const uint8_t *comp, long long at)
+{
+    return ((uint32_t)comp[at] << 24) | ((uint32_t)comp[at + 1] << 16) | ((uint32_t)comp[at + 2] << 8) | (uint32_t)comp[at + 3];
+}
+
+// What the two kernels of rocco_hip_zlib_inflate compute, block after block (the host twin: test support).
+inline void zlib_inflate_host(const uint8_t *comp, long long n_comp, const int64_t *table, long long n_blocks, uint8_t *out, long long n_out,
+                              int32_t *status_out, int64_t *produced_out, int64_t *report_out)
+{
+    HostInflateExec x = {comp};
+    InflateTables tables;
+    report_out[0] = -1;
+    report_out[1] = 0;
+    report_out[2] = 0;
+    for (long long i = 0; i < n_blocks; ++i) {
+        const int64_t *row = table + i * ROCCO_ZLIB_TABLE_COLUMNS;
+        int status = ROCCO_BGZF_ERR_TABLE;
+        long long produced = 0, end = 0;
+        if (zlib_row_fits(row, n_comp, n_out)) {
+            uint8_t *mine = out + row[3];
+            status = zlib_block(x, tables, row, mine, &produced, &end);
+            if (status == 0 && row[4] == 0) {
+                uint32_t adler = 1;
+                for (int c = 0; c < kCrcChunks; ++c) {
+                    long long first, length;
+                    crc_chunk(produced, c, &first, &length);
+                    adler = adler_combine(adler, adler_of_bytes(mine + first, length), length);
+                }
+                status = adler == zlib_stated_adler(comp, end) ? 0 : ROCCO_ZLIB_ERR_ADLER;
+            }
+        }
+        if (status_out != nullptr) {
+            status_out[i] = status;
+        }
+        if (produced_out != nullptr) {
+            produced_out[i] = produced;
         }
         if (status != 0 && report_out[0] < 0) {
             report_out[0] = i;

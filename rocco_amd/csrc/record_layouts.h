@@ -200,6 +200,21 @@ struct BgzfInflateLayout {
     }
 };
 
+// launch_zlib_inflate: as launch_bgzf_inflate, and per block where its stream ended in the compressed buffer (int64)
+struct ZlibInflateLayout {
+    size_t status, produced, ends, first_error, report, bytes;
+    explicit ZlibInflateLayout(size_t n_blocks)
+    {
+        Layout lay;
+        status = lay.at(n_blocks * sizeof(int));
+        produced = lay.at(n_blocks * sizeof(long long));
+        ends = lay.at(n_blocks * sizeof(long long));
+        first_error = lay.at(sizeof(unsigned long long));
+        report = lay.at(ROCCO_BGZF_REPORT * sizeof(long long));
+        bytes = lay.bytes();
+    }
+};
+
 }  // namespace
 
 }  // namespace rocco
