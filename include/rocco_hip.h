@@ -867,6 +867,18 @@ void rocco_hip_fragment_length_shape(int *shape_out);
  *   error in record order (the lowest code within a record; 0: none), [1] its record (-1).  contig_first_out_host,
  *   n_ref + 2 int64: [k] the first record of contig k or later for k = 0 .. n_ref (records without a contig count as
  *   n_ref), [n_ref + 1] = n; meaningful when there is no error.
+ * rocco_hip_bam_stream_firsts: splits a chain that was walked over n_streams streams laid one behind the other (the spans a
+ *   .bai index names, rocco_amd/bam.py: read_alignment_spans) back into its streams.  offsets_dev[n]: the ascending record
+ *   offsets of the walk; tid_dev[n]: their refIDs; bounds_host[n_streams + 1]: the ascending byte bounds of the streams
+ *   (0 <= bound; an empty stream repeats a bound; the last is n_bytes; ROCCO_HIP_EINVAL otherwise, or for n_streams < 1);
+ *   expect_tid_host[n_streams]: the refID every record of a stream must carry.  One lane per record (a grid stride under
+ *   ROCCO_BAM_MAX_GRID workgroups of ROCCO_BAM_THREADS): the bounds are bisected with an upper-bound search, so a record on a
+ *   repeated bound belongs to the last stream that begins there; every load is bounded by n and n_streams.
+ *   firsts_out_host[n_streams + 1]: [j] the first record at or after bound j, [n_streams] = n.  report_out_host: [0] the
+ *   code of the first error in stream order (the lowest code within a stream; 0: none), [1] its stream (-1):
+ *   ROCCO_BAM_ERR_SEAM, a bound with records or bytes behind it is not itself a record start (the index's begin or end lay
+ *   inside a record, the chain crossed the seam mis-framed); ROCCO_BAM_ERR_SPAN_TID, a record of the stream carries another
+ *   refID than expected (the index is stale or another file's).  Synchronises once, at its end.
  * rocco_hip_bam_shape: shape_out[0..2] = ROCCO_BAM_GUESS_DEPTH, ROCCO_BAM_SEGMENT_BYTES (the default S), ROCCO_BAM_THREADS. */
 #define ROCCO_BAM_GUESS_DEPTH 3
 #define ROCCO_BAM_SEGMENT_BYTES 16384
@@ -884,6 +896,8 @@ void rocco_hip_fragment_length_shape(int *shape_out);
 #define ROCCO_BAM_ERR_CG_TAG 9
 #define ROCCO_BAM_ERR_ORDER 10
 #define ROCCO_BAM_ERR_OFFSET 11
+#define ROCCO_BAM_ERR_SEAM 12
+#define ROCCO_BAM_ERR_SPAN_TID 13
 int rocco_hip_bam_walk_records(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, int64_t entry0, int n_ref,
                                size_t segment_bytes, int guess_mode, int64_t *offsets_out_dev, size_t capacity,
                                int64_t *segment_entry_out_dev, int64_t *report_out_host, void *stream);
@@ -891,6 +905,9 @@ int rocco_hip_bam_record_fields(rocco_hip_solver *solver, const uint8_t *bytes_d
                                 int n_ref, int32_t *tid_out_dev, int32_t *pos_out_dev, int32_t *end_out_dev, int32_t *isize_out_dev,
                                 uint16_t *flag_out_dev, uint8_t *mapq_out_dev, uint8_t *mate_same_out_dev, int32_t *qlen_out_dev,
                                 int64_t *contig_first_out_host, int64_t *report_out_host, void *stream);
+int rocco_hip_bam_stream_firsts(rocco_hip_solver *solver, const int64_t *offsets_dev, const int32_t *tid_dev, size_t n,
+                                const int64_t *bounds_host, const int32_t *expect_tid_host, size_t n_streams, int64_t *firsts_out_host,
+                                int64_t *report_out_host, void *stream);
 void rocco_hip_bam_shape(int *shape_out);
 
 /* ---- the BGZF blocks of a BAM file -> their inflated bytes (note (29)) ----------------------
@@ -1011,7 +1028,7 @@ void rocco_hip_zlib_shape(int *shape_out);
 #define ROCCO_COUNT_INTERVALS_THREADS 256  /* threads per workgroup of interval_count.hip's kernels */
 #define ROCCO_INTERVAL_FACTS_MAX_GRID 2048 /* unit: ROCCO_COUNT_INTERVALS_THREADS records (interval_track_facts_kernel) */
 #define ROCCO_FRAGMENT_MAX_GRID 2048       /* unit: ROCCO_FRAGMENT_THREADS records (record_flag_facts_kernel, template_length_kernel); ROCCO_FRAGMENT_DENSITY_RECORDS records (chunk_density_kernel) */
-#define ROCCO_BAM_MAX_GRID 4096            /* unit: one segment (bam_guess_kernel); ROCCO_BAM_THREADS segments (bam_walk_kernel, bam_emit_kernel); ROCCO_BAM_THREADS records (bam_fields_kernel) */
+#define ROCCO_BAM_MAX_GRID 4096            /* unit: one segment (bam_guess_kernel); ROCCO_BAM_THREADS segments (bam_walk_kernel, bam_emit_kernel); ROCCO_BAM_THREADS records (bam_fields_kernel, bam_stream_firsts_kernel) */
 /* rocco_hip_launch_caps: out[0 .. ROCCO_LAUNCH_CAPS) = ROCCO_SELECT_GRID_TARGET, ROCCO_SELECT_CHUNK_VALUES, ROCCO_SELECT_THREADS,
  * ROCCO_BH_MAX_GRID, ROCCO_BH_THREADS, ROCCO_CHROM_RANGE_MAX_GRID, ROCCO_COUNT_TAIL_MAX_GRID, ROCCO_COUNT_THREADS,
  * ROCCO_INTERVAL_FACTS_MAX_GRID, ROCCO_COUNT_INTERVALS_THREADS, ROCCO_FRAGMENT_MAX_GRID, ROCCO_FRAGMENT_THREADS,

@@ -58,6 +58,14 @@ from .bam import (  # noqa: F401  (htslib's BGZF reader, bam_read1, bam_endpos, 
     inflate_bgzf_device,
     parse_bam_header,
     read_alignment_file,
+    read_alignment_spans,
+    IndexedAlignmentFile,
+)
+from .bam_index import (  # noqa: F401  (htslib's BAI reader: hts_idx_load, hts_idx_get_stat, the pseudo-bin's offsets)
+    clear_bam_index_cache,
+    contig_span,
+    contig_stats,
+    open_bam_index,
 )
 from .bigwig import (  # noqa: F401  (the data blocks libBigWig inflates behind pyBigWig's intervals())
     clear_bigwig_cache,

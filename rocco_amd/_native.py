@@ -324,6 +324,9 @@ PROTOTYPES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, c_ll_p,
       ctypes.c_void_p]),
+    # (no reference line: the reference seeks one contig at a time; here the spans of K files are walked as one chain)
+    ("rocco_hip_bam_stream_firsts", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, c_int_p, ctypes.c_size_t, c_ll_p, c_ll_p, ctypes.c_void_p]),
     ("rocco_hip_bam_shape", None, [c_int_p]),
     # row f8 (csrc/bgzf_inflate.hip, csrc/inflate_core.h): htslib's bgzf_read_block: inflate, ISIZE and CRC32 of every block
     ("rocco_hip_bgzf_inflate", ctypes.c_int,

@@ -8,12 +8,19 @@ reference's signatures (rocco/readtracks.py:389-407, 242-252) and are composed f
 `rocco_amd.readtracks.bam_count_metadata_from_records` and `bam_chrom_reads_from_records`; an integrator binds the first
 behind the stub: ``rocco_amd.readtracks.get_bam_chrom_reads = rocco_amd.bam.get_bam_chrom_reads``.
 
-Not built: CRAM and SAM, the ``.bai`` index (the whole file is decoded; the index iterator's overlap
-test is already applied by the counting kernels), CIGARs kept in a ``CG`` tag (reported as an error).  There is no CPU
-fallback for the record walk."""
+A file that has a ``.bai`` index (rocco_amd/bam_index.py) is read contig by contig (note (32)):
+`read_alignment_spans` lays the spans of K (file, contig) pairs one behind the other -- with the index each begins and ends on
+a record boundary, so they form one record chain -- and decodes a group of them with one inflate, one walk and one field
+decode; `rocco_hip_bam_stream_firsts` splits the chain back and checks what the index claimed.  `_cached_file` hands out an
+`IndexedAlignmentFile` for such a file (``USE_INDEX``), which decodes a contig when it is asked for.
+
+Not built: CRAM and SAM, ``.csi`` indexes (such a file is decoded whole; the index iterator's overlap test is already applied
+by the counting kernels), CIGARs kept in a ``CG`` tag (reported as an error).  There is no CPU fallback for the record walk."""
 from __future__ import annotations
 
+import bisect
 import collections
+import collections.abc
 import ctypes
 import logging
 import multiprocessing
@@ -26,6 +33,7 @@ from typing import Iterator, List, Optional, Tuple
 import numpy as np
 
 from . import _native
+from . import bam_index as _bai
 from . import dp as _dp
 from . import readtracks as _rt
 from .readtracks import AlignmentFileRecords, AlignmentRecords
@@ -33,6 +41,8 @@ from .readtracks import AlignmentFileRecords, AlignmentRecords
 logger = _rt.logger  # (the reference's reader logs where its readtracks module does)
 
 DEFAULT_SLAB_BYTES = 256 << 20
+DEFAULT_BATCH_BYTES = 2 << 30  # inflated bytes of one group of `read_alignment_spans` (a choice, not a measurement: DESIGN.md note (32))
+USE_INDEX = True               # `_cached_file` reads a file that has a .bai index contig by contig (rocco_amd/bam_index.py)
 DEFAULT_INFLATE = "host"       # where `get_bam_chrom_reads` and `_get_bam_count_metadata` have a file's blocks inflated: "host" or "device"
 GUESS_DEPTH = 3                # ROCCO_BAM_GUESS_DEPTH of include/rocco_hip.h
 DEFAULT_SEGMENT_BYTES = 16384  # ROCCO_BAM_SEGMENT_BYTES
@@ -40,6 +50,7 @@ _BGZF_HEADER = 12              # ID1 ID2 CM FLG MTIME(4) XFL OS XLEN(2)
 
 ERR_BLOCK_SIZE, ERR_TRUNCATED, ERR_SIZES, ERR_READ_NAME, ERR_REF_ID, ERR_CIGAR_SEQ, ERR_POSITION, ERR_END, ERR_CG_TAG, ERR_ORDER, \
     ERR_OFFSET = range(1, 12)
+ERR_SEAM, ERR_SPAN_TID = 12, 13  # (of `rocco_hip_bam_stream_firsts`: what an index that does not describe its file looks like)
 _ERROR_TEXT = {
     ERR_BLOCK_SIZE: "its block_size is below 32",
     ERR_TRUNCATED: "the stream ends inside it",
@@ -100,6 +111,37 @@ def _crc_mismatch(where: str) -> ValueError:
     return ValueError(f"{where}: CRC32 mismatch")
 
 
+def _bgzf_block_at(raw, total: int, at: int, bad) -> Tuple[int, int, int, int, int]:
+    """The row of the block whose header begins at file offset ``at``; ``bad(what)`` makes the error for a header that is refused."""
+    if at + _BGZF_HEADER > total:
+        raise bad("the file ends inside the block header")
+    id1, id2, cm, flg = raw[at], raw[at + 1], raw[at + 2], raw[at + 3]
+    if id1 != 0x1F or id2 != 0x8B or cm != 8:
+        raise bad("bad header (no gzip magic)")
+    if not flg & 4:
+        raise bad("bad header (FLG.FEXTRA is not set)")
+    (xlen,) = struct.unpack_from("<H", raw, at + 10)
+    extra, extra_end = at + _BGZF_HEADER, at + _BGZF_HEADER + xlen
+    if extra_end > total:
+        raise bad("the file ends inside the block header")
+    bsize = None
+    while extra + 4 <= extra_end:
+        si1, si2, slen = raw[extra], raw[extra + 1], struct.unpack_from("<H", raw, extra + 2)[0]
+        if extra + 4 + slen > extra_end:
+            raise bad("bad header (an extra subfield overruns XLEN)")
+        if si1 == 66 and si2 == 67 and slen == 2:
+            bsize = struct.unpack_from("<H", raw, extra + 4)[0] + 1
+        extra += 4 + slen
+    if bsize is None:
+        raise bad("bad header (no BC subfield)")
+    if bsize < _BGZF_HEADER + xlen + 8:
+        raise bad("bad header (BSIZE is smaller than the header and trailer)")
+    if at + bsize > total:
+        raise bad(f"the file ends inside the block ({total - at} of {bsize} bytes)")
+    crc, isize = struct.unpack_from("<II", raw, at + bsize - 8)
+    return at, extra_end, at + bsize - 8, crc, isize
+
+
 def _bgzf_blocks(raw: memoryview, name: str) -> List[Tuple[int, int, int, int, int]]:
     """(file offset, first byte of the deflate data, one past its last, CRC32, ISIZE) per block, from the block headers."""
     blocks, at, total = [], 0, len(raw)
@@ -108,35 +150,46 @@ def _bgzf_blocks(raw: memoryview, name: str) -> List[Tuple[int, int, int, int, i
         return ValueError(f"{_block_where(name, len(blocks), at)}: {what}")
 
     while at < total:
-        if at + _BGZF_HEADER > total:
-            raise bad("the file ends inside the block header")
-        id1, id2, cm, flg = raw[at], raw[at + 1], raw[at + 2], raw[at + 3]
-        if id1 != 0x1F or id2 != 0x8B or cm != 8:
-            raise bad("bad header (no gzip magic)")
-        if not flg & 4:
-            raise bad("bad header (FLG.FEXTRA is not set)")
-        (xlen,) = struct.unpack_from("<H", raw, at + 10)
-        extra, extra_end = at + _BGZF_HEADER, at + _BGZF_HEADER + xlen
-        if extra_end > total:
-            raise bad("the file ends inside the block header")
-        bsize = None
-        while extra + 4 <= extra_end:
-            si1, si2, slen = raw[extra], raw[extra + 1], struct.unpack_from("<H", raw, extra + 2)[0]
-            if extra + 4 + slen > extra_end:
-                raise bad("bad header (an extra subfield overruns XLEN)")
-            if si1 == 66 and si2 == 67 and slen == 2:
-                bsize = struct.unpack_from("<H", raw, extra + 4)[0] + 1
-            extra += 4 + slen
-        if bsize is None:
-            raise bad("bad header (no BC subfield)")
-        if bsize < _BGZF_HEADER + xlen + 8:
-            raise bad("bad header (BSIZE is smaller than the header and trailer)")
-        if at + bsize > total:
-            raise bad(f"the file ends inside the block ({total - at} of {bsize} bytes)")
-        crc, isize = struct.unpack_from("<II", raw, at + bsize - 8)
-        blocks.append((at, extra_end, at + bsize - 8, crc, isize))
-        at += bsize
+        block = _bgzf_block_at(raw, total, at, bad)
+        blocks.append(block)
+        at = block[2] + 8
     return blocks
+
+
+def _bgzf_span_blocks(raw, name: str, contig: str, v_begin: int, v_end: int):
+    """The ranged front: (the block rows from file offset ``v_begin >> 16`` up to and including the block at ``v_end >> 16``
+    -- left out where ``v_end & 0xFFFF == 0`` --, the bytes to skip in the first block, the bytes to keep of the last).  The
+    checks and words of `_bgzf_blocks`; the blocks are numbered from the span's first.  ``skip == ISIZE`` is legal (htslib may
+    point at a block's end: such a block contributes nothing).  ValueError naming the file, the contig and the virtual offset
+    for a span that points outside the file or past a block's ISIZE."""
+    total = len(raw)
+    first, skip, last, keep = int(v_begin) >> 16, int(v_begin) & 0xFFFF, int(v_end) >> 16, int(v_end) & 0xFFFF
+
+    def outside(v: int, why: str) -> ValueError:
+        return ValueError(f"{name}: contig {contig}: virtual offset {v} ({v >> 16} << 16 | {v & 0xFFFF}) of the index {why}")
+
+    if v_end < v_begin:
+        raise outside(v_end, f"ends the span before its begin, virtual offset {v_begin}")
+    blocks, at = [], first
+
+    def bad(what: str) -> ValueError:
+        return ValueError(f"{_block_where(name, len(blocks), at)} (blocks counted from the span of contig {contig}): {what}")
+
+    while at < last or (at == last and keep != 0):
+        if at >= total:
+            raise outside(v_end if blocks else v_begin, f"points outside the file ({total} bytes)")
+        block = _bgzf_block_at(raw, total, at, bad)
+        blocks.append(block)
+        at = block[2] + 8
+    if (keep != 0 and blocks[-1][0] != last) or (keep == 0 and at != last):
+        raise outside(v_end, f"names no block: the blocks from the span's begin pass it, the next begins at file offset {at}")
+    if keep == 0:
+        keep = blocks[-1][4] if blocks else 0
+    if blocks and skip > blocks[0][4]:
+        raise outside(v_begin, f"points past the block's ISIZE ({blocks[0][4]})")
+    if blocks and keep > blocks[-1][4]:
+        raise outside(v_end, f"points past the block's ISIZE ({blocks[-1][4]})")
+    return blocks, skip, keep
 
 
 def _bgzf_front(source, slab_bytes: Optional[int], who: str):
@@ -504,6 +557,75 @@ def decode_records_device(bytes_t, entry0: int, n_ref: int, segment_bytes: Optio
     return fields, firsts, report
 
 
+def stream_firsts_device(offsets_t, tid_t, bounds, expect_tid):
+    """`rocco_hip_bam_stream_firsts`: splits the walked chain of K streams laid one behind the other back into its streams.
+    ``offsets_t`` / ``tid_t``: the int64 record offsets and int32 reference ids as CUDA tensors; ``bounds``: the K + 1 ascending
+    byte bounds; ``expect_tid``: the K reference ids.  Returns (the K + 1 first records as a list, (error code, stream))."""
+    import torch
+
+    lib = _native.load()
+    if not _dp._is_tensor(offsets_t) or offsets_t.dtype != torch.int64 or not offsets_t.is_cuda or not _dp._is_tensor(tid_t) or \
+            tid_t.dtype != torch.int32 or tid_t.device != offsets_t.device or tid_t.shape != offsets_t.shape or offsets_t.dim() != 1:
+        raise TypeError("stream_firsts_device: an int64 and an int32 CUDA tensor of one length on one device are required")
+    offsets_t, tid_t = offsets_t.contiguous(), tid_t.contiguous()
+    K, n = len(expect_tid), int(offsets_t.shape[0])
+    if K < 1 or len(bounds) != K + 1:
+        raise ValueError("stream_firsts_device: K >= 1 expected reference ids and K + 1 bounds are required")
+    bounds_c, expect_c = (ctypes.c_longlong * (K + 1))(*[int(b) for b in bounds]), (ctypes.c_int * K)(*[int(t) for t in expect_tid])
+    firsts, back = (ctypes.c_longlong * (K + 1))(), (ctypes.c_longlong * 2)()
+    with torch.cuda.device(offsets_t.device):
+        _native.check(lib.rocco_hip_bam_stream_firsts(
+            _native.solver_for(offsets_t.device.index).handle, offsets_t.data_ptr() if n else None, tid_t.data_ptr() if n else None, n,
+            bounds_c, expect_c, K, firsts, back, _dp._stream_ptr(offsets_t)), "rocco_hip_bam_stream_firsts")
+    return [int(v) for v in firsts], (int(back[0]), int(back[1]))
+
+
+def _decode_slabs(slabs, entry0: int, n_ref: int, segment_bytes: Optional[int], guess_mode: int, name: str, dev, cut_tail: int = 0):
+    """The slab loop of `read_alignment_file` and of a span too large for one group (`read_alignment_spans`): walks and decodes
+    ``slabs`` (device tensors of inflated bytes, at least one) from ``entry0`` of the first; a slab's bytes behind its last
+    complete record are carried, on the device, in front of the next; the last slab loses its last ``cut_tail`` bytes and must
+    end behind a complete record.  Returns (the fields of every slab, the records per contig -- those without one last --,
+    the walk's totals)."""
+    import torch
+
+    carry = empty = torch.empty(0, dtype=torch.uint8, device=dev)  # (what the walk has not consumed yet, in front of the next slab)
+    parts, counts, last_key, n_records, consumed = [], np.zeros(n_ref + 1, dtype=np.int64), -1, 0, 0
+    totals = {"records": 0, "segments": 0, "wrong_guesses": 0, "repair_rounds": 0, "slabs": 0}
+
+    def with_last(it):  # (the header needs a block, so there is a slab)
+        previous = next(it)
+        for item in it:
+            yield previous, False
+            previous = item
+        yield previous, True
+
+    for slab, is_last in with_last(iter(slabs)):
+        if is_last and cut_tail:
+            slab = slab[: slab.shape[0] - cut_tail]
+        data = torch.cat([carry, slab]) if carry.shape[0] else slab
+        if data.shape[0] < entry0 and not is_last:  # (the header straddles slabs)
+            carry = data
+            continue
+        fields, firsts, rep = decode_records_device(data, entry0, n_ref, segment_bytes, guess_mode, name, whole=is_last,
+                                                    first_record=n_records, first_byte=consumed)
+        slab_counts = np.diff(np.asarray(firsts, dtype=np.int64))
+        present = np.flatnonzero(slab_counts)
+        if present.size:
+            if int(present[0]) < last_key:
+                raise _record_error(name, ERR_ORDER, n_records, consumed + entry0)
+            last_key = int(present[-1])
+        counts += slab_counts
+        parts.append(fields)
+        n_records += rep["records"]
+        for key in ("records", "segments", "wrong_guesses", "repair_rounds"):
+            totals[key] += rep[key]
+        totals["slabs"] += 1
+        carry = data[rep["end_offset"]:].clone() if rep["end_offset"] < data.shape[0] else empty
+        consumed += rep["end_offset"]
+        entry0 = 0
+    return parts, counts, totals
+
+
 def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT_SLAB_BYTES, segment_bytes: Optional[int] = None,
                         threads: Optional[int] = None, guess_mode: int = 1, report: Optional[dict] = None, inflate: str = "host"):
     """A whole BAM file as (`AlignmentFileRecords` whose records carry ``qlen`` and are CUDA tensors, ``name`` the path; the
@@ -528,39 +650,7 @@ def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT
     else:
         slabs = _uploaded(_inflate_slabs(raw, path, blocks, threads, slab_bytes), dev)
     n_ref = len(contigs)
-    carry = empty = torch.empty(0, dtype=torch.uint8, device=dev)  # (what the walk has not consumed yet, in front of the next slab)
-    parts, counts, last_key, n_records, consumed = [], np.zeros(n_ref + 1, dtype=np.int64), -1, 0, 0
-    totals = {"records": 0, "segments": 0, "wrong_guesses": 0, "repair_rounds": 0, "slabs": 0}
-
-    def with_last(it):  # (the header needs a block, so there is a slab)
-        previous = next(it)
-        for item in it:
-            yield previous, False
-            previous = item
-        yield previous, True
-
-    for slab, is_last in with_last(slabs):
-        data = torch.cat([carry, slab]) if carry.shape[0] else slab
-        if data.shape[0] < entry0 and not is_last:  # (the header straddles slabs)
-            carry = data
-            continue
-        fields, firsts, rep = decode_records_device(data, entry0, n_ref, segment_bytes, guess_mode, path, whole=is_last,
-                                                    first_record=n_records, first_byte=consumed)
-        slab_counts = np.diff(np.asarray(firsts, dtype=np.int64))
-        present = np.flatnonzero(slab_counts)
-        if present.size:
-            if int(present[0]) < last_key:
-                raise _record_error(path, ERR_ORDER, n_records, consumed + entry0)
-            last_key = int(present[-1])
-        counts += slab_counts
-        parts.append(fields)
-        n_records += rep["records"]
-        for key in ("records", "segments", "wrong_guesses", "repair_rounds"):
-            totals[key] += rep[key]
-        totals["slabs"] += 1
-        carry = data[rep["end_offset"]:].clone() if rep["end_offset"] < data.shape[0] else empty
-        consumed += rep["end_offset"]
-        entry0 = 0
+    parts, counts, totals = _decode_slabs(slabs, entry0, n_ref, segment_bytes, guess_mode, path, dev)
     if report is not None:
         report.update(totals)
     whole = {name: (torch.cat([p[name] for p in parts]) if len(parts) > 1 else parts[0][name]) for name, _ in _FIELD_DTYPES}
@@ -577,17 +667,339 @@ def read_alignment_file(path, device=None, names=None, slab_bytes: int = DEFAULT
 
 
 # --------------------------------------------------------------------------------------------
+# contigs of files read through the .bai index: K streams, one device pass (note (32))
+# --------------------------------------------------------------------------------------------
+
+class _LeadingBlocks:
+    """The block rows of a file from its first, walked as `_header_from_leading_blocks` asks for them (the words of
+    `_bgzf_blocks`): the header of an indexed file costs its leading blocks, not a walk over every block header."""
+
+    def __init__(self, raw, name: str):
+        self.raw, self.name, self.rows, self.at, self.asked = raw, name, [], 0, 0
+
+    def _grow(self, k: int) -> None:
+        def bad(what: str) -> ValueError:
+            return ValueError(f"{_block_where(self.name, len(self.rows), self.at)}: {what}")
+
+        while len(self.rows) <= k and self.at < len(self.raw):
+            self.rows.append(_bgzf_block_at(self.raw, len(self.raw), self.at, bad))
+            self.at = self.rows[-1][2] + 8
+
+    def __len__(self) -> int:
+        self._grow(self.asked)
+        return len(self.rows)
+
+    def __getitem__(self, k: int):
+        self.asked = max(self.asked, k + 1)
+        self._grow(k)
+        return self.rows[k]
+
+
+def _mapped_bytes(path: str):
+    """The file's bytes, mapped: a span's blocks are read where they are used, the rest of the file is not."""
+    if os.path.getsize(path) == 0:
+        return memoryview(b"")
+    return memoryview(np.memmap(path, dtype=np.uint8, mode="r"))
+
+
+class _BamFront:
+    """What is kept of an indexed file between calls: its header's ``contigs``, ``tid_of`` (name -> reference id) and its
+    parsed ``index``."""
+
+    def __init__(self, path: str, contigs, index):
+        self.path, self.contigs, self.index = path, contigs, index
+        self.tid_of = {name: tid for tid, (name, _) in reversed(list(enumerate(contigs)))}
+
+
+_BAM_FRONT_CACHE: "collections.OrderedDict" = collections.OrderedDict()
+BAM_FRONT_CACHE_FILES = 1024
+
+
+def _file_key(path: str):
+    stat = os.stat(path)
+    return (os.path.abspath(path), int(stat.st_size), int(stat.st_mtime_ns))
+
+
+def _bam_front(path: str) -> Optional[_BamFront]:
+    """The header and the index of ``path`` (cached on the file's and the index's (path, size, mtime)); None without an index."""
+    index = _bai.open_bam_index(path)
+    if index is None:
+        return None
+    key = _file_key(path) + (index.name, index.size, id(index))
+    hit = _BAM_FRONT_CACHE.get(key)
+    if hit is not None:
+        _BAM_FRONT_CACHE.move_to_end(key)
+        return hit
+    raw = _mapped_bytes(path)
+    contigs, _ = _header_from_leading_blocks(raw, path, _LeadingBlocks(raw, path))
+    front = _BAM_FRONT_CACHE[key] = _BamFront(path, contigs, index)
+    while len(_BAM_FRONT_CACHE) > BAM_FRONT_CACHE_FILES:
+        _BAM_FRONT_CACHE.popitem(last=False)
+    return front
+
+
+class _Stream:
+    """One (file, contig) of `read_alignment_spans`: its blocks, the bytes to skip in the first and to keep of the last."""
+
+    __slots__ = ("path", "contig", "tid", "n_ref", "raw", "blocks", "skip", "keep", "size", "index_name")
+
+    def where(self) -> str:
+        return f"{self.path}: contig {self.contig}"
+
+
+def _not_this_file(stream: "_Stream", found: str) -> ValueError:
+    return ValueError(f"{stream.where()}: {found}; the index {stream.index_name} does not describe this file")
+
+
+def _span_streams(wanted) -> List["_Stream"]:
+    raws, out = {}, []
+    for path, contig in wanted:
+        path, contig = os.fspath(path), str(contig)
+        front = _bam_front(path)
+        if front is None:
+            raise ValueError(f"{path}: read_alignment_spans needs its .bai index (read_alignment_file reads a file without one)")
+        if contig not in front.tid_of:
+            raise KeyError(f"{path}: no contig {contig}")
+        s = _Stream()
+        s.path, s.contig, s.tid, s.n_ref, s.index_name = path, contig, front.tid_of[contig], len(front.contigs), front.index.name
+        span = _bai.contig_span(front.index, s.tid)
+        s.raw, s.blocks, s.skip, s.keep, s.size = None, [], 0, 0, 0
+        if span is not None:
+            if path not in raws:
+                raws[path] = _mapped_bytes(path)
+            s.raw = raws[path]
+            s.blocks, s.skip, s.keep = _bgzf_span_blocks(s.raw, path, contig, span[0], span[1])
+            if s.blocks:
+                s.size = sum(b[4] for b in s.blocks) - s.skip - (s.blocks[-1][4] - s.keep)
+                if s.size < 0:
+                    raise _not_this_file(s, f"its span ends at virtual offset {span[1]}, before its begin {span[0]}")
+        out.append(s)
+    return out
+
+
+def _span_groups(streams, batch_bytes: int):
+    """(first, one past the last) stream of every group: a group's inflated bytes stay under ``batch_bytes`` (a stream that
+    alone exceeds it is a group of its own and goes through the slab loop); its streams share one header length (the record
+    checks take ``n_ref``) and their reference ids do not descend (the record checks demand the order of a sorted file)."""
+    first = 0
+    while first < len(streams):
+        last, size, tid = first + 1, streams[first].size, (streams[first].tid if streams[first].size else -1)
+        while last < len(streams) and streams[first].size <= batch_bytes:
+            nxt = streams[last]
+            if nxt.n_ref != streams[first].n_ref or size + nxt.size > batch_bytes or (nxt.size and nxt.tid < tid):
+                break
+            size, tid, last = size + nxt.size, (nxt.tid if nxt.size else tid), last + 1
+        yield first, last
+        first = last
+
+
+def _group_bytes_device(group, dev):
+    """The useful bytes of the group's streams, one behind the other, from ONE block table, one pinned staging buffer, one
+    upload and one `rocco_hip_bgzf_inflate`; a block that two neighbouring streams share is inflated once."""
+    import torch
+
+    rows, owner, spans, comp_at, out_at = [], [], [], 0, 0  # spans: [file bytes, file offset, size] of every coalesced run
+    slices = []
+    for k, s in enumerate(group):
+        if not s.blocks:
+            slices.append((0, 0))
+            continue
+        first_row = None
+        for index, block in enumerate(s.blocks):
+            if block[4] > BGZF_MAX_ISIZE:
+                raise ValueError(f"{_block_where(s.path, index, block[0])}: length mismatch (ISIZE says {block[4]}, a BGZF block "
+                                 f"holds at most {BGZF_MAX_ISIZE} bytes; inflate=\"host\" reads a file that breaks this rule)")
+            if index == 0 and owner and owner[-1][0].raw is s.raw and owner[-1][2] == block[0]:
+                first_row = len(rows) - 1  # (the block the stream before ends in)
+                continue
+            lo, hi = block[1], block[2]
+            if spans and spans[-1][0] is s.raw and spans[-1][1] + spans[-1][2] <= lo and lo - (spans[-1][1] + spans[-1][2]) <= 64:
+                gap = lo - (spans[-1][1] + spans[-1][2])  # (neighbours: the trailer and the next header ride along)
+                spans[-1][2] += gap + hi - lo
+                comp_at += gap
+            else:
+                spans.append([s.raw, lo, hi - lo])
+            if first_row is None:
+                first_row = len(rows)
+            rows.append((comp_at, comp_at + hi - lo, block[4], block[3], out_at))
+            owner.append((s, index, block[0]))
+            comp_at += hi - lo
+            out_at += block[4]
+        last_row = len(rows) - 1
+        slices.append((rows[first_row][4] + s.skip, rows[last_row][4] + s.keep))
+    table = np.asarray(rows, dtype=np.int64).reshape(-1, BGZF_TABLE_COLUMNS)
+    head = table.size * 8
+    staged = _host_buffer(head + comp_at)  # (pinned: the table and the compressed bytes go up in one asynchronous copy)
+    staged[:head] = table.reshape(-1).view(np.uint8)
+    at = head
+    for raw, offset, size in spans:
+        staged[at: at + size] = np.frombuffer(raw[offset: offset + size], dtype=np.uint8)
+        at += size
+    with torch.cuda.device(dev):
+        up = torch.from_numpy(staged).to(dev, non_blocking=True)
+        out = torch.empty(out_at, dtype=torch.uint8, device=dev)
+        _, report = inflate_blocks_device(up[head:], up[:head].view(torch.int64), out)  # (synchronises: `staged` may go)
+        if report["block"] >= 0:
+            s, index, offset = owner[report["block"]]
+            raise _bgzf_error(f"{_block_where(s.path, index, offset)} (blocks counted from the span of contig {s.contig})",
+                              int(table[report["block"], 2]), report)
+        pieces = [out[lo:hi] for lo, hi in slices if hi > lo]
+        if len(pieces) == 1:
+            return pieces[0]
+        return torch.cat(pieces) if pieces else out[:0]
+
+
+def _group_bytes_host(group, dev, threads: Optional[int]):
+    """The same bytes from a host inflate: every block's useful bytes are placed directly at their final place in one pinned
+    buffer, which goes up in one copy."""
+    import torch
+
+    jobs, at = [], 0
+    for s in group:
+        for index, block in enumerate(s.blocks):
+            lo = s.skip if index == 0 else 0
+            hi = s.keep if index == len(s.blocks) - 1 else block[4]
+            jobs.append((s, index, block, lo, hi, at))
+            at += max(hi - lo, 0)
+    out = _host_buffer(at)
+
+    def one(job):
+        s, index, block, lo, hi, to = job
+        data = _inflate_block(s.raw, s.path, index, block)
+        if hi > lo:
+            out[to: to + hi - lo] = np.frombuffer(data, dtype=np.uint8)[lo:hi]
+
+    with ThreadPoolExecutor(max_workers=_default_threads() if threads is None else max(1, int(threads))) as pool:
+        for _ in pool.map(one, jobs):
+            pass
+    with torch.cuda.device(dev):
+        up = torch.from_numpy(out).to(dev, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()  # (the pinned `out` may go)
+    return up
+
+
+def _decode_group(group, dev, inflate: str, segment_bytes: Optional[int], threads: Optional[int]):
+    """One inflate, one walk, one field decode and one split for the streams of a group: ({field: tensor}, the K + 1 first
+    records)."""
+    data = _group_bytes_device(group, dev) if inflate == "device" else _group_bytes_host(group, dev, threads)
+    bounds = [0]
+    for s in group:
+        bounds.append(bounds[-1] + s.size)
+    if int(data.shape[0]) != bounds[-1]:
+        raise RuntimeError(f"read_alignment_spans: {int(data.shape[0])} bytes laid out where the spans hold {bounds[-1]}")
+
+    def stream_at(offset: int) -> int:
+        return min(max(bisect.bisect_right(bounds, offset) - 1, 0), len(group) - 1)
+
+    n_ref = group[0].n_ref
+    offsets, report = walk_records_device(data, 0, n_ref, segment_bytes)
+    if report["error"]:
+        k = stream_at(report["error_offset"])
+        raise _not_this_file(group[k], f"the record at byte {report['error_offset'] - bounds[k]} of its span, as the index states it: "
+                             f"{_ERROR_TEXT[report['error']]} (or the file is damaged there)")
+    fields, _, (code, record) = record_fields_device(data, offsets, n_ref)
+    firsts, (split_code, stream) = stream_firsts_device(offsets, fields["tid"], bounds, [s.tid for s in group])
+    if split_code == ERR_SEAM:
+        raise _not_this_file(group[stream], "no record begins where its span begins, or the span before it ends inside a record")
+    if split_code:
+        k, lo, hi = stream, firsts[stream], firsts[stream + 1]
+        other = fields["tid"][lo:hi]
+        other = other[other != group[k].tid]
+        found = int(other[0]) if other.numel() else -1
+        raise _not_this_file(group[k], f"a record of its span lies on reference {found}, the contig is reference {group[k].tid}")
+    if code:
+        at = int(offsets[record])
+        k = stream_at(at)
+        raise ValueError(f"{group[k].where()}: record {record - firsts[k]} of the contig, at byte {at - bounds[k]} of its span: "
+                         f"{_ERROR_TEXT.get(code, f'error {code}')}")
+    return fields, firsts
+
+
+def _decode_long_stream(s: "_Stream", dev, inflate: str, segment_bytes: Optional[int], threads: Optional[int], slab_bytes: int):
+    """A stream that alone exceeds a group's budget: the slab loop of `read_alignment_file` from the span's entry, cut at its end."""
+    slab_bytes = max(1, int(slab_bytes))
+    if inflate == "device":
+        slabs = _inflate_slabs_device(s.raw, s.path, s.blocks, dev, slab_bytes)
+    else:
+        slabs = _uploaded(_inflate_slabs(s.raw, s.path, s.blocks, threads, slab_bytes), dev)
+    try:
+        parts, counts, _ = _decode_slabs(slabs, s.skip, s.n_ref, segment_bytes, 1, s.path, dev, cut_tail=s.blocks[-1][4] - s.keep)
+    except ValueError as exc:
+        raise _not_this_file(s, f"its span does not decode ({exc})") from None
+    elsewhere = [k for k in np.flatnonzero(counts).tolist() if k != s.tid]
+    if elsewhere:
+        found = elsewhere[0] if elsewhere[0] < s.n_ref else -1
+        raise _not_this_file(s, f"a record of its span lies on reference {found}, the contig is reference {s.tid}")
+    return parts
+
+
+def read_alignment_spans(wanted, device=None, inflate: Optional[str] = None, segment_bytes: Optional[int] = None,
+                         batch_bytes: int = DEFAULT_BATCH_BYTES, threads: Optional[int] = None) -> List[AlignmentRecords]:
+    """The records of every ``(path, contig)`` of ``wanted`` -- several contigs of one file, one contig of K files, any mix --
+    through the files' ``.bai`` indexes: one `AlignmentRecords` with ``qlen`` per pair, as CUDA tensors, views of seven
+    concatenated arrays, the same values `read_alignment_file` gives for the contig.  Only the BGZF blocks between the virtual
+    offsets the index names for a contig are read (`rocco_amd.bam_index.contig_span`); a contig without a span gives empty
+    records; KeyError for a contig the file's header does not name, ValueError for a file without a ``.bai``.
+
+    The streams are grouped (`_span_groups`: under ``batch_bytes`` inflated bytes, `DEFAULT_BATCH_BYTES`); every group costs
+    one inflate (``inflate="device"``: one block table, one upload, one `rocco_hip_bgzf_inflate`; ``"host"``: the thread pool
+    places every block's useful bytes in one pinned buffer, one upload; default `DEFAULT_INFLATE`), one
+    `rocco_hip_bam_walk_records` over the useful bytes of its streams laid one behind the other -- each begins and ends on a
+    record boundary, so they form one record chain --, one `rocco_hip_bam_record_fields` and one
+    `rocco_hip_bam_stream_firsts`, which splits the chain back and checks what the index claimed: every stream begins on a
+    record start and holds records of its contig only.  A stream that alone exceeds ``batch_bytes`` goes through the slab loop
+    of `read_alignment_file`.  An index that does not describe its file (an offset inside a record, spans of other contigs,
+    another file's index) is a ValueError naming the file and the contig."""
+    import torch
+
+    inflate = DEFAULT_INFLATE if inflate is None else inflate
+    if inflate not in ("host", "device"):
+        raise ValueError(f"read_alignment_spans: inflate must be \"host\" or \"device\", not {inflate!r}")
+    batch_bytes = int(batch_bytes)
+    if batch_bytes < 1:
+        raise ValueError("read_alignment_spans: batch_bytes must be positive")
+    dev = _dp._device(device)
+    streams = _span_streams(list(wanted))
+    parts, lengths = [], []  # the fields of every group (or slab), and per stream its record count
+    with torch.cuda.device(dev):
+        for first, last in _span_groups(streams, batch_bytes):
+            group = streams[first:last]
+            if not any(s.size for s in group):
+                lengths += [0] * len(group)
+            elif len(group) == 1 and group[0].size > batch_bytes:
+                slabs = _decode_long_stream(group[0], dev, inflate, segment_bytes, threads, batch_bytes)
+                parts += slabs
+                lengths.append(sum(int(p["pos"].shape[0]) for p in slabs))
+            else:
+                fields, firsts = _decode_group(group, dev, inflate, segment_bytes, threads)
+                parts.append(fields)
+                lengths += np.diff(firsts).tolist()
+        names = [name for name in AlignmentRecords.__slots__]
+        if parts:
+            whole = {name: (torch.cat([p[name] for p in parts]) if len(parts) > 1 else parts[0][name]) for name in names}
+        else:
+            whole = {name: torch.empty(0, dtype=getattr(torch, dtype), device=dev) for name, dtype in _FIELD_DTYPES if name in names}
+    out, at = [], 0
+    for n in lengths:
+        out.append(AlignmentRecords._of(*[whole[name][at: at + n] for name in names]))
+        at += n
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # decoded files kept on the device (generate_chrom_matrix asks once per file and chromosome)
 # --------------------------------------------------------------------------------------------
 
-ALIGNMENT_CACHE_BYTES = 8 << 30  # the budget: 20 bytes per record; least recently used files leave first
+ALIGNMENT_CACHE_BYTES = 8 << 30  # the budget: 20 bytes per record; least recently used files (or contigs of indexed files) leave first
 _ALIGNMENT_CACHE: "collections.OrderedDict" = collections.OrderedDict()
+_INDEXED_FILES: dict = {}  # the `IndexedAlignmentFile` of a file key: a header and an index, no records
 _BAM_COUNT_METADATA_CACHE: dict = {}
 
 
 def clear_alignment_cache() -> None:
-    """Drops every decoded file (and the metadata derived from them)."""
+    """Drops every decoded file, every decoded contig of an indexed file (and the metadata derived from them)."""
     _ALIGNMENT_CACHE.clear()
+    _INDEXED_FILES.clear()
     _BAM_COUNT_METADATA_CACHE.clear()
 
 
@@ -595,9 +1007,135 @@ def _file_bytes(file: AlignmentFileRecords) -> int:
     return 20 * sum(len(r) for r in file.records.values())
 
 
+def _evict() -> None:
+    while len(_ALIGNMENT_CACHE) > 1 and sum(s for _, s in _ALIGNMENT_CACHE.values()) > ALIGNMENT_CACHE_BYTES:
+        _ALIGNMENT_CACHE.popitem(last=False)
+
+
+class _ContigRecords(collections.abc.Mapping):
+    """``IndexedAlignmentFile.records``: a mapping over the header's names; a contig is decoded when it is asked for."""
+
+    def __init__(self, file: "IndexedAlignmentFile"):
+        self._file = file
+
+    def __contains__(self, contig) -> bool:  # (membership is the header's: nothing is decoded)
+        return contig in self._file.tid_of
+
+    def __iter__(self):
+        return iter(name for name, _ in self._file.contigs)
+
+    def __len__(self) -> int:
+        return len(self._file.contigs)
+
+    def __getitem__(self, contig) -> AlignmentRecords:
+        if contig not in self._file.tid_of:
+            raise KeyError(contig)
+        return self._file.load([contig])[0]
+
+
+class _LazyTracks:
+    """``IndexedAlignmentFile.tracks()``: (contig, records) in header order, contigs without records left out, each decoded
+    when the iteration reaches it -- a probe that stops early (`rocco_amd.readtracks._head_chunks`) decodes the leading
+    contigs it reaches and no more."""
+
+    carries_qlen = True  # (records read through the index always carry `qlen`)
+
+    def __init__(self, file: "IndexedAlignmentFile"):
+        self._file = file
+
+    def __iter__(self):
+        for name, _ in self._file.contigs:
+            if self._file.count(name) == 0:
+                continue
+            records = self._file.records[name]
+            if len(records) > 0:
+                yield name, records
+
+
+class IndexedAlignmentFile(AlignmentFileRecords):
+    """A BAM file with a ``.bai`` index as `AlignmentFileRecords`: the header's ``contigs`` and the ``index``
+    (`rocco_amd.bam_index.BamIndex`), no records until they are asked for.  ``records`` is a mapping over the header's names
+    (membership is the header's, as for a decoded file); a contig is decoded on first access through `read_alignment_spans`
+    and kept in the alignment cache per contig.  `count` answers the length of a contig from the index statistics without
+    decoding; `load` fetches several contigs in one call; `tracks()` is lazy."""
+
+    def __init__(self, path: str, front: "_BamFront", key):
+        AlignmentFileRecords.__init__(self, front.contigs, {}, name=path)
+        self.path, self.index, self.tid_of, self.key = path, front.index, front.tid_of, key
+        self.records = _ContigRecords(self)
+
+    def count(self, contig: str) -> Optional[int]:
+        """The records of the contig by the index statistics (mapped + unmapped); 0 for a contig without a span; None where
+        the index has a span and no statistics for it."""
+        tid = self.tid_of[contig]
+        if _bai.contig_span(self.index, tid) is None:
+            return 0
+        stats = _bai.contig_stats(self.index, tid)
+        return None if stats is None else int(stats[0] + stats[1])
+
+    def index_read_counts(self, exclude_chromosomes=()) -> Optional[Tuple[int, int]]:
+        """(mapped, unmapped) summed over the contigs not in ``exclude_chromosomes`` from the index statistics, as the
+        reference's ``ccounts_getMappedReadCount`` takes them (``hts_idx_get_stat``); None for an index without pseudo-bins."""
+        excluded, mapped, unmapped = {str(c) for c in (exclude_chromosomes or ())}, 0, 0
+        for name, _ in self.contigs:
+            if name in excluded or _bai.contig_span(self.index, self.tid_of[name]) is None:
+                continue
+            stats = _bai.contig_stats(self.index, self.tid_of[name])
+            if stats is None:
+                return None
+            mapped, unmapped = mapped + int(stats[0]), unmapped + int(stats[1])
+        return mapped, unmapped
+
+    def load(self, names) -> List[AlignmentRecords]:
+        """The records of ``names``: those not in the cache are read in ONE `read_alignment_spans` call."""
+        return _load_contigs([(self, str(n)) for n in names])
+
+    def tracks(self, names=None):
+        """(contig, records), contigs without records left out: lazily in header order, or for ``names`` in their order,
+        fetched in one call."""
+        if names is None:
+            return _LazyTracks(self)
+        names = [n for n in names if n in self.tid_of]
+        return [(n, r) for n, r in zip(names, self.load(names)) if len(r) > 0]
+
+
+def _load_contigs(pairs) -> List[AlignmentRecords]:
+    """The records of every (`IndexedAlignmentFile`, contig): from the per-contig cache, the rest from ONE
+    `read_alignment_spans` call, kept under `ALIGNMENT_CACHE_BYTES` (least recently used entries leave first)."""
+    out, missing = [None] * len(pairs), []
+    for i, (file, contig) in enumerate(pairs):
+        hit = _ALIGNMENT_CACHE.get(file.key + (contig,))
+        if hit is not None:
+            _ALIGNMENT_CACHE.move_to_end(file.key + (contig,))
+            out[i] = hit[0]
+        else:
+            missing.append(i)
+    if missing:
+        order = {}
+        for i in missing:  # (a pair asked for twice is read once)
+            order.setdefault((pairs[i][0].key, pairs[i][1]), i)
+        first = list(order.values())
+        read = read_alignment_spans([(pairs[i][0].path, pairs[i][1]) for i in first], inflate=DEFAULT_INFLATE)
+        by_key = {}
+        for i, records in zip(first, read):
+            by_key[(pairs[i][0].key, pairs[i][1])] = records
+            _ALIGNMENT_CACHE[pairs[i][0].key + (pairs[i][1],)] = (records, 20 * len(records))
+        for i in missing:
+            out[i] = by_key[(pairs[i][0].key, pairs[i][1])]
+        _evict()
+    return out
+
+
 def _cached_file(bam_file: str) -> AlignmentFileRecords:
-    stat = os.stat(bam_file)
-    key = (os.path.abspath(bam_file), int(stat.st_size), int(stat.st_mtime_ns))
+    key = _file_key(bam_file)
+    if USE_INDEX:
+        front = _bam_front(bam_file)
+        if front is not None:
+            key = key + (front.index.name, front.index.size)
+            file = _INDEXED_FILES.get(key)
+            if file is None or file.index is not front.index:
+                file = _INDEXED_FILES[key] = IndexedAlignmentFile(bam_file, front, key)
+            return file
     hit = _ALIGNMENT_CACHE.get(key)
     if hit is not None:
         _ALIGNMENT_CACHE.move_to_end(key)
@@ -606,8 +1144,7 @@ def _cached_file(bam_file: str) -> AlignmentFileRecords:
     file.name = bam_file
     size = _file_bytes(file)
     _ALIGNMENT_CACHE[key] = (file, size)
-    while len(_ALIGNMENT_CACHE) > 1 and sum(s for _, s in _ALIGNMENT_CACHE.values()) > ALIGNMENT_CACHE_BYTES:
-        _ALIGNMENT_CACHE.popitem(last=False)
+    _evict()
     return file
 
 
@@ -684,6 +1221,27 @@ class _HeldRecords(logging.Filter):
         return False
 
 
+def _prefetch_chromosome(input_files, chromosome: str, chrom_sizes_file: str) -> None:
+    """The chromosome's records of every indexed file among ``input_files`` into the cache, in ONE `read_alignment_spans` call
+    (files without an index keep the whole-file route).  Nothing is fetched where a file or the chromosome is missing, and an
+    error raised here is dropped: it belongs to its file's own turn in the loop that follows, in the reference's order."""
+    if not USE_INDEX or not os.path.exists(chrom_sizes_file) or not all(os.path.exists(f) for f in input_files):
+        return
+    try:
+        if chromosome not in _rt.get_chroms_and_sizes(chrom_sizes_file):
+            return
+        pairs = []
+        for bam_file in input_files:
+            if _bai.bam_index_path(bam_file) is not None:
+                file = _cached_file(bam_file)
+                if isinstance(file, IndexedAlignmentFile) and chromosome in file.records:
+                    pairs.append((file, chromosome))
+        if pairs:
+            _load_contigs(pairs)
+    except (ValueError, KeyError, OSError):
+        return
+
+
 def generate_chrom_matrix_device(chromosome: str, input_files: list, chrom_sizes_file: str, step: int, const_scale: float = 1.0,
                                  round_digits: int = 5, scale_by_step: bool = False, effective_genome_size: float = -1,
                                  norm_method: str = "RPGC", min_mapping_score: int = 10, flag_include=None, flag_exclude: int = 3844,
@@ -708,6 +1266,7 @@ def generate_chrom_matrix_device(chromosome: str, input_files: list, chrom_sizes
     if ignore_for_norm is None:
         ignore_for_norm = ["chrX", "chrY", "chrM"]
     K = len(input_files)
+    _prefetch_chromosome(input_files, chromosome, chrom_sizes_file)
     before, records_list, metadata_list, present, chrom_size = [[] for _ in range(K)], [], [], [], 0
     held = _HeldRecords()
     logger.addFilter(held)

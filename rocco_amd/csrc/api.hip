@@ -1735,6 +1735,26 @@ int rocco_hip_bam_record_fields(rocco_hip_solver *solver, const uint8_t *bytes_d
                                     solver->dev_misc.ptr, (hipStream_t)stream);
 }
 
+int rocco_hip_bam_stream_firsts(rocco_hip_solver *solver, const int64_t *offsets_dev, const int32_t *tid_dev, size_t n,
+                                const int64_t *bounds_host, const int32_t *expect_tid_host, size_t n_streams, int64_t *firsts_out_host,
+                                int64_t *report_out_host, void *stream)
+{
+    if (solver == nullptr || bounds_host == nullptr || expect_tid_host == nullptr || firsts_out_host == nullptr || report_out_host == nullptr ||
+        n_streams < 1 || n_streams >= ((size_t)1 << 24) || n >= ((size_t)1 << 55) || (n > 0 && (offsets_dev == nullptr || tid_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    for (size_t j = 0; j < n_streams; ++j) {
+        if (bounds_host[j] < 0 || bounds_host[j] > bounds_host[j + 1]) {
+            return ROCCO_HIP_EINVAL;
+        }
+    }
+    if (const int rc = enter_record_call(solver, bam_stream_firsts_scratch_bytes(n_streams)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_bam_stream_firsts(offsets_dev, tid_dev, n, bounds_host, expect_tid_host, n_streams, firsts_out_host, report_out_host,
+                                    solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
 void rocco_hip_bam_shape(int *shape_out)
 {
     shape_out[0] = ROCCO_BAM_GUESS_DEPTH;

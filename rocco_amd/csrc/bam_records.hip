@@ -307,6 +307,77 @@ __global__ __launch_bounds__(kThreads) void bam_contig_first_kernel(const int *_
     }
 }
 
+// One lane per record of a chain walked over K streams laid one behind the other (rocco_amd/bam.py: read_alignment_spans):
+// bound[j], j = 0 .. K, are the ascending byte bounds of the streams (an empty stream repeats a bound, bound[K] = n_bytes).
+// Record r at offset o belongs to stream s = (the number of j in [0, K] with bound[j] <= o) - 1, the upper bound, so that
+// among repeated bounds the last one takes the record and the streams before it stay empty.  firsts[j]: the first record at
+// or after bound[j] (n where there is none).  The first record of its stream writes firsts[j] for every j behind the
+// stream of the record before it, the last record writes those behind its own: every firsts[j] is written once.
+// error: the lowest (stream << 8 | code) seen.
+__global__ __launch_bounds__(kThreads) void bam_stream_firsts_kernel(const long long *__restrict__ offsets, const int *__restrict__ tid,
+                                                                    long long n, const long long *__restrict__ bound,
+                                                                    const int *__restrict__ expect_tid, int K,
+                                                                    long long *__restrict__ firsts, unsigned long long *__restrict__ error)
+{
+    const long long stride = (long long)gridDim.x * kThreads;
+    const long long lane = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (n == 0) {
+        for (long long j = lane; j <= K; j += stride) {
+            firsts[j] = 0;
+        }
+        return;
+    }
+    for (long long r = lane; r < n; r += stride) {
+        const long long o = offsets[r];
+        // s: the last j in [0, K) with bound[j] <= o (0 where o lies in front of bound[0]: a seam error below)
+        int lo = 0, hi = K;  // the count of j in [0, K) with bound[j] <= o lies in [lo, hi]
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (bound[mid] <= o) {
+                lo = mid + 1;
+            } else {
+                hi = mid;
+            }
+        }
+        const int s = lo > 0 ? lo - 1 : 0;
+        int before = -1;  // the stream of the record in front (-1: none)
+        if (r > 0) {
+            const long long o0 = offsets[r - 1];
+            int lo0 = 0, hi0 = s + 1;  // (offsets ascend: it is no later than s)
+            while (lo0 < hi0) {
+                const int mid = lo0 + ((hi0 - lo0) >> 1);
+                if (bound[mid] <= o0) {
+                    lo0 = mid + 1;
+                } else {
+                    hi0 = mid;
+                }
+            }
+            before = lo0 > 0 ? lo0 - 1 : 0;
+        }
+        if (before < s) {  // the first record of stream s: every bound passed since the record in front must lie on it
+            if (o != bound[before + 1]) {
+                note_error(error, before + 1, ROCCO_BAM_ERR_SEAM);
+            }
+            for (int j = before + 1; j <= s; ++j) {
+                firsts[j] = r;
+            }
+        }
+        if (tid[r] != expect_tid[s]) {
+            note_error(error, s, ROCCO_BAM_ERR_SPAN_TID);
+        }
+        if (r == n - 1) {
+            if (o >= bound[K]) {
+                note_error(error, s, ROCCO_BAM_ERR_SEAM);
+            } else if (s + 1 < K && bound[s + 1] != bound[K]) {  // (bytes behind the last record that belong to a later stream)
+                note_error(error, s + 1, ROCCO_BAM_ERR_SEAM);
+            }
+            for (int j = s + 1; j <= K; ++j) {
+                firsts[j] = n;
+            }
+        }
+    }
+}
+
 size_t walk_scan_bytes(size_t n_segments)
 {
     size_t bytes = 0;
@@ -427,6 +498,46 @@ int launch_bam_record_fields(const uint8_t *bytes_dev, size_t n_bytes, const int
     }
     for (size_t k = 0; k < firsts.size(); ++k) {
         contig_first_out_host[k] = firsts[k];
+    }
+    report_out_host[0] = packed == ~0ULL ? 0 : (int64_t)(packed & 0xffULL);
+    report_out_host[1] = packed == ~0ULL ? -1 : (int64_t)(packed >> 8);
+    return ROCCO_HIP_OK;
+}
+
+size_t bam_stream_firsts_scratch_bytes(size_t K) { return BamStreamFirstsLayout(K).bytes; }
+
+int launch_bam_stream_firsts(const int64_t *offsets_dev, const int32_t *tid_dev, size_t n, const int64_t *bounds_host,
+                             const int32_t *expect_tid_host, size_t K, int64_t *firsts_out_host, int64_t *report_out_host, void *scratch_dev,
+                             hipStream_t stream)
+{
+    const BamStreamFirstsLayout at(K);
+    char *sc = (char *)scratch_dev;
+    long long *bound = (long long *)(sc + at.bound), *firsts = (long long *)(sc + at.firsts);
+    int *expect = (int *)(sc + at.expect);
+    unsigned long long *error = (unsigned long long *)(sc + at.error);
+    std::vector<long long> back(K + 1, 0);
+    unsigned long long packed = ~0ULL;
+    const int queued = queue_then_drain(stream, [&]() -> int {
+        ROCCO_HIP_TRY(hipMemcpyAsync(bound, bounds_host, (K + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+        if (K > 0) {
+            ROCCO_HIP_TRY(hipMemcpyAsync(expect, expect_tid_host, K * sizeof(int), hipMemcpyHostToDevice, stream));
+        }
+        ROCCO_HIP_TRY(hipMemsetAsync(error, 0xff, sizeof(unsigned long long), stream));
+        const long long items = n > K + 1 ? (long long)n : (long long)K + 1;
+        hipLaunchKernelGGL(bam_stream_firsts_kernel, dim3(bam_grid_for(items, kThreads)), dim3(kThreads), 0, stream,
+                           (const long long *)offsets_dev, (const int *)tid_dev, (long long)n, (const long long *)bound, (const int *)expect,
+                           (int)K, firsts, error);
+        ROCCO_HIP_TRY(hipGetLastError());
+        ROCCO_HIP_TRY(hipMemcpyAsync(back.data(), firsts, back.size() * sizeof(long long), hipMemcpyDeviceToHost, stream));
+        ROCCO_HIP_TRY(hipMemcpyAsync(&packed, error, sizeof(packed), hipMemcpyDeviceToHost, stream));
+        ROCCO_HIP_TRY(hipStreamSynchronize(stream));
+        return ROCCO_HIP_OK;
+    });
+    if (queued != ROCCO_HIP_OK) {
+        return queued;
+    }
+    for (size_t j = 0; j <= K; ++j) {
+        firsts_out_host[j] = back[j];
     }
     report_out_host[0] = packed == ~0ULL ? 0 : (int64_t)(packed & 0xffULL);
     report_out_host[1] = packed == ~0ULL ? -1 : (int64_t)(packed >> 8);

@@ -396,6 +396,10 @@ int launch_bam_record_fields(const uint8_t *bytes_dev, size_t n_bytes, const int
                              int32_t *pos_out_dev, int32_t *end_out_dev, int32_t *isize_out_dev, uint16_t *flag_out_dev,
                              uint8_t *mapq_out_dev, uint8_t *mate_same_out_dev, int32_t *qlen_out_dev, int64_t *contig_first_out_host,
                              int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
+size_t bam_stream_firsts_scratch_bytes(size_t K);
+int launch_bam_stream_firsts(const int64_t *offsets_dev, const int32_t *tid_dev, size_t n, const int64_t *bounds_host,
+                             const int32_t *expect_tid_host, size_t K, int64_t *firsts_out_host, int64_t *report_out_host, void *scratch_dev,
+                             hipStream_t stream);
 
 // ---- bgzf_inflate.hip -------------------------------------------------------------------------
 size_t bgzf_inflate_scratch_bytes(size_t n_blocks);

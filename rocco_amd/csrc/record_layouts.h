@@ -185,6 +185,21 @@ struct BamFieldsLayout {
     }
 };
 
+// launch_bam_stream_firsts: the K + 1 bounds and the K + 1 first records (int64), the K expected reference ids (int32), the
+// error word
+struct BamStreamFirstsLayout {
+    size_t bound, firsts, expect, error, bytes;
+    explicit BamStreamFirstsLayout(size_t K)
+    {
+        Layout lay;
+        bound = lay.at((K + 1) * sizeof(long long));
+        firsts = lay.at((K + 1) * sizeof(long long));
+        expect = lay.at((K > 0 ? K : 1) * sizeof(int));
+        error = lay.at(sizeof(unsigned long long));
+        bytes = lay.bytes();
+    }
+};
+
 // launch_bgzf_inflate: per block its status (int32; unused where the caller brings its own), the bytes it inflates to (int64);
 // the word of the first failing block; the report
 struct BgzfInflateLayout {

@@ -821,6 +821,8 @@ def _as_file(file) -> AlignmentFileRecords:
 
 
 def _need_qlen(file: AlignmentFileRecords, tracks, what: str) -> None:
+    if getattr(tracks, "carries_qlen", False):  # (lazy tracks of an indexed file: decoded as a probe reaches them, always with `qlen`)
+        return
     for contig, records in tracks:
         if records.qlen is None:
             raise ValueError(f"{what}: the records of {file.name or 'the file'} on {contig} carry no `qlen` (query length); build "
@@ -923,6 +925,10 @@ def alignment_mapped_read_count_from_records(file, exclude_chromosomes=()) -> Tu
     reference's callers drop it)."""
     file = _as_file(file)
     excluded = {str(c) for c in (exclude_chromosomes or ())}
+    from_index = getattr(file, "index_read_counts", None)  # (an indexed file: the index statistics, as the reference reads them)
+    counted = from_index(excluded) if from_index is not None else None
+    if counted is not None:
+        return counted
     tracks = [(n, r) for n, r in file.tracks() if n not in excluded]
     if not tracks:
         return 0, 0
