@@ -549,7 +549,10 @@ int rocco_hip_bartlett_multipliers_f64(rocco_hip_solver *solver, const double *i
  * rocco_hip_sort_f64: ascending sorted copy of a float64 vector (-0.0 before +0.0).  Every np.median / MAD / median
  *   of the positive scores of the estimate is an order statistic of it.
  * rocco_hip_sorted_probe_f64: values at up to 8 ranks of a sorted vector, and for up to 8 thresholds t how many
- *   elements x have (x - shift) <= t and (x - shift) < t (binary search: x - shift is monotone in x).
+ *   elements x have (x - shift) <= t and (x - shift) < t (binary search: x - shift is monotone in x).  The sort orders bit
+ *   patterns: NaNs with the sign set come first, the other NaNs last.  They satisfy no comparison and the search skips
+ *   them: a count is the index of the first element past those that satisfy it, leading NaNs included (t = -inf, "<": the
+ *   number of leading NaNs; t = +inf, "<=": the index of the first trailing NaN).
  * rocco_hip_autocovariance_sums_f64: sums_out[k] = sum_i (x_i - mean)(x_{i+k} - mean), k = 0..max_lag (< n; any number of lags,
  *   1024 per pair of launches), summed in a fixed order.  (The reference takes them from an FFT: agreement to ~1e-13 relative, not bitwise.)
  * rocco_hip_negative_part_f64: out = scores - clip(scores, 0, None) (the residual template of the direct-score null).

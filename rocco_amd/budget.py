@@ -430,7 +430,14 @@ def estimate_budget_nonnull_fraction_from_score_track(score_track, dependence_la
     _native.check(lib.rocco_hip_negative_part_f64(solver.handle, s_t.data_ptr(), template_t.data_ptr(), n, stream),
                   "rocco_hip_negative_part_f64")
     sorted_template = sort_device(template_t)
-    null_center = _median_of_sorted_range(sorted_template, 0, n)
+    # A NaN score, or +inf (inf - inf), leaves a NaN in the template; np.median is then NaN and the reference refuses the
+    # track.  The sort orders bit patterns -- sign-set NaNs first, the others last -- so its middle ranks would be finite:
+    # the two ends are read with them.
+    mid_lo, mid_hi = (n - 1) // 2, n // 2
+    (c_lo, c_hi, lowest, highest), _, _ = sorted_probe(sorted_template, ranks=(mid_lo, mid_hi, 0, n - 1))
+    if np.isnan(lowest) or np.isnan(highest):
+        raise ValueError("Direct-score budget null fit produced non-finite values")
+    null_center = c_lo if mid_lo == mid_hi else (c_lo + c_hi) / 2.0
     # residuals (template - centre) <= 0 are the first `m` of the sorted template (x - c is monotone in x)
     _, (m,), (n_below,) = sorted_probe(sorted_template, thresholds=(0.0,), shift=null_center)
     if m == 0:  # cannot happen (the median has at least one element at or below it); kept for the reference's branch
@@ -970,8 +977,10 @@ def _resolve_chrom_gamma(chrom: str, args: dict, chrom_scores, budget_rate_meta:
     positive_count, positive_median = 0, 1.0
     if n > 0:
         ordered = sort_device(s_t)
-        _, (not_positive,), _ = sorted_probe(ordered, thresholds=(0.0,))  # scores <= 0 come first
-        positive_count = n - not_positive
+        # scores <= 0 come first (behind the sign-set NaNs); the positive ones end where the other NaNs begin: the
+        # reference's `scores > 0.0` drops every NaN and keeps +inf
+        _, (not_positive, not_trailing_nan), _ = sorted_probe(ordered, thresholds=(0.0, np.inf))
+        positive_count = not_trailing_nan - not_positive
         if positive_count > 0:
             positive_median = _median_of_sorted_range(ordered, not_positive, positive_count)
     tau = max(1.0, float(budget_rate_meta.get("autocorrelation_time", 1.0)))

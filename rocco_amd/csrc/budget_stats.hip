@@ -41,7 +41,10 @@ __global__ __launch_bounds__(256) void from_key_kernel(const u64 *__restrict__ k
 }
 
 // values at ranks; per threshold t: how many elements satisfy (x - shift) <= t and (x - shift) < t (x - shift is
-// monotone in x, so a binary search on the sorted x finds both)
+// monotone in x, so a binary search on the sorted x finds both).  A NaN satisfies no comparison; the sort puts the sign-set
+// ones first and the others last, and the search leaves them there: a count is the index of the first element past those
+// that satisfy the comparison, the leading NaNs included (threshold -inf, strict: their number; threshold +inf: the index
+// of the first trailing NaN).
 __global__ __launch_bounds__(64) void sorted_probe_kernel(const double *__restrict__ sorted, long long n, SortedProbe p,
                                                          double *__restrict__ values_out, long long *__restrict__ counts_out)
 {
@@ -56,8 +59,9 @@ __global__ __launch_bounds__(64) void sorted_probe_kernel(const double *__restri
             long long lo = 0, hi = n;  // first index whose shifted value is NOT (<= thr / < thr)
             while (lo < hi) {
                 const long long mid = lo + (hi - lo) / 2;
-                const double v = sorted[mid] - p.shift;
-                const bool inside = strict ? (v < thr) : (v <= thr);
+                const double x = sorted[mid];
+                const double v = x - p.shift;
+                const bool inside = (x != x) ? (__double_as_longlong(x) < 0) : (strict ? (v < thr) : (v <= thr));
                 if (inside) {
                     lo = mid + 1;
                 } else {
