@@ -955,7 +955,7 @@ void rocco_hip_bam_shape(int *shape_out);
 #define ROCCO_BGZF_ERR_LENGTH 2
 #define ROCCO_BGZF_ERR_CRC 3
 #define ROCCO_BGZF_ERR_TABLE 4
-#define ROCCO_BGZF_MAX_GRID (1 << 20) /* workgroups of bgzf_inflate_kernel and bgzf_crc_kernel at most; unit: one BGZF block (a workgroup strides over the rows i, i + grid, ...) */
+#define ROCCO_BGZF_MAX_GRID (1 << 20) /* workgroups of inflate_kernel<BgzfFraming> and check_kernel<BgzfFraming> at most; unit: one BGZF block (a workgroup strides over the rows i, i + grid, ...) */
 int rocco_hip_bgzf_inflate(rocco_hip_solver *solver, const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks,
                            uint8_t *out_dev, size_t n_out, int32_t *status_out_dev, int64_t *report_out_host, void *stream);
 int rocco_hip_bgzf_inflate_host(rocco_hip_solver *solver, const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks,
@@ -1000,7 +1000,7 @@ void rocco_hip_bgzf_shape(int *shape_out);
 #define ROCCO_ZLIB_ERR_HEADER 5
 #define ROCCO_ZLIB_ERR_ADLER 6
 #define ROCCO_ZLIB_ERR_TRUNCATED 7
-#define ROCCO_ZLIB_MAX_GRID (1 << 16) /* workgroups of zlib_inflate_kernel and zlib_adler_kernel at most; unit: one data block */
+#define ROCCO_ZLIB_MAX_GRID (1 << 16) /* workgroups of inflate_kernel<ZlibFraming> and check_kernel<ZlibFraming> at most; unit: one data block */
 int rocco_hip_zlib_inflate(rocco_hip_solver *solver, const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks,
                            uint8_t *out_dev, size_t n_out, int32_t *status_out_dev, int64_t *produced_out_dev, int64_t *report_out_host,
                            void *stream);

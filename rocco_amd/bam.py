@@ -27,7 +27,6 @@ import multiprocessing
 import os
 import struct
 import zlib
-from concurrent.futures import ThreadPoolExecutor
 from typing import Iterator, List, Optional, Tuple
 
 import numpy as np
@@ -36,6 +35,10 @@ from . import _native
 from . import bam_index as _bai
 from . import dp as _dp
 from . import readtracks as _rt
+from .inflate import (  # noqa: F401  (what the bigWig reader shares; the names stay importable from here)
+    BGZF_ERR_CRC, BGZF_ERR_LENGTH, BGZF_ERR_STREAM, BGZF_ERR_TABLE, BGZF_MAX_GRID, BGZF_MAX_ISIZE, BGZF_STREAM_REASONS, BGZF_TABLE_COLUMNS,
+    BGZF_THREADS, _STREAM_REASON_TEXT, SpanList, _default_threads, _host_buffer, bgzf_block_table, bgzf_shape, inflate_blocks_device,
+    inflate_blocks_host, on_pool, refuse_large_blocks, upload_blocks)
 from .readtracks import AlignmentFileRecords, AlignmentRecords
 
 logger = _rt.logger  # (the reference's reader logs where its readtracks module does)
@@ -66,27 +69,10 @@ _ERROR_TEXT = {
     ERR_OFFSET: "no record is framed there",
 }
 
-# ROCCO_BGZF_* of include/rocco_hip.h
-BGZF_THREADS, BGZF_TABLE_COLUMNS, BGZF_MAX_ISIZE, BGZF_STREAM_REASONS = 64, 5, 65536, 12
-BGZF_ERR_STREAM, BGZF_ERR_LENGTH, BGZF_ERR_CRC, BGZF_ERR_TABLE = range(1, 5)
-BGZF_MAX_GRID = 1 << 20  # workgroups of an inflate launch at most: block i + BGZF_MAX_GRID is the next turn of block i's workgroup
-_STREAM_REASON_TEXT = {
-    1: "invalid block type", 2: "invalid stored block lengths", 3: "too many length or distance symbols", 4: "invalid code lengths set",
-    5: "invalid bit length repeat", 6: "invalid code -- missing end-of-block", 7: "invalid literal/lengths set", 8: "invalid distances set",
-    9: "invalid literal/length code", 10: "invalid distance code", 11: "invalid distance too far back", 12: "incomplete or truncated stream",
-}
-
 
 # --------------------------------------------------------------------------------------------
 # BGZF: the front both inflates share (source, blocks, slab rule, error words) and the host inflate
 # --------------------------------------------------------------------------------------------
-
-def _default_threads() -> int:
-    try:
-        return max(1, min(16, len(os.sched_getaffinity(0))))
-    except AttributeError:  # (no affinity interface on this platform)
-        return 1
-
 
 def _source_bytes(source):
     if isinstance(source, (bytes, bytearray, memoryview)):
@@ -223,19 +209,6 @@ def _whole_or_slabs(slabs, slab_bytes: Optional[int], empty):
     return slabs[0] if slabs else empty()
 
 
-def _host_buffer(n: int) -> np.ndarray:
-    """n bytes of host memory as a uint8 array: pinned where a device is present (uploads from it run asynchronously)."""
-    import torch
-
-    t = torch.empty(max(int(n), 1), dtype=torch.uint8)
-    if torch.cuda.is_available():
-        try:
-            t = t.pin_memory()
-        except RuntimeError:  # (no pinned memory left: ordinary memory uploads as well, synchronously)
-            pass
-    return t.numpy()[: int(n)]
-
-
 def _inflate_block(raw: memoryview, name: str, index: int, block) -> bytes:
     """One block through zlib, its length and CRC32 checked."""
     at, lo, hi, crc, isize = block
@@ -252,19 +225,16 @@ def _inflate_block(raw: memoryview, name: str, index: int, block) -> bytes:
 
 
 def _inflate_slabs(raw: memoryview, name: str, blocks, threads: Optional[int], slab_bytes: Optional[int]) -> Iterator[np.ndarray]:
-    threads = _default_threads() if threads is None else max(1, int(threads))
-    with ThreadPoolExecutor(max_workers=threads) as pool:
-        for first, last in _slab_groups(blocks, slab_bytes):
-            starts = np.zeros(last - first + 1, dtype=np.int64)
-            np.cumsum([b[4] for b in blocks[first:last]], out=starts[1:])
-            out = _host_buffer(int(starts[-1]))
+    for first, last in _slab_groups(blocks, slab_bytes):
+        starts = np.zeros(last - first + 1, dtype=np.int64)
+        np.cumsum([b[4] for b in blocks[first:last]], out=starts[1:])
+        out = _host_buffer(int(starts[-1]))
 
-            def one(k):
-                out[starts[k - first]: starts[k - first + 1]] = np.frombuffer(_inflate_block(raw, name, k, blocks[k]), dtype=np.uint8)
+        def one(k):
+            out[starts[k - first]: starts[k - first + 1]] = np.frombuffer(_inflate_block(raw, name, k, blocks[k]), dtype=np.uint8)
 
-            for _ in pool.map(one, range(first, last)):
-                pass
-            yield out
+        on_pool(one, range(first, last), threads)
+        yield out
 
 
 def inflate_bgzf(source, threads: Optional[int] = None, slab_bytes: Optional[int] = None):
@@ -286,64 +256,6 @@ def inflate_bgzf(source, threads: Optional[int] = None, slab_bytes: Optional[int
 # device: BGZF (csrc/bgzf_inflate.hip, csrc/inflate_core.h)
 # --------------------------------------------------------------------------------------------
 
-def bgzf_shape() -> dict:
-    """`rocco_hip_bgzf_shape`: the lanes per block, the columns of the block table, the largest ISIZE, the stream reasons."""
-    shape = (ctypes.c_int * 4)()
-    _native.load().rocco_hip_bgzf_shape(shape)
-    return {"threads": int(shape[0]), "table_columns": int(shape[1]), "max_isize": int(shape[2]), "stream_reasons": int(shape[3])}
-
-
-def bgzf_block_table(blocks, base: int = 0) -> np.ndarray:
-    """The block table of `rocco_hip_bgzf_inflate` for `_bgzf_blocks` rows: int64 [n][5] = first byte of the deflate data
-    (relative to ``base``), one past its last, ISIZE, CRC32, the prefix sum of ISIZE."""
-    table = np.zeros((len(blocks), BGZF_TABLE_COLUMNS), dtype=np.int64)
-    if blocks:
-        rows = np.asarray(blocks, dtype=np.int64)
-        table[:, 0], table[:, 1], table[:, 2], table[:, 3] = rows[:, 1] - base, rows[:, 2] - base, rows[:, 4], rows[:, 3]
-        table[1:, 4] = np.cumsum(table[:-1, 2])
-    return table
-
-
-def _report(back) -> dict:
-    return {"block": int(back[0]), "status": int(back[1]), "produced": int(back[2])}
-
-
-def inflate_blocks_host(comp, table: np.ndarray, out: np.ndarray):
-    """`rocco_hip_bgzf_inflate_host` (test support: the kernels' decode rules compiled for the host, on the calling thread):
-    inflates the rows of ``table`` from ``comp`` (bytes or a uint8 array) into the uint8 array ``out``; returns (the int32
-    status per block, the report ``block`` / ``status`` / ``produced``)."""
-    comp = np.ascontiguousarray(np.frombuffer(comp, dtype=np.uint8) if not isinstance(comp, np.ndarray) else comp)
-    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, BGZF_TABLE_COLUMNS)
-    if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
-        raise TypeError("inflate_blocks_host: out must be a writable contiguous uint8 array")
-    status = np.zeros(table.shape[0], dtype=np.int32)
-    back = (ctypes.c_longlong * 4)()
-    _native.check(_native.load().rocco_hip_bgzf_inflate_host(
-        None, comp.ctypes.data if comp.size else None, comp.size, table.ctypes.data if table.size else None, table.shape[0],
-        out.ctypes.data if out.size else None, out.size, status.ctypes.data if status.size else None, back), "rocco_hip_bgzf_inflate_host")
-    return status, _report(back)
-
-
-def inflate_blocks_device(comp_t, table_t, out_t, want_status: bool = False):
-    """`rocco_hip_bgzf_inflate`: inflates the rows of the int64 CUDA tensor ``table_t`` ([n][5]) from the uint8 CUDA tensor
-    ``comp_t`` into the uint8 CUDA tensor ``out_t``; returns (the int32 status per block as a CUDA tensor, or None, the report)."""
-    import torch
-
-    for t, dtype in ((comp_t, torch.uint8), (table_t, torch.int64), (out_t, torch.uint8)):
-        if not _dp._is_tensor(t) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.device != out_t.device:
-            raise TypeError("inflate_blocks_device: contiguous CUDA tensors on one device are required (uint8, int64, uint8)")
-    if table_t.numel() % BGZF_TABLE_COLUMNS:
-        raise ValueError("inflate_blocks_device: the block table has 5 columns")
-    n_blocks = table_t.numel() // BGZF_TABLE_COLUMNS
-    status = torch.empty(n_blocks, dtype=torch.int32, device=out_t.device) if want_status else None
-    back = (ctypes.c_longlong * 4)()
-    _native.check(_native.load().rocco_hip_bgzf_inflate(
-        _native.solver_for(out_t.device.index).handle, comp_t.data_ptr() or None, comp_t.numel(), table_t.data_ptr() or None, n_blocks,
-        out_t.data_ptr() or None, out_t.numel(), status.data_ptr() if status is not None and n_blocks else None, back,
-        _dp._stream_ptr(out_t)), "rocco_hip_bgzf_inflate")
-    return status, _report(back)
-
-
 def _bgzf_error(where: str, isize: int, report: dict) -> ValueError:
     """The host path's words (`_inflate_block`) for a block the device refused."""
     code, why = report["status"] & 0xFF, report["status"] >> 8
@@ -359,22 +271,17 @@ def _bgzf_error(where: str, isize: int, report: dict) -> ValueError:
 def _inflate_slabs_device(raw: memoryview, name: str, blocks, dev, slab_bytes: Optional[int]):
     import torch
 
-    for index, block in enumerate(blocks):
-        if block[4] > BGZF_MAX_ISIZE:
-            raise ValueError(f"{_block_where(name, index, block[0])}: length mismatch (ISIZE says {block[4]}, a BGZF block "
-                             f"holds at most {BGZF_MAX_ISIZE} bytes; inflate=\"host\" reads a file that breaks this rule)")
+    refuse_large_blocks(blocks, lambda index, block: _block_where(name, index, block[0]))
     for first, last in _slab_groups(blocks, slab_bytes):
         group = blocks[first:last]
-        base, end = group[0][1], group[-1][2]
+        base, end = group[0][1], group[-1][2]  # (a slab's blocks lie one behind the other: one span, headers and trailers ride along)
         table = bgzf_block_table(group, base)
-        head = table.size * 8
-        staged = _host_buffer(head + end - base)  # (pinned: the table and the compressed bytes go up in one asynchronous copy)
-        staged[:head] = table.reshape(-1).view(np.uint8)
-        staged[head:] = np.frombuffer(raw[base:end], dtype=np.uint8)
+        spans = SpanList()
+        spans.add(raw, base, end)
         with torch.cuda.device(dev):
-            up = torch.from_numpy(staged).to(dev, non_blocking=True)
+            table_t, comp_t = upload_blocks(table, spans.spans, spans.n_comp, dev)
             out = torch.empty(int(table[-1, 2] + table[-1, 4]), dtype=torch.uint8, device=dev)
-            _, report = inflate_blocks_device(up[head:], up[:head].view(torch.int64), out)  # (synchronises: `staged` may go)
+            _, report = inflate_blocks_device(comp_t, table_t, out)  # (synchronises: the upload's pinned buffer may go)
         if report["block"] >= 0:
             bad = group[report["block"]]
             raise _bgzf_error(_block_where(name, first + report["block"], bad[0]), bad[4], report)
@@ -793,52 +700,44 @@ def _span_groups(streams, batch_bytes: int):
         first = last
 
 
-def _group_bytes_device(group, dev):
-    """The useful bytes of the group's streams, one behind the other, from ONE block table, one pinned staging buffer, one
-    upload and one `rocco_hip_bgzf_inflate`; a block that two neighbouring streams share is inflated once."""
-    import torch
-
-    rows, owner, spans, comp_at, out_at = [], [], [], 0, 0  # spans: [file bytes, file offset, size] of every coalesced run
+def _group_layout(group):
+    """ONE block table and one compressed buffer for the blocks of the group's streams: (the table, the span list, per row its
+    (stream, block index, file offset), per stream the slice of the inflated bytes that is its own); a block that two
+    neighbouring streams share has one row."""
+    rows, owner, spans, out_at = [], [], SpanList(), 0
     slices = []
     for k, s in enumerate(group):
         if not s.blocks:
             slices.append((0, 0))
             continue
+        refuse_large_blocks(s.blocks, lambda index, block: _block_where(s.path, index, block[0]))
         first_row = None
         for index, block in enumerate(s.blocks):
-            if block[4] > BGZF_MAX_ISIZE:
-                raise ValueError(f"{_block_where(s.path, index, block[0])}: length mismatch (ISIZE says {block[4]}, a BGZF block "
-                                 f"holds at most {BGZF_MAX_ISIZE} bytes; inflate=\"host\" reads a file that breaks this rule)")
             if index == 0 and owner and owner[-1][0].raw is s.raw and owner[-1][2] == block[0]:
                 first_row = len(rows) - 1  # (the block the stream before ends in)
                 continue
             lo, hi = block[1], block[2]
-            if spans and spans[-1][0] is s.raw and spans[-1][1] + spans[-1][2] <= lo and lo - (spans[-1][1] + spans[-1][2]) <= 64:
-                gap = lo - (spans[-1][1] + spans[-1][2])  # (neighbours: the trailer and the next header ride along)
-                spans[-1][2] += gap + hi - lo
-                comp_at += gap
-            else:
-                spans.append([s.raw, lo, hi - lo])
+            comp_at = spans.add(s.raw, lo, hi, max_gap=64)  # (neighbours: the trailer and the next header ride along)
             if first_row is None:
                 first_row = len(rows)
             rows.append((comp_at, comp_at + hi - lo, block[4], block[3], out_at))
             owner.append((s, index, block[0]))
-            comp_at += hi - lo
             out_at += block[4]
         last_row = len(rows) - 1
         slices.append((rows[first_row][4] + s.skip, rows[last_row][4] + s.keep))
-    table = np.asarray(rows, dtype=np.int64).reshape(-1, BGZF_TABLE_COLUMNS)
-    head = table.size * 8
-    staged = _host_buffer(head + comp_at)  # (pinned: the table and the compressed bytes go up in one asynchronous copy)
-    staged[:head] = table.reshape(-1).view(np.uint8)
-    at = head
-    for raw, offset, size in spans:
-        staged[at: at + size] = np.frombuffer(raw[offset: offset + size], dtype=np.uint8)
-        at += size
+    return np.asarray(rows, dtype=np.int64).reshape(-1, BGZF_TABLE_COLUMNS), spans, owner, slices
+
+
+def _group_bytes_device(group, dev):
+    """The useful bytes of the group's streams, one behind the other, from the one table of `_group_layout`, one pinned
+    staging buffer, one upload and one `rocco_hip_bgzf_inflate`."""
+    import torch
+
+    table, spans, owner, slices = _group_layout(group)
     with torch.cuda.device(dev):
-        up = torch.from_numpy(staged).to(dev, non_blocking=True)
-        out = torch.empty(out_at, dtype=torch.uint8, device=dev)
-        _, report = inflate_blocks_device(up[head:], up[:head].view(torch.int64), out)  # (synchronises: `staged` may go)
+        table_t, comp_t = upload_blocks(table, spans.spans, spans.n_comp, dev)
+        out = torch.empty(int(table[:, 2].sum()), dtype=torch.uint8, device=dev)
+        _, report = inflate_blocks_device(comp_t, table_t, out)  # (synchronises: the upload's pinned buffer may go)
         if report["block"] >= 0:
             s, index, offset = owner[report["block"]]
             raise _bgzf_error(f"{_block_where(s.path, index, offset)} (blocks counted from the span of contig {s.contig})",
@@ -869,12 +768,9 @@ def _group_bytes_host(group, dev, threads: Optional[int]):
         if hi > lo:
             out[to: to + hi - lo] = np.frombuffer(data, dtype=np.uint8)[lo:hi]
 
-    with ThreadPoolExecutor(max_workers=_default_threads() if threads is None else max(1, int(threads))) as pool:
-        for _ in pool.map(one, jobs):
-            pass
+    on_pool(one, jobs, threads)
     with torch.cuda.device(dev):
-        up = torch.from_numpy(out).to(dev, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()  # (the pinned `out` may go)
+        (up,) = _uploaded([out], dev)  # (waits for the copy: the pinned `out` may go)
     return up
 
 

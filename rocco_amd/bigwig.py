@@ -12,18 +12,18 @@ Not built: the decode of the sections into (start, end, value) intervals on the 
 from __future__ import annotations
 
 import collections
-import ctypes
 import os
 import struct
 import zlib
-from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _native
 from . import dp as _dp
-from .bam import BGZF_ERR_LENGTH, BGZF_ERR_STREAM, BGZF_MAX_ISIZE, _STREAM_REASON_TEXT, _default_threads, _host_buffer
+from .inflate import (  # noqa: F401  (what the BAM reader shares; the zlib names stay importable from here)
+    BGZF_ERR_LENGTH, BGZF_ERR_STREAM, BGZF_MAX_ISIZE, ZLIB_ERR_ADLER, ZLIB_ERR_HEADER, ZLIB_ERR_TRUNCATED, ZLIB_HEADER_REASONS, ZLIB_MAX_GRID,
+    ZLIB_TABLE_COLUMNS, _ADLER_TEXT, _HEADER_REASON_TEXT, _STREAM_REASON_TEXT, _TRUNCATED_TEXT, SpanList, _host_buffer, on_pool, upload_blocks,
+    zlib_inflate_blocks_device, zlib_inflate_blocks_host, zlib_shape)
 
 DEFAULT_INFLATE = "device"  # where the data blocks are inflated: "device" or "host"
 
@@ -32,12 +32,6 @@ _HEADER, _ZOOM_HEADER, _CHROM_TREE_HEADER, _RTREE_HEADER, _NODE_HEADER = 64, 24,
 _RTREE_LEAF = np.dtype([("start_chrom", "<u4"), ("start_base", "<u4"), ("end_chrom", "<u4"), ("end_base", "<u4"), ("offset", "<u8"), ("size", "<u8")])
 _RTREE_CHILD = np.dtype([("start_chrom", "<u4"), ("start_base", "<u4"), ("end_chrom", "<u4"), ("end_base", "<u4"), ("offset", "<u8")])
 MAX_TREE_DEPTH = 64
-
-# ROCCO_ZLIB_* of include/rocco_hip.h
-ZLIB_TABLE_COLUMNS, ZLIB_HEADER_REASONS, ZLIB_MAX_GRID = 5, 4, 1 << 16
-ZLIB_ERR_HEADER, ZLIB_ERR_ADLER, ZLIB_ERR_TRUNCATED = 5, 6, 7
-_HEADER_REASON_TEXT = {1: "incorrect header check", 2: "unknown compression method", 3: "invalid window size", 4: "a preset dictionary is asked for"}
-_TRUNCATED_TEXT, _ADLER_TEXT = "incomplete or truncated stream", "incorrect data check"
 
 
 # --------------------------------------------------------------------------------------------
@@ -210,57 +204,8 @@ def chrom_blocks(file: BigWigFile, chromosome: str, raw=None) -> List[Tuple[int,
 # the block table, the two inflates
 # --------------------------------------------------------------------------------------------
 
-def zlib_shape() -> dict:
-    """`rocco_hip_zlib_shape`: the lanes per block, the columns of the block table, the largest capacity, the header reasons, the grid cap."""
-    shape = (ctypes.c_int * 5)()
-    _native.load().rocco_hip_zlib_shape(shape)
-    return dict(zip(("threads", "table_columns", "max_capacity", "header_reasons", "max_grid"), (int(v) for v in shape)))
-
-
 def slot_stride(capacity: int) -> int:
     return (int(capacity) + 7) // 8 * 8
-
-
-def _report(back) -> dict:
-    return {"block": int(back[0]), "status": int(back[1]), "produced": int(back[2])}
-
-
-def zlib_inflate_blocks_host(comp, table: np.ndarray, out: np.ndarray):
-    """`rocco_hip_zlib_inflate_host` (test support: the kernels' rules compiled for the host, on the calling thread); returns
-    (int32 status per block, int64 produced per block, the report ``block`` / ``status`` / ``produced``)."""
-    comp = np.ascontiguousarray(np.frombuffer(comp, dtype=np.uint8) if not isinstance(comp, np.ndarray) else comp)
-    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, ZLIB_TABLE_COLUMNS)
-    if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
-        raise TypeError("zlib_inflate_blocks_host: out must be a writable contiguous uint8 array")
-    status, produced = np.zeros(table.shape[0], dtype=np.int32), np.zeros(table.shape[0], dtype=np.int64)
-    back = (ctypes.c_longlong * 4)()
-    _native.check(_native.load().rocco_hip_zlib_inflate_host(
-        None, comp.ctypes.data if comp.size else None, comp.size, table.ctypes.data if table.size else None, table.shape[0],
-        out.ctypes.data if out.size else None, out.size, status.ctypes.data if status.size else None,
-        produced.ctypes.data if produced.size else None, back), "rocco_hip_zlib_inflate_host")
-    return status, produced, _report(back)
-
-
-def zlib_inflate_blocks_device(comp_t, table_t, out_t):
-    """`rocco_hip_zlib_inflate`: inflates the rows of the int64 CUDA tensor ``table_t`` ([n][5]) from the uint8 CUDA tensor
-    ``comp_t`` into the uint8 CUDA tensor ``out_t``; returns (int32 status, int64 produced per block as CUDA tensors, the report)."""
-    import torch
-
-    for t, dtype in ((comp_t, torch.uint8), (table_t, torch.int64), (out_t, torch.uint8)):
-        if not _dp._is_tensor(t) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.device != out_t.device:
-            raise TypeError("zlib_inflate_blocks_device: contiguous CUDA tensors on one device are required (uint8, int64, uint8)")
-    if table_t.numel() % ZLIB_TABLE_COLUMNS:
-        raise ValueError("zlib_inflate_blocks_device: the block table has 5 columns")
-    n_blocks = table_t.numel() // ZLIB_TABLE_COLUMNS
-    status = torch.empty(n_blocks, dtype=torch.int32, device=out_t.device)
-    produced = torch.empty(n_blocks, dtype=torch.int64, device=out_t.device)
-    back = (ctypes.c_longlong * 4)()
-    with torch.cuda.device(out_t.device):
-        _native.check(_native.load().rocco_hip_zlib_inflate(
-            _native.solver_for(out_t.device.index).handle, comp_t.data_ptr() or None, comp_t.numel(), table_t.data_ptr() or None, n_blocks,
-            out_t.data_ptr() or None, out_t.numel(), status.data_ptr() if n_blocks else None, produced.data_ptr() if n_blocks else None,
-            back, _dp._stream_ptr(out_t)), "rocco_hip_zlib_inflate")
-    return status, produced, _report(back)
 
 
 def _status_words(status: int, produced: int, capacity: int) -> str:
@@ -319,17 +264,14 @@ def _block_where(name: str, index: int, at: int) -> str:
     return f"{name}: bigWig data block {index} at file offset {at}"
 
 
-def inflate_chrom_blocks(wanted: Sequence[Tuple[BigWigFile, str]], dev, inflate: str):
-    """The inflated data blocks of one chromosome of each of K files: ONE block table, one upload, one inflate.  Returns
-    (slots uint8 CUDA tensor, the block table int64 CUDA tensor [n][5], produced int64 CUDA tensor [n], the K + 1 block
-    offsets of the files): block i's bytes are ``slots[table[i, 3]: table[i, 3] + produced[i]]``."""
-    import torch
-
-    blocks, file_first = [], [0]
-    spans, comp_at = [], 0  # the compressed buffer: (file index, file offset, bytes) of every coalesced span, one behind the other
-    rows = []
+def _chrom_layout(wanted: Sequence[Tuple[BigWigFile, str]], inflate: str):
+    """ONE block table and one compressed buffer for the data blocks of one chromosome of each of K files: (the table int64
+    [n][5], the span list, per block its (file index, index among the chromosome's blocks, file offset), the K + 1 block
+    offsets of the files, the bytes of the slots)."""
+    blocks, file_first, spans, rows = [], [0], SpanList(), []
     for k, (file, chromosome) in enumerate(wanted):
-        leaves = chrom_blocks(file, chromosome)
+        raw = _raw(file.name)  # (mapped: the span list tells the files apart by it)
+        leaves = chrom_blocks(file, chromosome, raw)
         buf = int(file.header["uncompressBufSize"])
         framing = 0 if buf > 0 else 1
         capacity = buf if buf > 0 else max((size for _, size in leaves), default=0)
@@ -337,32 +279,27 @@ def inflate_chrom_blocks(wanted: Sequence[Tuple[BigWigFile, str]], dev, inflate:
             raise _bad(file.name, "the header", 0, f"uncompressBufSize {capacity} exceeds {BGZF_MAX_ISIZE}: the device inflate holds no larger "
                        "block and no CPU fallback exists for such blocks in device mode (inflate=\"host\" reads this file)")
         for index, (offset, size) in enumerate(leaves):
-            if spans and spans[-1][0] == k and spans[-1][1] + spans[-1][2] == offset:
-                spans[-1][2] += size  # (the blocks of a chromosome lie one behind the other in files written by the usual tools)
-            else:
-                spans.append([k, offset, size])
+            # (the blocks of a chromosome lie one behind the other in files written by the usual tools: they ride in one span)
+            comp_at = spans.add(raw, offset, offset + size)
             rows.append((comp_at, comp_at + size, capacity, framing))
             blocks.append((k, index, offset))
-            comp_at += size
         file_first.append(len(rows))
-    n_blocks = len(rows)
-    table = np.zeros((n_blocks, ZLIB_TABLE_COLUMNS), dtype=np.int64)
-    if n_blocks:
+    table = np.zeros((len(rows), ZLIB_TABLE_COLUMNS), dtype=np.int64)
+    if rows:
         table[:, [0, 1, 2, 4]] = np.asarray(rows, dtype=np.int64)
         strides = (table[:, 2] + 7) // 8 * 8
         table[1:, 3] = np.cumsum(strides[:-1])
-    n_out = int(table[-1, 3] + (table[-1, 2] + 7) // 8 * 8) if n_blocks else 0
-    head = table.size * 8
-    staged = _host_buffer(head + comp_at)  # (pinned: the table and the compressed bytes go up in one asynchronous copy)
-    staged[:head] = table.reshape(-1).view(np.uint8)
-    at, raws = head, {}
-    for k, offset, size in spans:
-        raw = raws.get(k)
-        if raw is None:
-            raw = raws[k] = _raw(wanted[k][0].name)
-        staged[at: at + size] = raw[offset: offset + size]
-        at += size
-    raws.clear()
+    n_out = int(table[-1, 3] + (table[-1, 2] + 7) // 8 * 8) if rows else 0
+    return table, spans, blocks, np.asarray(file_first, dtype=np.int64), n_out
+
+
+def inflate_chrom_blocks(wanted: Sequence[Tuple[BigWigFile, str]], dev, inflate: str):
+    """The inflated data blocks of one chromosome of each of K files: the one table of `_chrom_layout`, one upload, one
+    inflate.  Returns (slots uint8 CUDA tensor, the block table int64 CUDA tensor [n][5], produced int64 CUDA tensor [n],
+    the K + 1 block offsets of the files): block i's bytes are ``slots[table[i, 3]: table[i, 3] + produced[i]]``."""
+    import torch
+
+    table, spans, blocks, file_first, n_out = _chrom_layout(wanted, inflate)
 
     def refuse(block: int, words: str) -> ValueError:
         k, index, offset = blocks[block]
@@ -370,33 +307,32 @@ def inflate_chrom_blocks(wanted: Sequence[Tuple[BigWigFile, str]], dev, inflate:
 
     with torch.cuda.device(dev):
         if inflate == "device":
-            up = torch.from_numpy(staged).to(dev, non_blocking=True)
-            table_t, comp_t = up[:head].view(torch.int64), up[head:]
+            table_t, comp_t = upload_blocks(table, spans.spans, spans.n_comp, dev)
             slots_t = torch.empty(n_out, dtype=torch.uint8, device=dev)
-            _, produced_t, report = zlib_inflate_blocks_device(comp_t, table_t, slots_t)  # (synchronises: `staged` may go)
+            _, produced_t, report = zlib_inflate_blocks_device(comp_t, table_t, slots_t)  # (synchronises: the upload's pinned buffer may go)
             if report["block"] >= 0:
                 raise refuse(report["block"], _status_words(report["status"], report["produced"], int(table[report["block"], 2])))
         else:
             slots = _host_buffer(n_out)
-            produced = np.zeros(n_blocks, dtype=np.int64)
-            comp = staged[head:]
+            raws = [_raw(file.name) for file, _ in wanted]
 
             def one(i):
                 lo, hi, capacity, slot, framing = (int(v) for v in table[i])
-                status, data = host_block_status(comp[lo:hi].tobytes(), capacity, framing)
+                k, _, offset = blocks[i]
+                status, data = host_block_status(raws[k][offset: offset + hi - lo].tobytes(), capacity, framing)
                 if status == 0:
                     slots[slot: slot + len(data)] = np.frombuffer(data, dtype=np.uint8)
-                produced[i] = len(data)
-                return status
+                return status, len(data)
 
-            with ThreadPoolExecutor(max_workers=_default_threads()) as pool:
-                for i, status in enumerate(pool.map(one, range(n_blocks))):
-                    if status != 0:
-                        raise refuse(i, _status_words(status, int(produced[i]), int(table[i, 2])))
+            done = on_pool(one, range(table.shape[0]))
+            produced = np.asarray([n for _, n in done], dtype=np.int64).reshape(-1)
+            for i, (status, n) in enumerate(done):
+                if status != 0:
+                    raise refuse(i, _status_words(status, n, int(table[i, 2])))
             slots_t = torch.from_numpy(slots).to(dev)
             table_t = torch.from_numpy(table.reshape(-1)).to(dev)
             produced_t = torch.from_numpy(produced).to(dev)
-    return slots_t, table_t.view(-1, ZLIB_TABLE_COLUMNS), produced_t, np.asarray(file_first, dtype=np.int64)
+    return slots_t, table_t.view(-1, ZLIB_TABLE_COLUMNS), produced_t, file_first
 
 
 # --------------------------------------------------------------------------------------------

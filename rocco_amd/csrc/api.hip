@@ -6,6 +6,7 @@
 #include <atomic>
 
 #include "budget.h"
+#include "inflate_core.h"
 
 #include <algorithm>
 #include <cmath>
@@ -101,6 +102,39 @@ static int enter_record_call(rocco_hip_solver *solver, size_t bytes)
     ROCCO_HIP_TRY(hipSetDevice(solver->device));
     (void)hipGetLastError();
     return solver->dev_misc.reserve(bytes);
+}
+
+// what the four inflate entry points ask of their arguments, device or host memory alike
+static bool inflate_args_ok(const void *comp, size_t n_comp, const void *table, size_t n_blocks, const void *out, size_t n_out, const void *report)
+{
+    return report != nullptr && n_blocks < (size_t)0x7fffffff && n_comp < ((size_t)1 << 62) && n_out < ((size_t)1 << 62) &&
+           (n_blocks == 0 || table != nullptr) && (n_comp == 0 || comp != nullptr) && (n_out == 0 || out != nullptr);
+}
+
+template <class F>
+static int inflate_on_device(rocco_hip_solver *solver, const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks,
+                             uint8_t *out_dev, size_t n_out, int32_t *status_out_dev, int64_t *produced_out_dev, int64_t *report_out_host,
+                             void *stream)
+{
+    if (solver == nullptr || !inflate_args_ok(comp_dev, n_comp, table_dev, n_blocks, out_dev, n_out, report_out_host)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, inflate_scratch_bytes<F>(n_blocks)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_inflate<F>(comp_dev, n_comp, table_dev, n_blocks, out_dev, n_out, status_out_dev, produced_out_dev, report_out_host,
+                             solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+template <class F>
+static int inflate_on_host(const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks, uint8_t *out, size_t n_out,
+                           int32_t *status_out, int64_t *produced_out, int64_t *report_out)
+{
+    if (!inflate_args_ok(comp, n_comp, table, n_blocks, out, n_out, report_out)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    inflate_host<F>(comp, (long long)n_comp, table, (long long)n_blocks, out, (long long)n_out, status_out, produced_out, report_out);
+    return ROCCO_HIP_OK;
 }
 
 extern "C" {
@@ -1765,28 +1799,14 @@ void rocco_hip_bam_shape(int *shape_out)
 int rocco_hip_bgzf_inflate(rocco_hip_solver *solver, const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks,
                            uint8_t *out_dev, size_t n_out, int32_t *status_out_dev, int64_t *report_out_host, void *stream)
 {
-    if (solver == nullptr || report_out_host == nullptr || n_blocks >= (size_t)0x7fffffff || n_comp >= ((size_t)1 << 62) ||
-        n_out >= ((size_t)1 << 62) || (n_blocks > 0 && table_dev == nullptr) || (n_comp > 0 && comp_dev == nullptr) ||
-        (n_out > 0 && out_dev == nullptr)) {
-        return ROCCO_HIP_EINVAL;
-    }
-    if (const int rc = enter_record_call(solver, bgzf_inflate_scratch_bytes(n_blocks)); rc != ROCCO_HIP_OK) {
-        return rc;
-    }
-    return launch_bgzf_inflate(comp_dev, n_comp, table_dev, n_blocks, out_dev, n_out, status_out_dev, report_out_host,
-                               solver->dev_misc.ptr, (hipStream_t)stream);
+    return inflate_on_device<BgzfFraming>(solver, comp_dev, n_comp, table_dev, n_blocks, out_dev, n_out, status_out_dev, nullptr,
+                                          report_out_host, stream);
 }
 
-int rocco_hip_bgzf_inflate_host(rocco_hip_solver *solver, const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks,
-                                uint8_t *out, size_t n_out, int32_t *status_out, int64_t *report_out)
+int rocco_hip_bgzf_inflate_host(rocco_hip_solver *, const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks, uint8_t *out,
+                                size_t n_out, int32_t *status_out, int64_t *report_out)
 {
-    (void)solver;
-    if (report_out == nullptr || n_blocks >= (size_t)0x7fffffff || n_comp >= ((size_t)1 << 62) || n_out >= ((size_t)1 << 62) ||
-        (n_blocks > 0 && table == nullptr) || (n_comp > 0 && comp == nullptr) || (n_out > 0 && out == nullptr)) {
-        return ROCCO_HIP_EINVAL;
-    }
-    bgzf_inflate_host_blocks(comp, n_comp, table, n_blocks, out, n_out, status_out, report_out);
-    return ROCCO_HIP_OK;
+    return inflate_on_host<BgzfFraming>(comp, n_comp, table, n_blocks, out, n_out, status_out, nullptr, report_out);
 }
 
 void rocco_hip_bgzf_shape(int *shape_out)
@@ -1801,28 +1821,14 @@ int rocco_hip_zlib_inflate(rocco_hip_solver *solver, const uint8_t *comp_dev, si
                            uint8_t *out_dev, size_t n_out, int32_t *status_out_dev, int64_t *produced_out_dev, int64_t *report_out_host,
                            void *stream)
 {
-    if (solver == nullptr || report_out_host == nullptr || n_blocks >= (size_t)0x7fffffff || n_comp >= ((size_t)1 << 62) ||
-        n_out >= ((size_t)1 << 62) || (n_blocks > 0 && table_dev == nullptr) || (n_comp > 0 && comp_dev == nullptr) ||
-        (n_out > 0 && out_dev == nullptr)) {
-        return ROCCO_HIP_EINVAL;
-    }
-    if (const int rc = enter_record_call(solver, zlib_inflate_scratch_bytes(n_blocks)); rc != ROCCO_HIP_OK) {
-        return rc;
-    }
-    return launch_zlib_inflate(comp_dev, n_comp, table_dev, n_blocks, out_dev, n_out, status_out_dev, produced_out_dev, report_out_host,
-                               solver->dev_misc.ptr, (hipStream_t)stream);
+    return inflate_on_device<ZlibFraming>(solver, comp_dev, n_comp, table_dev, n_blocks, out_dev, n_out, status_out_dev, produced_out_dev,
+                                          report_out_host, stream);
 }
 
-int rocco_hip_zlib_inflate_host(rocco_hip_solver *solver, const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks,
-                                uint8_t *out, size_t n_out, int32_t *status_out, int64_t *produced_out, int64_t *report_out)
+int rocco_hip_zlib_inflate_host(rocco_hip_solver *, const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks, uint8_t *out,
+                                size_t n_out, int32_t *status_out, int64_t *produced_out, int64_t *report_out)
 {
-    (void)solver;
-    if (report_out == nullptr || n_blocks >= (size_t)0x7fffffff || n_comp >= ((size_t)1 << 62) || n_out >= ((size_t)1 << 62) ||
-        (n_blocks > 0 && table == nullptr) || (n_comp > 0 && comp == nullptr) || (n_out > 0 && out == nullptr)) {
-        return ROCCO_HIP_EINVAL;
-    }
-    zlib_inflate_host_blocks(comp, n_comp, table, n_blocks, out, n_out, status_out, produced_out, report_out);
-    return ROCCO_HIP_OK;
+    return inflate_on_host<ZlibFraming>(comp, n_comp, table, n_blocks, out, n_out, status_out, produced_out, report_out);
 }
 
 void rocco_hip_zlib_shape(int *shape_out)

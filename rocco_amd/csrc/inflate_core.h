@@ -1,6 +1,6 @@
-// rocco_amd/csrc/inflate_core.h -- RFC 1951 inflate and CRC32 of one BGZF block: ONE statement of the decode rules, compiled
-// for the device (csrc/bgzf_inflate.hip: one wavefront per block) and for the host (bgzf_inflate_host below: one thread, test
-// support in the sense synth.hip is).  DESIGN.md section 0 row f8, note (29).
+// rocco_amd/csrc/inflate_core.h -- RFC 1951 inflate of one block and its check value under BGZF or zlib framing: ONE statement
+// of the decode rules, compiled for the device (csrc/bgzf_inflate.hip: one wavefront per block) and for the host (inflate_host
+// below: one thread, test support in the sense synth.hip is).  DESIGN.md section 0 rows f8 and f10, notes (29) and (31).
 //
 // The code is written for L lanes that all carry the same decoder state (bit buffer, output position, current tables) and
 // branch alike; what differs between lanes is only which element of a cooperative loop a lane takes: the symbols of a code
@@ -463,12 +463,41 @@ ROCCO_INFLATE_HD void crc_chunk(long long n, int c, long long *first, long long 
     *length = hi - lo;
 }
 
-// a row of the block table (rocco_hip.h) against the two buffers
-ROCCO_INFLATE_HD bool bgzf_row_fits(const int64_t *row, long long n_comp, long long n_out)
-{
-    return row[0] >= 0 && row[0] <= row[1] && row[1] <= n_comp && row[2] >= 0 && row[2] <= ROCCO_BGZF_MAX_ISIZE && row[4] >= 0 &&
-           row[4] <= n_out && row[2] <= n_out - row[4];
-}
+// ---- a framing: what stands around the deflate data of a row, as a compile-time policy of the kernels (bgzf_inflate.hip) and
+// of their host twin (inflate_host below).  F states the table (kColumns, kOffsetColumn: where the row's bytes go in the output
+// buffer), the grid cap, fits(row, n_comp, n_out) (the row against the two buffers) and block(x, tables, row, out, &produced,
+// &end) (everything of the row but its check value); and for the check: has_check(row), check_bytes(row, produced) (the bytes
+// it covers), check_chunk / check_combine / kCheckStart (a chunk's value, the value of A || B, the value of no bytes),
+// stated(row, comp, end) (the value the file states), kCheckError, CheckTables with check_tables_build (what the chunk
+// function looks up, in LDS on the device), and kStatedInStream: the stated value is read from the compressed buffer at the
+// stream's end (the kernels then keep an `ends` array and the check reads comp) instead of from the row.
+
+// BGZF (rocco_hip.h: row = first, last, ISIZE, CRC32, offset): a raw deflate stream that inflates to exactly ISIZE bytes
+struct BgzfFraming {
+    static constexpr int kColumns = ROCCO_BGZF_TABLE_COLUMNS, kOffsetColumn = 4, kCheckError = ROCCO_BGZF_ERR_CRC;
+    static constexpr long long kMaxGrid = ROCCO_BGZF_MAX_GRID;
+    static constexpr bool kStatedInStream = false;
+    static constexpr uint32_t kCheckStart = 0;
+    using CheckTables = CrcTables;
+
+    static ROCCO_INFLATE_HD bool fits(const int64_t *row, long long n_comp, long long n_out)
+    {
+        return row[0] >= 0 && row[0] <= row[1] && row[1] <= n_comp && row[2] >= 0 && row[2] <= ROCCO_BGZF_MAX_ISIZE && row[4] >= 0 &&
+               row[4] <= n_out && row[2] <= n_out - row[4];
+    }
+    template <class X>
+    static ROCCO_INFLATE_HD int block(X &x, InflateTables &t, const int64_t *row, uint8_t *out, long long *produced_out, long long *)
+    {
+        return inflate_block(x, t, row[0], row[1], out, row[2], produced_out);
+    }
+    static ROCCO_INFLATE_HD bool has_check(const int64_t *) { return true; }
+    static ROCCO_INFLATE_HD long long check_bytes(const int64_t *row, long long) { return row[2]; }
+    template <class X>
+    static ROCCO_INFLATE_HD void check_tables_build(X &x, CrcTables &t) { crc_tables_build(x, t); }
+    static ROCCO_INFLATE_HD uint32_t check_chunk(const CrcTables &t, const uint8_t *p, long long n) { return crc_of_bytes(t, p, n); }
+    static ROCCO_INFLATE_HD uint32_t check_combine(const CrcTables &t, uint32_t a, uint32_t b, long long len_b) { return crc_combine(t, a, b, len_b); }
+    static ROCCO_INFLATE_HD uint32_t stated(const int64_t *row, const uint8_t *, long long) { return (uint32_t)row[3]; }
+};
 
 // ---- the host entry (test support): one thread, the same functions ---------------------------------------------------------
 struct HostInflateExec {
@@ -481,37 +510,41 @@ struct HostInflateExec {
     uint8_t in_raw(long long i) const { return comp[i]; }
 };
 
-// What the two kernels of bgzf_inflate.hip compute, block after block: status_out[i] (may be null), the bytes of every block
-// at its offset, and report_out[ROCCO_BGZF_REPORT] = the first failing block (-1), its status, the bytes it inflates to.
-inline void bgzf_inflate_host(const uint8_t *comp, long long n_comp, const int64_t *table, long long n_blocks, uint8_t *out, long long n_out,
-                              int32_t *status_out, int64_t *report_out)
+// What the two kernels of bgzf_inflate.hip compute under framing F, block after block: status_out[i] and produced_out[i]
+// (either may be null), the bytes of every block at its offset, and report_out[ROCCO_BGZF_REPORT] = the first failing block
+// (-1), its status, the bytes it inflates to, 0.
+template <class F>
+inline void inflate_host(const uint8_t *comp, long long n_comp, const int64_t *table, long long n_blocks, uint8_t *out, long long n_out,
+                         int32_t *status_out, int64_t *produced_out, int64_t *report_out)
 {
     HostInflateExec x = {comp};
     InflateTables tables;
-    CrcTables crc_tables;
-    crc_tables_build(x, crc_tables);
+    typename F::CheckTables check_tables;
+    F::check_tables_build(x, check_tables);
     report_out[0] = -1;
-    report_out[1] = 0;
-    report_out[2] = 0;
+    report_out[1] = report_out[2] = report_out[3] = 0;
     for (long long i = 0; i < n_blocks; ++i) {
-        const int64_t *row = table + i * ROCCO_BGZF_TABLE_COLUMNS;
+        const int64_t *row = table + i * F::kColumns;
         int status = ROCCO_BGZF_ERR_TABLE;
-        long long produced = 0;
-        if (bgzf_row_fits(row, n_comp, n_out)) {
-            uint8_t *mine = out + row[4];
-            status = inflate_block(x, tables, row[0], row[1], mine, row[2], &produced);
-            if (status == 0) {
-                uint32_t crc = 0;
+        long long produced = 0, end = 0;
+        if (F::fits(row, n_comp, n_out)) {
+            uint8_t *mine = out + row[F::kOffsetColumn];
+            status = F::block(x, tables, row, mine, &produced, &end);
+            if (status == 0 && F::has_check(row)) {
+                uint32_t check = F::kCheckStart;
                 for (int c = 0; c < kCrcChunks; ++c) {
                     long long first, length;
-                    crc_chunk(row[2], c, &first, &length);
-                    crc = crc_combine(crc_tables, crc, crc_of_bytes(crc_tables, mine + first, length), length);
+                    crc_chunk(F::check_bytes(row, produced), c, &first, &length);
+                    check = F::check_combine(check_tables, check, F::check_chunk(check_tables, mine + first, length), length);
                 }
-                status = crc == (uint32_t)row[3] ? 0 : ROCCO_BGZF_ERR_CRC;
+                status = check == F::stated(row, comp, end) ? 0 : F::kCheckError;
             }
         }
         if (status_out != nullptr) {
             status_out[i] = status;
+        }
+        if (produced_out != nullptr) {
+            produced_out[i] = produced;
         }
         if (status != 0 && report_out[0] < 0) {
             report_out[0] = i;
@@ -585,13 +618,6 @@ ROCCO_INFLATE_HD uint32_t adler_combine(uint32_t adler_a, uint32_t adler_b, long
     return sum1 | (sum2 << 16);
 }
 
-// a row of the zlib block table (rocco_hip.h) against the two buffers
-ROCCO_INFLATE_HD bool zlib_row_fits(const int64_t *row, long long n_comp, long long n_out)
-{
-    return row[0] >= 0 && row[0] <= row[1] && row[1] <= n_comp && row[2] >= 0 && row[2] <= ROCCO_BGZF_MAX_ISIZE && row[3] >= 0 &&
-           row[3] <= n_out && row[2] <= n_out - row[3] && (row[4] == 0 || row[4] == 1);
-}
-
 // Everything of a row but its Adler-32: the header, the stream, the room for the check value, the length; a stored row is
 // copied.  Returns the status so far (0: the Adler-32 of out[0, *produced_out) is still to be compared with the four bytes
 // at *end_out; a stored row has none and *end_out is its span's end).  Cooperative, as inflate_block is.
@@ -630,44 +656,32 @@ ROCCO_INFLATE_HD uint32_t zlib_stated_adler(const uint8_t *comp, long long at)
     return ((uint32_t)comp[at] << 24) | ((uint32_t)comp[at + 1] << 16) | ((uint32_t)comp[at + 2] << 8) | (uint32_t)comp[at + 3];
 }
 
-// What the two kernels of rocco_hip_zlib_inflate compute, block after block (the host twin: test support).
-inline void zlib_inflate_host(const uint8_t *comp, long long n_comp, const int64_t *table, long long n_blocks, uint8_t *out, long long n_out,
-                              int32_t *status_out, int64_t *produced_out, int64_t *report_out)
-{
-    HostInflateExec x = {comp};
-    InflateTables tables;
-    report_out[0] = -1;
-    report_out[1] = 0;
-    report_out[2] = 0;
-    for (long long i = 0; i < n_blocks; ++i) {
-        const int64_t *row = table + i * ROCCO_ZLIB_TABLE_COLUMNS;
-        int status = ROCCO_BGZF_ERR_TABLE;
-        long long produced = 0, end = 0;
-        if (zlib_row_fits(row, n_comp, n_out)) {
-            uint8_t *mine = out + row[3];
-            status = zlib_block(x, tables, row, mine, &produced, &end);
-            if (status == 0 && row[4] == 0) {
-                uint32_t adler = 1;
-                for (int c = 0; c < kCrcChunks; ++c) {
-                    long long first, length;
-                    crc_chunk(produced, c, &first, &length);
-                    adler = adler_combine(adler, adler_of_bytes(mine + first, length), length);
-                }
-                status = adler == zlib_stated_adler(comp, end) ? 0 : ROCCO_ZLIB_ERR_ADLER;
-            }
-        }
-        if (status_out != nullptr) {
-            status_out[i] = status;
-        }
-        if (produced_out != nullptr) {
-            produced_out[i] = produced;
-        }
-        if (status != 0 && report_out[0] < 0) {
-            report_out[0] = i;
-            report_out[1] = status;
-            report_out[2] = produced;
-        }
+// zlib (rocco_hip.h: row = first, last, capacity, offset, framing): the Adler-32 covers the bytes produced (at most the
+// capacity) and stands behind the stream; a stored row (framing 1) has none
+struct ZlibFraming {
+    static constexpr int kColumns = ROCCO_ZLIB_TABLE_COLUMNS, kOffsetColumn = 3, kCheckError = ROCCO_ZLIB_ERR_ADLER;
+    static constexpr long long kMaxGrid = ROCCO_ZLIB_MAX_GRID;
+    static constexpr bool kStatedInStream = true;
+    static constexpr uint32_t kCheckStart = 1;
+    struct CheckTables {};  // (the Adler-32 looks nothing up)
+
+    static ROCCO_INFLATE_HD bool fits(const int64_t *row, long long n_comp, long long n_out)
+    {
+        return row[0] >= 0 && row[0] <= row[1] && row[1] <= n_comp && row[2] >= 0 && row[2] <= ROCCO_BGZF_MAX_ISIZE && row[3] >= 0 &&
+               row[3] <= n_out && row[2] <= n_out - row[3] && (row[4] == 0 || row[4] == 1);
     }
-}
+    template <class X>
+    static ROCCO_INFLATE_HD int block(X &x, InflateTables &t, const int64_t *row, uint8_t *out, long long *produced_out, long long *end_out)
+    {
+        return zlib_block(x, t, row, out, produced_out, end_out);
+    }
+    static ROCCO_INFLATE_HD bool has_check(const int64_t *row) { return row[4] == 0; }
+    static ROCCO_INFLATE_HD long long check_bytes(const int64_t *, long long produced) { return produced; }
+    template <class X>
+    static ROCCO_INFLATE_HD void check_tables_build(X &, CheckTables &) {}
+    static ROCCO_INFLATE_HD uint32_t check_chunk(const CheckTables &, const uint8_t *p, long long n) { return adler_of_bytes(p, n); }
+    static ROCCO_INFLATE_HD uint32_t check_combine(const CheckTables &, uint32_t a, uint32_t b, long long len_b) { return adler_combine(a, b, len_b); }
+    static ROCCO_INFLATE_HD uint32_t stated(const int64_t *, const uint8_t *comp, long long end) { return zlib_stated_adler(comp, end); }
+};
 
 }  // namespace rocco

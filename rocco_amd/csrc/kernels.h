@@ -402,18 +402,16 @@ int launch_bam_stream_firsts(const int64_t *offsets_dev, const int32_t *tid_dev,
                              hipStream_t stream);
 
 // ---- bgzf_inflate.hip -------------------------------------------------------------------------
-size_t bgzf_inflate_scratch_bytes(size_t n_blocks);
-int launch_bgzf_inflate(const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks, uint8_t *out_dev, size_t n_out,
-                        int32_t *status_out_dev, int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
-// test support: the same blocks over host memory on the calling thread (inflate_core.h compiled for the host)
-void bgzf_inflate_host_blocks(const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks, uint8_t *out, size_t n_out,
-                              int32_t *status_out, int64_t *report_out);
-// the zlib-framed blocks of a bigWig file (row f10): the same decoder, a header in front, an Adler-32 behind
-size_t zlib_inflate_scratch_bytes(size_t n_blocks);
-int launch_zlib_inflate(const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks, uint8_t *out_dev, size_t n_out,
-                        int32_t *status_out_dev, int64_t *produced_out_dev, int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
-void zlib_inflate_host_blocks(const uint8_t *comp, size_t n_comp, const int64_t *table, size_t n_blocks, uint8_t *out, size_t n_out,
-                              int32_t *status_out, int64_t *produced_out, int64_t *report_out);
+// F: BgzfFraming (the blocks of a BAM file, row f8) or ZlibFraming (the data blocks of a bigWig file, row f10) of
+// inflate_core.h; bgzf_inflate.hip instantiates both.  status_out_dev and produced_out_dev may be null.  The host twin (test
+// support) is inflate_host<F> of inflate_core.h.
+struct BgzfFraming;
+struct ZlibFraming;
+template <class F>
+size_t inflate_scratch_bytes(size_t n_blocks);
+template <class F>
+int launch_inflate(const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks, uint8_t *out_dev, size_t n_out,
+                   int32_t *status_out_dev, int64_t *produced_out_dev, int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
 
 // ---- synth.hip ------------------------------------------------------------------------------
 int launch_synth(void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, uint64_t seed,

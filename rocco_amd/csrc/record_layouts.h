@@ -200,30 +200,19 @@ struct BamStreamFirstsLayout {
     }
 };
 
-// launch_bgzf_inflate: per block its status (int32; unused where the caller brings its own), the bytes it inflates to (int64);
-// the word of the first failing block; the report
-struct BgzfInflateLayout {
-    size_t status, produced, first_error, report, bytes;
-    explicit BgzfInflateLayout(size_t n_blocks)
+// launch_inflate: per block its status (int32) and the bytes it inflates to (int64), each unused where the caller brings its
+// own; with_ends (zlib framing): per block where its stream ended in the compressed buffer (int64); the word of the first
+// failing block; the report
+struct InflateLayout {
+    size_t status, produced, ends = 0, first_error, report, bytes;
+    InflateLayout(size_t n_blocks, bool with_ends)
     {
         Layout lay;
         status = lay.at(n_blocks * sizeof(int));
         produced = lay.at(n_blocks * sizeof(long long));
-        first_error = lay.at(sizeof(unsigned long long));
-        report = lay.at(ROCCO_BGZF_REPORT * sizeof(long long));
-        bytes = lay.bytes();
-    }
-};
-
-// launch_zlib_inflate: as launch_bgzf_inflate, and per block where its stream ended in the compressed buffer (int64)
-struct ZlibInflateLayout {
-    size_t status, produced, ends, first_error, report, bytes;
-    explicit ZlibInflateLayout(size_t n_blocks)
-    {
-        Layout lay;
-        status = lay.at(n_blocks * sizeof(int));
-        produced = lay.at(n_blocks * sizeof(long long));
-        ends = lay.at(n_blocks * sizeof(long long));
+        if (with_ends) {
+            ends = lay.at(n_blocks * sizeof(long long));
+        }
         first_error = lay.at(sizeof(unsigned long long));
         report = lay.at(ROCCO_BGZF_REPORT * sizeof(long long));
         bytes = lay.bytes();

@@ -186,8 +186,10 @@ def test_constants_agree_with_the_c_header():
                        "ROCCO_BGZF_ERR_CRC": bam.BGZF_ERR_CRC, "ROCCO_BGZF_ERR_TABLE": bam.BGZF_ERR_TABLE}
     (shift,) = re.findall(r"#define ROCCO_BGZF_MAX_GRID \(1 << (\d+)\)", text)  # (the grid cap, written as the kernel file wrote it)
     assert bam.BGZF_MAX_GRID == 1 << int(shift) == 1 << 20
-    source = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rocco_amd", "csrc", "bgzf_inflate.hip")).read()
-    assert "kMaxGrid = ROCCO_BGZF_MAX_GRID;" in source and "1 << 20" not in source
+    # (the cap is stated by the BGZF framing of inflate_core.h and used by the one launcher of the kernel file: neither writes the number)
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rocco_amd", "csrc")
+    framing, source = open(os.path.join(csrc, "inflate_core.h")).read(), open(os.path.join(csrc, "bgzf_inflate.hip")).read()
+    assert "kMaxGrid = ROCCO_BGZF_MAX_GRID;" in framing and "F::kMaxGrid" in source and "1 << 20" not in source + framing
     assert (bam.BGZF_ERR_STREAM, bam.BGZF_ERR_LENGTH, bam.BGZF_ERR_CRC, bam.BGZF_ERR_TABLE) == (gx.ERR_STREAM, gx.ERR_LENGTH, gx.ERR_CRC, gx.ERR_TABLE)
     assert bam.bgzf_shape() == {"threads": 64, "table_columns": 5, "max_isize": 65536, "stream_reasons": 12}
     assert sorted(bam._STREAM_REASON_TEXT) == list(range(1, bam.BGZF_STREAM_REASONS + 1))
