@@ -1008,6 +1008,72 @@ int rocco_hip_zlib_inflate_host(rocco_hip_solver *solver, const uint8_t *comp, s
                                 uint8_t *out, size_t n_out, int32_t *status_out, int64_t *produced_out, int64_t *report_out);
 void rocco_hip_zlib_shape(int *shape_out);
 
+/* ---- the inflated data blocks of bigWig files -> their intervals (note (31)) --------------
+ * What libBigWig's bwGetOverlappingIntervals(bw, chrom, 0, length) does with every data block once it is inflated
+ * (bwValues.c), which is what pyBigWig's intervals(chromosome) returns.  The input is what rocco_hip_zlib_inflate left:
+ *   slots[0, n_slots), the block table int64 [n_blocks][ROCCO_ZLIB_TABLE_COLUMNS] (column 2 the slot's capacity, column 3
+ *   its offset in slots), produced int64 [n_blocks] (the bytes of block i are slots[offset, offset + produced[i])), and
+ *   for the n_files files whose blocks lie one behind the other in the table three HOST arrays: file_first int64
+ *   [n_files + 1] (file k's blocks are file_first[k] .. file_first[k + 1]; ascending from 0 to n_blocks), chrom_id and
+ *   chrom_length int64 [n_files] (the chromosome's id and length in file k's chromosome tree).
+ * Per block, in this order (refusals are this project's: libBigWig would read past the section or wrap):
+ *   the row must fit: 0 <= capacity, 0 <= offset, offset + capacity <= n_slots, 0 <= produced <= capacity, else
+ *     ROCCO_BGZF_ERR_TABLE and nothing of the block is read;
+ *   produced < 24: ROCCO_BIGWIG_ERR_SHORT (no room for the header, which libBigWig reads without asking);
+ *   the header `<IIIIIBBH` = chromId, chromStart, chromEnd, itemStep, itemSpan, type, reserved, itemCount; chromId other
+ *     than the file's chrom_id: the block is skipped whole as libBigWig skips it (status 0, no interval, nothing else judged);
+ *   type outside 1 (bedGraph), 2 (variableStep), 3 (fixedStep): ROCCO_BIGWIG_ERR_TYPE (libBigWig's switch has no default);
+ *   produced < 24 + itemCount * (12, 8, 4 by type): ROCCO_BIGWIG_ERR_ITEMS (libBigWig would read past the section); more
+ *     bytes than that are ignored, as libBigWig ignores them;
+ *   item j: (start, end, float32) | (start, float32), end = start + itemSpan | (float32), start = chromStart + j * itemStep,
+ *     end = start + itemSpan, in 64-bit arithmetic; an end beyond 2^32 - 1: ROCCO_BIGWIG_ERR_WRAP (libBigWig's uint32_t
+ *     would wrap around) for the whole block;
+ *   an item is kept unless end <= 0 || start >= chrom_length (bwValues.c's test against the queried range [0, length)).
+ * The kept items of all blocks in block order, within a block in item order, are the output: starts int64, ends int64,
+ * values float64 (the float32 as C's (double) widens it: NaN payloads and zero signs stay) -- the arguments of
+ * rocco_hip_bigwig_dense_fill_f64.
+ *
+ * rocco_hip_bigwig_sections_facts: the first call.  status_out_dev int32 [n_status >= n_blocks]: 0 or why the block is
+ *   refused; block_first_out_dev int64 [n_block_first >= n_blocks + 1]: the index of every block's first kept item (a refused
+ *   block keeps none), the last cell the total; file_offsets_out_host int64 [n_files + 1]: the same for the files;
+ *   report_out_host, ROCCO_BGZF_REPORT int64: [0] the first refused block in table order or -1, [1] its status, [2] the total.
+ *   One wavefront of ROCCO_BIGWIG_THREADS lanes per block under a grid stride of ROCCO_BIGWIG_MAX_GRID workgroups.
+ *   ROCCO_HIP_EINVAL before anything is launched where a pointer is null while its size is not 0, a size is too small or
+ *   file_first does not ascend from 0 to n_blocks.  Waits for the device ONCE, at its end, and returns the error state
+ *   it finds there (ROCCO_HIP_EHIP): a fault of its kernels is this call's error, not a later call's.
+ * rocco_hip_bigwig_sections_emit: the second call, with the same inputs and block_first_dev as the first left it; total is
+ *   report[2].  Writes starts_out_dev[0, total), ends_out_dev[0, total), values_out_dev[0, total); n_starts, n_ends and
+ *   n_values are the arrays' sizes in elements: ROCCO_HIP_EINVAL before anything is launched where one is smaller than
+ *   total, a pointer is null while its size is not 0, or n_block_first < n_blocks + 1.  total = 0 launches nothing.  No
+ *   index at or past the least of the three sizes is written whatever block_first_dev holds.  Waits once, at its end.
+ * rocco_hip_bigwig_sections_host: test support, as rocco_hip_zlib_inflate_host is: both stages over HOST memory on the
+ *   calling thread from the same source (csrc/bigwig_sections.h compiled for the host); solver may be NULL.  starts_out
+ *   NULL (with ends_out, values_out NULL and their sizes 0): the first stage alone.  Else the items are written where no
+ *   block is refused; a total beyond a size is ROCCO_HIP_EINVAL with nothing written.
+ * rocco_hip_bigwig_sections_shape: shape_out[0..2] = ROCCO_BIGWIG_THREADS, ROCCO_BIGWIG_MAX_GRID, the header's 24 bytes. */
+#define ROCCO_BIGWIG_THREADS 64
+#define ROCCO_BIGWIG_MAX_GRID (1 << 16) /* workgroups of sections_facts_kernel and sections_emit_kernel at most; unit: one data block */
+#define ROCCO_BIGWIG_ERR_SHORT 8
+#define ROCCO_BIGWIG_ERR_TYPE 9
+#define ROCCO_BIGWIG_ERR_ITEMS 10
+#define ROCCO_BIGWIG_ERR_WRAP 11
+int rocco_hip_bigwig_sections_facts(rocco_hip_solver *solver, const uint8_t *slots_dev, size_t n_slots, const int64_t *table_dev,
+                                    const int64_t *produced_dev, size_t n_blocks, const int64_t *file_first_host,
+                                    const int64_t *chrom_id_host, const int64_t *chrom_length_host, size_t n_files, int32_t *status_out_dev,
+                                    size_t n_status, int64_t *block_first_out_dev, size_t n_block_first, int64_t *file_offsets_out_host,
+                                    int64_t *report_out_host, void *stream);
+int rocco_hip_bigwig_sections_emit(rocco_hip_solver *solver, const uint8_t *slots_dev, size_t n_slots, const int64_t *table_dev,
+                                   const int64_t *produced_dev, size_t n_blocks, const int64_t *file_first_host,
+                                   const int64_t *chrom_id_host, const int64_t *chrom_length_host, size_t n_files,
+                                   const int64_t *block_first_dev, size_t n_block_first, size_t total, int64_t *starts_out_dev, size_t n_starts,
+                                   int64_t *ends_out_dev, size_t n_ends, double *values_out_dev, size_t n_values, void *stream);
+int rocco_hip_bigwig_sections_host(rocco_hip_solver *solver, const uint8_t *slots, size_t n_slots, const int64_t *table, const int64_t *produced,
+                                   size_t n_blocks, const int64_t *file_first, const int64_t *chrom_id, const int64_t *chrom_length,
+                                   size_t n_files, int32_t *status_out, size_t n_status, int64_t *block_first_out, size_t n_block_first,
+                                   int64_t *file_offsets_out, int64_t *starts_out, size_t n_starts, int64_t *ends_out, size_t n_ends,
+                                   double *values_out, size_t n_values, int64_t *report_out);
+void rocco_hip_bigwig_sections_shape(int *shape_out);
+
 /* ---- the grid caps of the record and select kernels -----------------------------------------------------------------
  * Every kernel behind the data front end caps its grid; past cap x unit a workgroup takes several units in turn (a grid
  * stride).  The caps are stated here once, the .hip files are built to them, and rocco_hip_launch_caps hands them to the

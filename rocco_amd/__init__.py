@@ -67,10 +67,12 @@ from .bam_index import (  # noqa: F401  (htslib's BAI reader: hts_idx_load, hts_
     contig_stats,
     open_bam_index,
 )
-from .bigwig import (  # noqa: F401  (the data blocks libBigWig inflates behind pyBigWig's intervals())
+from .bigwig import (  # noqa: F401  (what libBigWig does behind pyBigWig's intervals(): the data blocks, their intervals)
     clear_bigwig_cache,
     open_bigwig,
     read_bigwig_blocks,
+    read_bigwig_intervals,
+    read_bigwig_intervals_batch,
 )
 from .rocco import (  # noqa: F401
     chrom_solution_to_bed,

@@ -345,6 +345,19 @@ PROTOTYPES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
       ctypes.c_void_p, ctypes.c_void_p, c_ll_p]),
     ("rocco_hip_zlib_shape", None, [c_int_p]),
+    # row f10 (csrc/bigwig_sections.hip, csrc/bigwig_sections.h): libBigWig's bwGetOverlappingIntervals over the inflated blocks
+    ("rocco_hip_bigwig_sections_facts", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, c_ll_p, c_ll_p,
+      ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_bigwig_sections_emit", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, c_ll_p, c_ll_p,
+      ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    ("rocco_hip_bigwig_sections_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, c_ll_p, c_ll_p,
+      ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, c_ll_p]),
+    ("rocco_hip_bigwig_sections_shape", None, [c_int_p]),
     # (no reference line: the grid caps of the record and select kernels, for the tests that go past one launch's first turn)
     ("rocco_hip_launch_caps", None, [c_int_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,

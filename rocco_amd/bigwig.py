@@ -6,12 +6,18 @@ check and Adler-32 in HIP) or on the host (``inflate="host"``: `zlib.decompress`
 out are the inflated sections in HBM, one slot per block in R-tree leaf order -- the order libBigWig's
 ``bwGetOverlappingIntervals`` reads them in.
 
-Not built: the decode of the sections into (start, end, value) intervals on the device, and with it the reference's
-``get_bigwig_chrom_scores`` / ``generate_chrom_matrix`` over bigWig paths (note (31) says why); zoom levels (never read, as
-``intervals()`` never reads them), big-endian files (refused), bigBed."""
+The sections are decoded where they lie (csrc/bigwig_sections.hip over the rules of csrc/bigwig_sections.h, which the host
+twin `decode_sections_host` compiles too): `read_bigwig_intervals` / `read_bigwig_intervals_batch` return what pyBigWig's
+``intervals(chromosome)`` lists as three CUDA tensors, `get_bigwig_chrom_scores` and `generate_chrom_matrix(_device)` are the
+reference's functions of these names over bigWig paths (rocco/readtracks.py:94-186, 521-633) with no pyBigWig behind them.
+
+Not built: zoom levels (never read, as ``intervals()`` never reads them), big-endian files (refused), bigBed, a dense fill
+over several files at once."""
 from __future__ import annotations
 
 import collections
+import ctypes
+import logging
 import os
 import struct
 import zlib
@@ -19,13 +25,26 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import _native
 from . import dp as _dp
+from . import readtracks as _rt
 from .inflate import (  # noqa: F401  (what the BAM reader shares; the zlib names stay importable from here)
     BGZF_ERR_LENGTH, BGZF_ERR_STREAM, BGZF_MAX_ISIZE, ZLIB_ERR_ADLER, ZLIB_ERR_HEADER, ZLIB_ERR_TRUNCATED, ZLIB_HEADER_REASONS, ZLIB_MAX_GRID,
     ZLIB_TABLE_COLUMNS, _ADLER_TEXT, _HEADER_REASON_TEXT, _STREAM_REASON_TEXT, _TRUNCATED_TEXT, SpanList, _host_buffer, on_pool, upload_blocks,
     zlib_inflate_blocks_device, zlib_inflate_blocks_host, zlib_shape)
 
 DEFAULT_INFLATE = "device"  # where the data blocks are inflated: "device" or "host"
+logger = logging.getLogger(__name__)
+
+# ROCCO_BIGWIG_* of include/rocco_hip.h
+BIGWIG_ERR_SHORT, BIGWIG_ERR_TYPE, BIGWIG_ERR_ITEMS, BIGWIG_ERR_WRAP = 8, 9, 10, 11
+SECTION_HEADER_BYTES, SECTION_MAX_END = 24, 0xFFFFFFFF
+_SECTION_TEXT = {
+    BIGWIG_ERR_SHORT: f"the section is shorter than its {SECTION_HEADER_BYTES}-byte header",
+    BIGWIG_ERR_TYPE: "the section's type is not 1 (bedGraph), 2 (variableStep) or 3 (fixedStep)",
+    BIGWIG_ERR_ITEMS: "the section's header counts more items than its bytes hold (libBigWig would read past the section)",
+    BIGWIG_ERR_WRAP: f"an item of the section ends beyond {SECTION_MAX_END} (libBigWig would wrap around)",
+}
 
 BIGWIG_MAGIC, CHROM_TREE_MAGIC, RTREE_MAGIC = 0x888FFC26, 0x78CA8C91, 0x2468ACE0
 _HEADER, _ZOOM_HEADER, _CHROM_TREE_HEADER, _RTREE_HEADER, _NODE_HEADER = 64, 24, 32, 48, 4
@@ -352,3 +371,299 @@ def read_bigwig_blocks(path, chromosome: str, device=None, inflate: Optional[str
         raise KeyError(f"{file.name}: no chromosome {chromosome}")
     slots, table, produced, _ = inflate_chrom_blocks([(file, chromosome)], dev, inflate)
     return slots, table, produced
+
+
+# --------------------------------------------------------------------------------------------
+# the sections -> intervals (csrc/bigwig_sections.h, csrc/bigwig_sections.hip)
+# --------------------------------------------------------------------------------------------
+
+def sections_shape() -> dict:
+    """`rocco_hip_bigwig_sections_shape`: the lanes per block, the grid cap, the bytes of a section's header."""
+    shape = (ctypes.c_int * 3)()
+    _native.load().rocco_hip_bigwig_sections_shape(shape)
+    return dict(zip(("threads", "max_grid", "header_bytes"), (int(v) for v in shape)))
+
+
+def _file_arrays(file_first, chrom_ids, chrom_lengths):
+    """The three host arrays of the section entry points, int64: K + 1 block offsets, K chromosome ids, K chromosome lengths."""
+    first, ids, lengths = (np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int64) for a in (file_first, chrom_ids, chrom_lengths))
+    if first.size != ids.size + 1 or ids.size != lengths.size:
+        raise ValueError("K + 1 block offsets, K chromosome ids and K chromosome lengths are required")
+    return first, ids, lengths
+
+
+def _ll(a: np.ndarray):
+    return a.ctypes.data_as(_native.c_ll_p)
+
+
+def decode_sections_host(slots, table, produced, file_first, chrom_ids, chrom_lengths, emit: bool = True) -> dict:
+    """`rocco_hip_bigwig_sections_host` (test support: the kernels' rules compiled for the host, on the calling thread) over
+    NumPy arrays: ``status`` int32 per block, ``block_first`` int64 [n + 1], ``file_offsets`` int64 [K + 1], ``report``
+    (``block`` / ``status`` / ``produced``: the total), and with ``emit`` where no block is refused ``starts`` / ``ends``
+    int64 and ``values`` float64 (else None)."""
+    slots = np.ascontiguousarray(slots, dtype=np.uint8).reshape(-1)
+    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, ZLIB_TABLE_COLUMNS)
+    produced = np.ascontiguousarray(produced, dtype=np.int64).reshape(-1)
+    first, ids, lengths = _file_arrays(file_first, chrom_ids, chrom_lengths)
+    n = table.shape[0]
+    if produced.size != n:
+        raise ValueError("one produced per row of the block table is required")
+    status, block_first = np.zeros(n, dtype=np.int32), np.zeros(n + 1, dtype=np.int64)
+    offsets, back = np.zeros(first.size, dtype=np.int64), (ctypes.c_longlong * 4)()
+
+    def ptr(a):
+        return a.ctypes.data if a is not None and a.size else None
+
+    def call(starts, ends, values):
+        _native.check(_native.load().rocco_hip_bigwig_sections_host(
+            None, ptr(slots), slots.size, ptr(table), ptr(produced), n, _ll(first), _ll(ids), _ll(lengths), ids.size, ptr(status), n,
+            block_first.ctypes.data, block_first.size, _ll(offsets), ptr(starts), 0 if starts is None else starts.size, ptr(ends),
+            0 if ends is None else ends.size, ptr(values), 0 if values is None else values.size, back), "rocco_hip_bigwig_sections_host")
+
+    call(None, None, None)
+    out = {"status": status, "block_first": block_first, "file_offsets": offsets, "report": _report(back), "starts": None, "ends": None,
+           "values": None}
+    if emit and back[0] < 0:
+        total = int(back[2])
+        starts, ends, values = np.empty(total, dtype=np.int64), np.empty(total, dtype=np.int64), np.empty(total, dtype=np.float64)
+        if total:
+            call(starts, ends, values)
+        out.update(starts=starts, ends=ends, values=values)
+    return out
+
+
+def _report(back) -> dict:
+    return {"block": int(back[0]), "status": int(back[1]), "produced": int(back[2])}
+
+
+def _section_inputs(slots_t, table_t, produced_t):
+    import torch
+
+    for t, dtype in ((slots_t, torch.uint8), (table_t, torch.int64), (produced_t, torch.int64)):
+        if not _dp._is_tensor(t) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.device != slots_t.device:
+            raise TypeError("the sections: contiguous CUDA tensors on one device are required (uint8, int64, int64)")
+    if table_t.numel() % ZLIB_TABLE_COLUMNS or table_t.numel() // ZLIB_TABLE_COLUMNS != produced_t.numel():
+        raise ValueError(f"the block table has {ZLIB_TABLE_COLUMNS} columns and one produced per row")
+    return produced_t.numel()
+
+
+def sections_facts_device(slots_t, table_t, produced_t, file_first, chrom_ids, chrom_lengths):
+    """`rocco_hip_bigwig_sections_facts` over what `inflate_chrom_blocks` returns: (int32 status per block, int64 block_first
+    [n + 1] -- both CUDA tensors --, the K + 1 interval offsets of the files as a NumPy array, the report).  Returns when the
+    kernels have run."""
+    import torch
+
+    n = _section_inputs(slots_t, table_t, produced_t)
+    first, ids, lengths = _file_arrays(file_first, chrom_ids, chrom_lengths)
+    dev = slots_t.device
+    status_t = torch.empty(n, dtype=torch.int32, device=dev)
+    block_first_t = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    offsets, back = np.zeros(first.size, dtype=np.int64), (ctypes.c_longlong * 4)()
+    with torch.cuda.device(dev):
+        _native.check(_native.load().rocco_hip_bigwig_sections_facts(
+            _native.solver_for(dev.index).handle, slots_t.data_ptr() or None, slots_t.numel(), table_t.data_ptr() or None,
+            produced_t.data_ptr() or None, n, _ll(first), _ll(ids), _ll(lengths), ids.size, status_t.data_ptr() or None, n,
+            block_first_t.data_ptr(), n + 1, _ll(offsets), back, _dp._stream_ptr(slots_t)), "rocco_hip_bigwig_sections_facts")
+    return status_t, block_first_t, offsets, _report(back)
+
+
+def sections_emit_device(slots_t, table_t, produced_t, file_first, chrom_ids, chrom_lengths, block_first_t, total: int, starts_t, ends_t,
+                         values_t) -> None:
+    """`rocco_hip_bigwig_sections_emit`: the ``total`` kept items into the first cells of ``starts_t`` / ``ends_t`` (int64) and
+    ``values_t`` (float64), whose sizes go along.  Not called for a total of 0 (an empty tensor has no address)."""
+    import torch
+
+    n = _section_inputs(slots_t, table_t, produced_t)
+    first, ids, lengths = _file_arrays(file_first, chrom_ids, chrom_lengths)
+    dev = slots_t.device
+    for t, dtype in ((block_first_t, torch.int64), (starts_t, torch.int64), (ends_t, torch.int64), (values_t, torch.float64)):
+        if not _dp._is_tensor(t) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+            raise TypeError("sections_emit_device: contiguous CUDA tensors on the sections' device are required (int64, int64, int64, float64)")
+    if int(total) == 0:
+        return
+    with torch.cuda.device(dev):
+        _native.check(_native.load().rocco_hip_bigwig_sections_emit(
+            _native.solver_for(dev.index).handle, slots_t.data_ptr() or None, slots_t.numel(), table_t.data_ptr() or None,
+            produced_t.data_ptr() or None, n, _ll(first), _ll(ids), _ll(lengths), ids.size, block_first_t.data_ptr() or None,
+            block_first_t.numel(), int(total), starts_t.data_ptr() or None, starts_t.numel(), ends_t.data_ptr() or None, ends_t.numel(),
+            values_t.data_ptr() or None, values_t.numel(), _dp._stream_ptr(slots_t)), "rocco_hip_bigwig_sections_emit")
+
+
+def decode_sections_device(slots_t, table_t, produced_t, file_first, chrom_ids, chrom_lengths) -> dict:
+    """Both calls: ``status`` (CUDA int32), ``file_offsets`` (NumPy, K + 1), ``report``, and where no block is refused
+    ``starts`` / ``ends`` (CUDA int64) and ``values`` (CUDA float64), else None.  No block: no call."""
+    import torch
+
+    dev = slots_t.device
+    n = _section_inputs(slots_t, table_t, produced_t)
+    first, ids, lengths = _file_arrays(file_first, chrom_ids, chrom_lengths)
+    if n == 0:
+        status_t, offsets, report, block_first_t = torch.empty(0, dtype=torch.int32, device=dev), np.zeros(first.size, dtype=np.int64), _report((-1, 0, 0)), None
+    else:
+        status_t, block_first_t, offsets, report = sections_facts_device(slots_t, table_t, produced_t, first, ids, lengths)
+    out = {"status": status_t, "file_offsets": offsets, "report": report, "starts": None, "ends": None, "values": None}
+    if report["block"] < 0:
+        total = report["produced"]
+        starts_t, ends_t = torch.empty(total, dtype=torch.int64, device=dev), torch.empty(total, dtype=torch.int64, device=dev)
+        values_t = torch.empty(total, dtype=torch.float64, device=dev)
+        if total:
+            sections_emit_device(slots_t, table_t, produced_t, first, ids, lengths, block_first_t, total, starts_t, ends_t, values_t)
+        out.update(starts=starts_t, ends=ends_t, values=values_t)
+    return out
+
+
+def _section_words(status: int) -> str:
+    return _SECTION_TEXT.get(status & 0xFF, f"its row of the block table does not fit the buffers (status {status})")
+
+
+def read_bigwig_intervals_batch(wanted: Sequence[Tuple[str, str]], device=None, inflate: Optional[str] = None) -> list:
+    """For every (path, chromosome): what pyBigWig's ``intervals(chromosome)`` lists, as (starts int64, ends int64, values
+    float64) CUDA tensors in its order -- views into three arrays that hold the intervals of all files --, or None for a
+    chromosome the file lacks.  One block table, one inflate and one decode for all files (two waits for the device in the
+    decode, one in the device inflate).  ValueError naming the file, the block and its file offset for a block that does
+    not inflate or whose section is refused (csrc/bigwig_sections.h says what libBigWig would have done with it)."""
+    inflate = _resolve_inflate(inflate)
+    dev = _dp._device(device)
+    files = [open_bigwig(path) for path, _ in wanted]
+    present = [k for k, (file, (_, chromosome)) in enumerate(zip(files, wanted)) if chromosome in file.chroms]
+    out: list = [None] * len(wanted)
+    if not present:
+        return out
+    pairs = [(files[k], wanted[k][1]) for k in present]
+    slots, table, produced, file_first = inflate_chrom_blocks(pairs, dev, inflate)
+    ids = [file.chroms[chromosome][0] for file, chromosome in pairs]
+    lengths = [file.chroms[chromosome][1] for file, chromosome in pairs]
+    got = decode_sections_device(slots, table.reshape(-1), produced, file_first, ids, lengths)
+    if got["report"]["block"] >= 0:
+        block = got["report"]["block"]
+        k = int(np.searchsorted(file_first, block, side="right")) - 1
+        index = block - int(file_first[k])
+        file, chromosome = pairs[k]
+        raise ValueError(f"{_block_where(file.name, index, chrom_blocks(file, chromosome)[index][0])}: {_section_words(got['report']['status'])}")
+    offsets = got["file_offsets"]
+    for j, k in enumerate(present):
+        lo, hi = int(offsets[j]), int(offsets[j + 1])
+        out[k] = (got["starts"][lo:hi], got["ends"][lo:hi], got["values"][lo:hi])
+    return out
+
+
+def read_bigwig_intervals(path, chromosome: str, device=None, inflate: Optional[str] = None):
+    """What pyBigWig's ``open(path).intervals(chromosome)`` lists, as (starts int64, ends int64, values float64) CUDA tensors
+    in its order (the values are the file's float32 widened), or None for a chromosome the file lacks.  A chromosome without
+    intervals gives three empty tensors (pyBigWig: None).  Errors as `read_bigwig_intervals_batch`."""
+    return read_bigwig_intervals_batch([(os.fspath(path), chromosome)], device=device, inflate=inflate)[0]
+
+
+# --------------------------------------------------------------------------------------------
+# the reference's two entry points over bigWig paths (rocco/readtracks.py:94-186, 521-633)
+# --------------------------------------------------------------------------------------------
+
+def _checked_open(bigwig_file: str, chromosome: str, chrom_sizes_file: str) -> BigWigFile:
+    """What the reference's ``get_bigwig_chrom_scores`` does before it asks for intervals, in its order
+    (rocco/readtracks.py:103-119)."""
+    if not os.path.exists(bigwig_file):
+        raise FileNotFoundError(f"bigWig file not found: {bigwig_file}")
+    if not os.path.exists(chrom_sizes_file):
+        raise FileNotFoundError(f"Chromosome sizes file not found: {chrom_sizes_file}")
+    if chromosome not in _rt.get_chroms_and_sizes(chrom_sizes_file):
+        raise ValueError(f"Chromosome {chromosome} not found in chromosome sizes file: {chrom_sizes_file}")
+    return open_bigwig(bigwig_file)
+
+
+def _scores_of(bigwig_file: str, chromosome: str, file: BigWigFile, intervals, const_scale: float, round_digits: int, dev):
+    """rocco/readtracks.py:121-186 for a file already open and read: (first start, step, values in HBM) or (None, None, None),
+    with the reference's warnings and errors in its order."""
+    if chromosome not in file.chroms:
+        logger.warning("Chromosome %s not found in bigWig file: %s. Returning (None,None).", chromosome, bigwig_file)
+        return None, None, None
+    starts, ends, values = intervals
+    if int(starts.shape[0]) == 0:
+        logger.warning("No intervals found in bigWig file: %s for chromosome: %s. Returning (None,None).", bigwig_file, chromosome)
+        return None, None, None
+    first, step, full = _rt.bigwig_dense_fill_device(starts, ends, values, const_scale=const_scale, round_digits=round_digits,
+                                                     bigwig_file=bigwig_file, chromosome=chromosome, device=dev)
+    if const_scale == 0:  # (behind the five validations, where the reference has it)
+        logger.warning("You are scaling the values by 0.")
+    return first, step, full
+
+
+def get_bigwig_chrom_scores_device(bigwig_file: str, chromosome: str, chrom_sizes_file: str, const_scale: float = 1.0, round_digits: int = 5,
+                                   device=None, inflate: Optional[str] = None):
+    """`get_bigwig_chrom_scores` with the track left in HBM: (first start, step, values as a float64 CUDA tensor), the
+    reference's ``full_intervals`` being ``first + step * arange(len(values))``; (None, None, None) where it returns
+    (None, None)."""
+    file = _checked_open(bigwig_file, chromosome, chrom_sizes_file)
+    dev = _dp._device(device)
+    intervals = read_bigwig_intervals(bigwig_file, chromosome, device=dev, inflate=inflate) if chromosome in file.chroms else None
+    return _scores_of(bigwig_file, chromosome, file, intervals, const_scale, round_digits, dev)
+
+
+def get_bigwig_chrom_scores(bigwig_file: str, chromosome: str, chrom_sizes_file: str, const_scale: float = 1.0, round_digits: int = 5):
+    """rocco/readtracks.py:94-186 with the same arguments, return value, errors and log records, and no pyBigWig: the container
+    on the host, inflate, section decode, validation, dense fill, scaling and rounding on the device.  The binding:
+    ``rocco_amd.readtracks.get_bigwig_chrom_scores = rocco_amd.bigwig.get_bigwig_chrom_scores``."""
+    first, step, full = get_bigwig_chrom_scores_device(bigwig_file, chromosome, chrom_sizes_file, const_scale, round_digits)
+    if first is None:
+        return None, None
+    return np.arange(first, first + step * int(full.shape[0]), step, dtype=np.int64).astype(int), full.cpu().numpy()
+
+
+def generate_chrom_matrix_device(chromosome: str, input_files: list, chrom_sizes_file: str, step: int, const_scale: float = 1.0,
+                                 round_digits: int = 5, scale_by_step: bool = False, effective_genome_size: float = -1,
+                                 norm_method: str = "RPGC", min_mapping_score: int = 10, flag_include=None, flag_exclude: int = 3844,
+                                 extend_reads: int = -1, center_reads: bool = False, ignore_for_norm=None, scale_factor: float = 1.0,
+                                 num_processors: int = -1, low_memory: bool = False, device=None, inflate: Optional[str] = None):
+    """The reference's ``generate_chrom_matrix`` over bigWig files (rocco/readtracks.py:521-633, same keywords; those of the BAM
+    branch are taken and not used, as there) with the matrix left on the device: (starts as a host ``int`` array, matrix as a
+    CUDA tensor), or ``(None, None)``.  The files are read in ONE batch (`read_bigwig_intervals_batch`), then filled one by
+    one in file order, so errors and log records come as the reference's per-file loop gives them: a file the reference
+    would not have reached (one behind the first that raises) is not looked at.  This is the function to bind behind
+    ``rocco_amd.rocco.generate_chrom_matrix`` for bigWig inputs."""
+    import torch
+
+    track_types = {_rt._get_track_type(input_file) for input_file in input_files}
+    if len(track_types) != 1:
+        raise ValueError("All input files must share the same type.")
+    if next(iter(track_types)) != "bigwig":
+        raise ValueError("rocco_amd.bigwig.generate_chrom_matrix reads bigWig files: BAM inputs go through rocco_amd.bam.generate_chrom_matrix")
+    dev = _dp._device(device)
+    opened, stopped = [], None
+    for input_file in input_files:  # (what the reference does per file before it reads: up to the first file that raises)
+        try:
+            opened.append(_checked_open(input_file, chromosome, chrom_sizes_file))
+        except (OSError, ValueError, RuntimeError) as exc:
+            stopped = exc
+            break
+    read = read_bigwig_intervals_batch([(file.name, chromosome) for file in opened], device=dev, inflate=inflate)
+    results = [_scores_of(input_file, chromosome, file, intervals, const_scale, round_digits, dev)
+               for input_file, file, intervals in zip(input_files, opened, read)]
+    if stopped is not None:
+        raise stopped
+    interval_matrix, vals_matrix = [], []
+    for input_file, (first, step_, full) in zip(input_files, results):
+        if first is None:
+            logger.warning(f"No data found for {input_file} in chromosome {chromosome}. Excluding this track for {chromosome}.")
+            continue
+        interval_matrix.append(first + step_ * torch.arange(int(full.shape[0]), dtype=torch.int64, device=dev))
+        vals_matrix.append(full)
+    if not interval_matrix:
+        logger.warning(f"No data found in the files {str(input_files)} for chromosome {chromosome}. Returning (None,None).")
+        return None, None
+    common, matrix = _rt.assemble_chrom_matrix_device(interval_matrix, vals_matrix, track_type="bigwig", low_memory=low_memory,
+                                                      chromosome=chromosome, device=dev)
+    return common.cpu().numpy().astype(int), matrix
+
+
+def generate_chrom_matrix(chromosome: str, input_files: list, chrom_sizes_file: str, step: int, const_scale: float = 1.0,
+                          round_digits: int = 5, scale_by_step: bool = False, effective_genome_size: float = -1,
+                          norm_method: str = "RPGC", min_mapping_score: int = 10, flag_include=None, flag_exclude: int = 3844,
+                          extend_reads: int = -1, center_reads: bool = False, ignore_for_norm=None, scale_factor: float = 1.0,
+                          num_processors: int = -1, low_memory: bool = False):
+    """`generate_chrom_matrix_device` with the reference's signature and return value (rocco/readtracks.py:521-633): NumPy
+    ``(common_intervals.astype(int), count_matrix)``, or ``(None, None)``."""
+    starts, matrix = generate_chrom_matrix_device(chromosome, input_files, chrom_sizes_file, step, const_scale, round_digits, scale_by_step,
+                                                  effective_genome_size, norm_method, min_mapping_score, flag_include, flag_exclude,
+                                                  extend_reads, center_reads, ignore_for_norm, scale_factor, num_processors, low_memory)
+    if starts is None:
+        return None, None
+    return starts, matrix.cpu().numpy()

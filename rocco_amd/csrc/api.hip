@@ -7,6 +7,7 @@
 
 #include "budget.h"
 #include "inflate_core.h"
+#include "bigwig_sections.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1838,6 +1839,115 @@ void rocco_hip_zlib_shape(int *shape_out)
     shape_out[2] = ROCCO_BGZF_MAX_ISIZE;
     shape_out[3] = ROCCO_ZLIB_HEADER_REASONS;
     shape_out[4] = ROCCO_ZLIB_MAX_GRID;
+}
+
+// what the three section entry points ask of their inputs, device or host memory alike: every pointer with a size that is
+// not 0, the files' arrays sound, the per-block outputs long enough
+static bool sections_args_ok(const void *slots, size_t n_slots, const void *table, const void *produced, size_t n_blocks,
+                             const int64_t *file_first, const int64_t *chrom_id, const int64_t *chrom_length, size_t n_files,
+                             const void *block_first, size_t n_block_first)
+{
+    if (n_blocks >= (size_t)0x7fffffff || n_files >= ((size_t)1 << 24) || n_slots >= ((size_t)1 << 62) || file_first == nullptr ||
+        (n_files > 0 && (chrom_id == nullptr || chrom_length == nullptr)) || (n_slots > 0 && slots == nullptr) ||
+        (n_blocks > 0 && (table == nullptr || produced == nullptr)) || block_first == nullptr || n_block_first < n_blocks + 1 || !section_files_ok(file_first, n_files, n_blocks)) {
+        return false;
+    }
+    for (size_t k = 0; k < n_files; ++k) {
+        if (chrom_id[k] < 0 || chrom_id[k] > 0xFFFFFFFFLL || chrom_length[k] < 0 || chrom_length[k] > 0xFFFFFFFFLL) {
+            return false;
+        }
+    }
+    return true;
+}
+
+static bool sections_status_ok(const void *status, size_t n_status, size_t n_blocks)
+{
+    return n_status >= n_blocks && (n_status == 0 || status != nullptr);
+}
+
+static bool sections_outputs_ok(size_t total, const void *starts, size_t n_starts, const void *ends, size_t n_ends, const void *values,
+                                size_t n_values)
+{
+    return total < ((size_t)1 << 55) && n_starts >= total && n_ends >= total && n_values >= total && (n_starts == 0 || starts != nullptr) &&
+           (n_ends == 0 || ends != nullptr) && (n_values == 0 || values != nullptr);
+}
+
+int rocco_hip_bigwig_sections_facts(rocco_hip_solver *solver, const uint8_t *slots_dev, size_t n_slots, const int64_t *table_dev,
+                                    const int64_t *produced_dev, size_t n_blocks, const int64_t *file_first_host,
+                                    const int64_t *chrom_id_host, const int64_t *chrom_length_host, size_t n_files, int32_t *status_out_dev,
+                                    size_t n_status, int64_t *block_first_out_dev, size_t n_block_first, int64_t *file_offsets_out_host,
+                                    int64_t *report_out_host, void *stream)
+{
+    if (solver == nullptr || file_offsets_out_host == nullptr || report_out_host == nullptr ||
+        !sections_args_ok(slots_dev, n_slots, table_dev, produced_dev, n_blocks, file_first_host, chrom_id_host, chrom_length_host, n_files,
+                          block_first_out_dev, n_block_first) ||
+        !sections_status_ok(status_out_dev, n_status, n_blocks)) {
+        set_last_error("bigwig_sections_facts: a null pointer with a size, a size too small, or file offsets that do not ascend from 0 to n_blocks");
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, bigwig_sections_scratch_bytes(n_blocks, n_files)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_bigwig_sections_facts(slots_dev, n_slots, table_dev, produced_dev, n_blocks, file_first_host, chrom_id_host, chrom_length_host,
+                                        n_files, status_out_dev, block_first_out_dev, file_offsets_out_host, report_out_host,
+                                        solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_bigwig_sections_emit(rocco_hip_solver *solver, const uint8_t *slots_dev, size_t n_slots, const int64_t *table_dev,
+                                   const int64_t *produced_dev, size_t n_blocks, const int64_t *file_first_host,
+                                   const int64_t *chrom_id_host, const int64_t *chrom_length_host, size_t n_files,
+                                   const int64_t *block_first_dev, size_t n_block_first, size_t total, int64_t *starts_out_dev, size_t n_starts,
+                                   int64_t *ends_out_dev, size_t n_ends, double *values_out_dev, size_t n_values, void *stream)
+{
+    if (solver == nullptr ||
+        !sections_args_ok(slots_dev, n_slots, table_dev, produced_dev, n_blocks, file_first_host, chrom_id_host, chrom_length_host, n_files,
+                          block_first_dev, n_block_first) ||
+        !sections_outputs_ok(total, starts_out_dev, n_starts, ends_out_dev, n_ends, values_out_dev, n_values)) {
+        set_last_error("bigwig_sections_emit: a null pointer with a size, an output shorter than the total, or file offsets that do not ascend "
+                       "from 0 to n_blocks");
+        return ROCCO_HIP_EINVAL;
+    }
+    if (total == 0 || n_blocks == 0) {
+        return ROCCO_HIP_OK;
+    }
+    if (const int rc = enter_record_call(solver, bigwig_sections_scratch_bytes(n_blocks, n_files)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    const size_t capacity = std::min(n_starts, std::min(n_ends, n_values));
+    return launch_bigwig_sections_emit(slots_dev, n_slots, table_dev, produced_dev, n_blocks, file_first_host, chrom_id_host, chrom_length_host,
+                                       n_files, block_first_dev, capacity, starts_out_dev, ends_out_dev, values_out_dev, solver->dev_misc.ptr,
+                                       (hipStream_t)stream);
+}
+
+int rocco_hip_bigwig_sections_host(rocco_hip_solver *, const uint8_t *slots, size_t n_slots, const int64_t *table, const int64_t *produced,
+                                   size_t n_blocks, const int64_t *file_first, const int64_t *chrom_id, const int64_t *chrom_length,
+                                   size_t n_files, int32_t *status_out, size_t n_status, int64_t *block_first_out, size_t n_block_first,
+                                   int64_t *file_offsets_out, int64_t *starts_out, size_t n_starts, int64_t *ends_out, size_t n_ends,
+                                   double *values_out, size_t n_values, int64_t *report_out)
+{
+    if (file_offsets_out == nullptr || report_out == nullptr ||
+        !sections_args_ok(slots, n_slots, table, produced, n_blocks, file_first, chrom_id, chrom_length, n_files, block_first_out, n_block_first) ||
+        !sections_status_ok(status_out, n_status, n_blocks) ||
+        !sections_outputs_ok(0, starts_out, n_starts, ends_out, n_ends, values_out, n_values) ||
+        ((starts_out == nullptr) != (ends_out == nullptr)) || ((starts_out == nullptr) != (values_out == nullptr))) {
+        set_last_error("bigwig_sections_host: a null pointer with a size, a size too small, or file offsets that do not ascend from 0 to n_blocks");
+        return ROCCO_HIP_EINVAL;
+    }
+    static_assert(sizeof(double) == sizeof(uint64_t), "the values are placed as bit patterns");
+    if (!sections_host(slots, n_slots, table, produced, n_blocks, file_first, chrom_id, chrom_length, n_files, status_out, block_first_out,
+                       file_offsets_out, starts_out, ends_out, (uint64_t *)values_out, std::min(n_starts, std::min(n_ends, n_values)),
+                       report_out)) {
+        set_last_error("bigwig_sections_host: the sections hold " + std::to_string(report_out[2]) + " intervals, an output has room for fewer");
+        return ROCCO_HIP_EINVAL;
+    }
+    return ROCCO_HIP_OK;
+}
+
+void rocco_hip_bigwig_sections_shape(int *shape_out)
+{
+    shape_out[0] = ROCCO_BIGWIG_THREADS;
+    shape_out[1] = ROCCO_BIGWIG_MAX_GRID;
+    shape_out[2] = (int)kSectionHeaderBytes;
 }
 
 void rocco_hip_launch_caps(int *out)

@@ -413,6 +413,19 @@ template <class F>
 int launch_inflate(const uint8_t *comp_dev, size_t n_comp, const int64_t *table_dev, size_t n_blocks, uint8_t *out_dev, size_t n_out,
                    int32_t *status_out_dev, int64_t *produced_out_dev, int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
 
+// ---- bigwig_sections.hip ----------------------------------------------------------------------
+// the inflated sections of bigWig files -> intervals (row f10); the rules and the host twin are bigwig_sections.h's.  The
+// entry points of api.hip have checked every size; 0 scratch bytes: hipcub refused the shape
+size_t bigwig_sections_scratch_bytes(size_t n_blocks, size_t n_files);
+int launch_bigwig_sections_facts(const uint8_t *slots_dev, size_t n_slots, const int64_t *table_dev, const int64_t *produced_dev, size_t n_blocks,
+                                 const int64_t *file_first_host, const int64_t *chrom_id_host, const int64_t *chrom_length_host, size_t n_files,
+                                 int32_t *status_out_dev, int64_t *block_first_out_dev, int64_t *file_offsets_out_host, int64_t *report_out_host,
+                                 void *scratch_dev, hipStream_t stream);
+int launch_bigwig_sections_emit(const uint8_t *slots_dev, size_t n_slots, const int64_t *table_dev, const int64_t *produced_dev, size_t n_blocks,
+                                const int64_t *file_first_host, const int64_t *chrom_id_host, const int64_t *chrom_length_host, size_t n_files,
+                                const int64_t *block_first_dev, size_t capacity, int64_t *starts_out_dev, int64_t *ends_out_dev,
+                                double *values_out_dev, void *scratch_dev, hipStream_t stream);
+
 // ---- synth.hip ------------------------------------------------------------------------------
 int launch_synth(void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, uint64_t seed,
                  hipStream_t stream);

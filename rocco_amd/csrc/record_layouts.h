@@ -219,6 +219,24 @@ struct InflateLayout {
     }
 };
 
+// launch_bigwig_sections_facts / _emit: the files' arrays as they go up (n_files + 1 block offsets, n_files chromosome ids,
+// n_files chromosome lengths, int64; first, so that both calls find them at one place whatever hipcub asks for), the
+// n_blocks + 1 kept-item counts (int64), the word of the first refused block, what comes back (the report and the
+// n_files + 1 interval offsets, int64), hipcub's scan over the counts
+struct SectionsLayout {
+    size_t files, counts, first_error, back, scan, bytes;
+    SectionsLayout(size_t n_blocks, size_t n_files, size_t scan_bytes)
+    {
+        Layout lay;
+        files = lay.at((3 * n_files + 1) * sizeof(long long));
+        counts = lay.at((n_blocks + 1) * sizeof(long long));
+        first_error = lay.at(sizeof(unsigned long long));
+        back = lay.at((ROCCO_BGZF_REPORT + n_files + 1) * sizeof(long long));
+        scan = lay.at(scan_bytes > 0 ? scan_bytes : 1);
+        bytes = lay.bytes();
+    }
+};
+
 }  // namespace
 
 }  // namespace rocco
