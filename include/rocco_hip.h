@@ -758,6 +758,17 @@ void rocco_hip_track_matrix_shape(int *out);
  *   max(end, pos + 1) - pos of track t (the width of the candidate window, so one very long record costs time on its
  *   track, never correctness), [2 t + 1] non-zero when the track's pos does not ascend -- its counts are then undefined
  *   and the caller refuses them.  One synchronisation, at the end.  P * F < 2^31 - 1.
+ * rocco_hip_count_alignment_intervals_sets: the same counting for a contig group that is
+ *   resident once, with the peaks and the null regions on it counted in one launch series and the counts stored at their
+ *   final places.  options_host points to S option sets, 1 <= S <= ROCCO_COUNT_INTERVALS_MAX_SETS; set_id_dev is int32 [P],
+ *   the set of every interval.  row_dev is int64 [P]: the count of interval p in file f goes to
+ *   out_dev[row[p] * out_stride + col0 + f], out_dev being int32 [out_rows][out_stride] (out_stride: ints per row).
+ *   Exactly the addressed cells are written, zeros included; every other cell of out_dev keeps its contents.  The rows of
+ *   one call must be distinct: the caller's to ensure, not tested here (two intervals of one row would race).  S outside
+ *   its range, out_rows = 0 or col0 + F > out_stride is ROCCO_HIP_EINVAL before anything is queued; a set id outside
+ *   [0, S) or a row outside [0, out_rows) is ROCCO_HIP_EINVAL after the call's one synchronisation (the flag comes back
+ *   with the track facts): no cell of such an interval is written, the other intervals' cells are.  Everything else --
+ *   tracks, intervals, counts, track_facts_out_host (2 T ints, filled in both cases) -- as the call above.
  * rocco_hip_count_intervals_shape: shape_out[0..2] = candidate records of one work unit, workgroups of the counting
  *   launch at most, wavefronts per workgroup (a wavefront takes one unit at a time, in a grid stride). */
 #define ROCCO_COUNT_INTERVALS_UNIT 256
@@ -769,6 +780,14 @@ int rocco_hip_count_alignment_intervals_batch(rocco_hip_solver *solver, const in
                                               const rocco_hip_count_options *options_host, const int32_t *contig_id_dev,
                                               const int32_t *start_dev, const int32_t *end_region_dev, size_t P, int32_t *out_dev,
                                               int32_t *track_facts_out_host, void *stream);
+#define ROCCO_COUNT_INTERVALS_MAX_SETS 4
+int rocco_hip_count_alignment_intervals_sets(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                             const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mapq_dev,
+                                             const uint8_t *mate_same_dev, const int64_t *rec_offsets_host, size_t F, size_t C,
+                                             const rocco_hip_count_options *options_host, size_t S, const int32_t *set_id_dev,
+                                             const int32_t *contig_id_dev, const int32_t *start_dev, const int32_t *end_region_dev,
+                                             const int64_t *row_dev, size_t P, int32_t *out_dev, size_t out_rows,
+                                             size_t out_stride, size_t col0, int32_t *track_facts_out_host, void *stream);
 void rocco_hip_count_intervals_shape(int *shape_out);
 
 /* ---- decoded alignment records of whole files -> the facts behind the count metadata ------

@@ -79,6 +79,8 @@ from .rocco import (  # noqa: F401
     combine_chrom_results,
     cscores_quantiles,
     cscores_quantiles_batch_device,
+    generate_narrowpeak_if_requested,
+    run_to_narrowpeak,
     score_central_tendency_chrom,
     score_dispersion_chrom,
     solve_cached_chromosomes,

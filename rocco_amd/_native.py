@@ -299,6 +299,12 @@ PROTOTYPES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       c_ll_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_size_t, ctypes.c_void_p, c_int_p, ctypes.c_void_p]),
+    # row f12: the same for S option sets with placed output (the peaks and nulls of rocco/scores.py's score_peaks in one call)
+    ("rocco_hip_count_alignment_intervals_sets", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      c_ll_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+      ctypes.c_size_t, c_int_p, ctypes.c_void_p]),
     ("rocco_hip_count_intervals_shape", None, [c_int_p]),
     # row f7 (csrc/fragment_length.hip): ccounts_getMappedReadCount, rocco/native/ccounts_backend.c:1712-1888
     ("rocco_hip_record_flag_facts", ctypes.c_int,

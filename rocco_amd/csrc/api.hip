@@ -1646,6 +1646,38 @@ int rocco_hip_count_alignment_intervals_batch(rocco_hip_solver *solver, const in
                                             track_facts_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
 }
 
+int rocco_hip_count_alignment_intervals_sets(rocco_hip_solver *solver, const int32_t *pos_dev, const int32_t *end_dev,
+                                             const int32_t *isize_dev, const uint16_t *flag_dev, const uint8_t *mapq_dev,
+                                             const uint8_t *mate_same_dev, const int64_t *rec_offsets_host, size_t F, size_t C,
+                                             const rocco_hip_count_options *options_host, size_t S, const int32_t *set_id_dev,
+                                             const int32_t *contig_id_dev, const int32_t *start_dev, const int32_t *end_region_dev,
+                                             const int64_t *row_dev, size_t P, int32_t *out_dev, size_t out_rows,
+                                             size_t out_stride, size_t col0, int32_t *track_facts_out_host, void *stream)
+{
+    if (solver == nullptr || F == 0 || C == 0 || P == 0 || rec_offsets_host == nullptr || options_host == nullptr ||
+        set_id_dev == nullptr || contig_id_dev == nullptr || start_dev == nullptr || end_region_dev == nullptr ||
+        row_dev == nullptr || out_dev == nullptr || track_facts_out_host == nullptr || S == 0 ||
+        S > (size_t)ROCCO_COUNT_INTERVALS_MAX_SETS || out_rows == 0 || col0 > out_stride || F > out_stride - col0) {
+        return ROCCO_HIP_EINVAL;
+    }
+    const size_t bytes = count_intervals_sets_scratch_bytes(rec_offsets_host, F, C, P);
+    if (bytes == 0) {  // (before rec_offsets_host[F * C] is read: F * C may be what was refused)
+        return ROCCO_HIP_EINVAL;
+    }
+    if (rec_offsets_host[F * C] > rec_offsets_host[0] &&
+        (pos_dev == nullptr || end_dev == nullptr || isize_dev == nullptr || flag_dev == nullptr || mapq_dev == nullptr ||
+         mate_same_dev == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, bytes); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_count_alignment_intervals_sets(pos_dev, end_dev, isize_dev, flag_dev, mapq_dev, mate_same_dev, rec_offsets_host, F,
+                                                 C, options_host, S, set_id_dev, contig_id_dev, start_dev, end_region_dev, row_dev,
+                                                 P, out_dev, out_rows, out_stride, col0, track_facts_out_host,
+                                                 solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
 void rocco_hip_count_intervals_shape(int *shape_out)
 {
     shape_out[0] = ROCCO_COUNT_INTERVALS_UNIT;

@@ -20,6 +20,11 @@
 //                                atomicAdd (a plain store where the pair has one unit)
 // Integer counts: the result does not depend on scheduling.  A long record widens L for its whole track: more candidates
 // are read and filtered (time), never a wrong count.
+//
+// Row f12 (a contig group resident once, its peaks and null regions counted together): the same three steps with
+// interval_sets_bounds_kernel / interval_sets_count_kernel -- every interval names one of up to four option sets, which
+// travel by value in the kernel arguments, and the count of (interval p, file f) is stored at out[row[p] * out_stride +
+// col0 + f]; the bounds kernel zeroes that cell, so exactly the addressed cells of out are written.
 #include "kernels.h"
 #include "record_cells.h"
 #include "record_layouts.h"
@@ -80,6 +85,22 @@ __global__ __launch_bounds__(kThreads) void interval_track_facts_kernel(const in
     }
 }
 
+// the candidates [*lo, *lo + *n) of region [s, e) on contig c of file f: first pos > s - L, first pos >= e; none for a
+// contig outside [0, C) or an empty region
+__device__ __forceinline__ void candidate_window(const int *__restrict__ pos, const long long *__restrict__ rec_offsets,
+                                                 const int *__restrict__ facts, int f, int C, int c, long long s, long long e,
+                                                 long long *lo, long long *n)
+{
+    if (c >= 0 && c < C && s >= 0 && e > s) {
+        const int t = f * C + c;
+        const long long b = rec_offsets[t], last = rec_offsets[t + 1];
+        const long long L = facts[2 * t];
+        *lo = lower_bound_pos(pos, b, last, s - L + 1);  // first pos > start - L
+        const long long hi = lower_bound_pos(pos, *lo, last, e);  // first pos >= end (at or behind lo: start - L < end)
+        *n = hi - *lo;
+    }
+}
+
 // one thread per (interval p, file f), pair = p * F + f: cand_lo / cand_n = its candidates, units = its work units.
 // units has pairs + 1 entries (the last one 0) so that the exclusive scan's last entry is the total.
 __global__ __launch_bounds__(kThreads) void interval_bounds_kernel(const int *__restrict__ pos, const long long *__restrict__ rec_offsets,
@@ -99,17 +120,8 @@ __global__ __launch_bounds__(kThreads) void interval_bounds_kernel(const int *__
     }
     const long long p = pair / F;
     const int f = (int)(pair - p * F);
-    const int c = contig_id[p];
-    const long long s = start[p], e = end[p];
     long long lo = 0, n = 0;
-    if (c >= 0 && c < C && s >= 0 && e > s) {
-        const int t = f * C + c;
-        const long long b = rec_offsets[t], last = rec_offsets[t + 1];
-        const long long L = facts[2 * t];
-        lo = lower_bound_pos(pos, b, last, s - L + 1);  // first pos > start - L
-        const long long hi = lower_bound_pos(pos, lo, last, e);  // first pos >= end (at or behind lo: start - L < end)
-        n = hi - lo;
-    }
+    candidate_window(pos, rec_offsets, facts, f, C, contig_id[p], start[p], end[p], &lo, &n);
     cand_lo[pair] = lo;
     cand_n[pair] = (int)n;
     units[pair] = (n + kUnit - 1) / kUnit;
@@ -120,6 +132,29 @@ __device__ __forceinline__ long long uniform64(long long v)
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)v);
     const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)v >> 32));
     return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// the records [base, min(base + kUnit, limit)) that count for t's region (one bin), summed over the wavefront
+__device__ __forceinline__ int count_unit(const CountTrack &t, const int *__restrict__ pos, const int *__restrict__ end,
+                                          const int *__restrict__ isize, const unsigned short *__restrict__ flag,
+                                          const unsigned char *__restrict__ mapq, const unsigned char *__restrict__ mate_same,
+                                          long long base, long long limit, int lane)
+{
+    int count = 0;
+#pragma unroll
+    for (int j = 0; j < kRecsPerLane; ++j) {
+        const long long r = base + j * kWave + lane;
+        if (r < limit) {
+            int i0 = -1, i1 = -1;
+            if (record_cells(t, pos[r], end[r], isize[r], flag[r], mapq[r], mate_same[r], &i0, &i1)) {
+                count += 1;  // (one bin: i0 == 0)
+            }
+        }
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        count += __shfl_xor(count, off);
+    }
+    return count;
 }
 
 // unit_first: the exclusive scan of units (pairs + 1 entries; unit_first[pairs] is the number of units).  `options` holds
@@ -145,27 +180,101 @@ __global__ __launch_bounds__(kThreads) void interval_count_kernel(
         t.end = stop[p];
         t.step = t.end - t.start;  // intervalSizeBP = end - start (_hts_counts.c:571-836): one bin
         t.n_bins = 1;
-        const long long base = lo + (unit - first_unit) * kUnit;
-        const long long limit = lo + n;
-        int count = 0;
-#pragma unroll
-        for (int j = 0; j < kRecsPerLane; ++j) {
-            const long long r = base + j * kWave + lane;
-            if (r < limit) {
-                int i0 = -1, i1 = -1;
-                if (record_cells(t, pos[r], end[r], isize[r], flag[r], mapq[r], mate_same[r], &i0, &i1)) {
-                    count += 1;  // (one bin: i0 == 0)
-                }
-            }
-        }
-        for (int off = kWave / 2; off > 0; off >>= 1) {
-            count += __shfl_xor(count, off);
-        }
+        const int count = count_unit(t, pos, end, isize, flag, mapq, mate_same, lo + (unit - first_unit) * kUnit, lo + n, lane);
         if (lane == 0 && count != 0) {
             if (n <= kUnit) {
                 out[pair] = count;  // the pair's only unit
             } else {
                 atomicAdd(&out[pair], count);
+            }
+        }
+    }
+}
+
+// ---- the same counting for a resident contig group with several option sets and placed output ----
+// The S option sets of a call travel by value in the kernel arguments: a wavefront picks its interval's set once per unit.
+struct CountSets {
+    CountTrack set[ROCCO_COUNT_INTERVALS_MAX_SETS];
+};
+
+// where the counts of interval p go: out[row[p] * out_stride + col0 + f]
+struct OutPlace {
+    long long out_rows, out_stride, col0;
+};
+
+// interval_bounds_kernel for the sets call: an interval whose set id is outside [0, S) or whose row is outside
+// [0, out_rows) raises *error and gets no unit and no store; every other pair's output cell is zeroed here, so that the
+// count kernel adds into zeros and every cell nobody addresses keeps its contents.
+__global__ __launch_bounds__(kThreads) void interval_sets_bounds_kernel(
+    const int *__restrict__ pos, const long long *__restrict__ rec_offsets, const int *__restrict__ facts, int F, int C, int S,
+    const int *__restrict__ set_id, const int *__restrict__ contig_id, const int *__restrict__ start, const int *__restrict__ end,
+    const long long *__restrict__ row, OutPlace place, long long pairs, long long *__restrict__ cand_lo,
+    int *__restrict__ cand_n, long long *__restrict__ units, int *__restrict__ out, int *__restrict__ error)
+{
+    const long long pair = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (pair > pairs) {
+        return;
+    }
+    if (pair == pairs) {
+        units[pair] = 0;
+        return;
+    }
+    const long long p = pair / F;
+    const int f = (int)(pair - p * F);
+    const int sid = set_id[p];
+    const long long r = row[p];
+    long long lo = 0, n = 0;
+    if (sid < 0 || sid >= S || r < 0 || r >= place.out_rows) {
+        if (f == 0) {
+            atomicOr(error, 1);
+        }
+    } else {
+        candidate_window(pos, rec_offsets, facts, f, C, contig_id[p], start[p], end[p], &lo, &n);
+        out[r * place.out_stride + place.col0 + f] = 0;
+    }
+    cand_lo[pair] = lo;
+    cand_n[pair] = (int)n;
+    units[pair] = (n + kUnit - 1) / kUnit;
+}
+
+// interval_count_kernel with the option set and the output cell of the unit's interval.  Only pairs the bounds kernel
+// accepted have units, so set_id[p] and row[p] are in range here.
+__global__ __launch_bounds__(kThreads) void interval_sets_count_kernel(
+    const int *__restrict__ pos, const int *__restrict__ end, const int *__restrict__ isize,
+    const unsigned short *__restrict__ flag, const unsigned char *__restrict__ mapq,
+    const unsigned char *__restrict__ mate_same, CountSets sets, int F, const int *__restrict__ set_id,
+    const int *__restrict__ start, const int *__restrict__ stop, const long long *__restrict__ row, OutPlace place, int pairs,
+    const long long *__restrict__ cand_lo, const int *__restrict__ cand_n, const long long *__restrict__ unit_first,
+    int *__restrict__ out)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const long long total_units = unit_first[pairs];
+    const long long stride = (long long)gridDim.x * kWavesPerGroup;
+    for (long long unit = uniform64((long long)blockIdx.x * kWavesPerGroup + (threadIdx.x / kWave)); unit < total_units; unit += stride) {
+        const int pair = __builtin_amdgcn_readfirstlane(find_slot(unit_first, pairs, unit));
+        const int p = pair / F;
+        const long long first_unit = unit_first[pair];
+        const long long lo = cand_lo[pair];
+        const int n = cand_n[pair];
+        const int sid = __builtin_amdgcn_readfirstlane(set_id[p]);
+        CountTrack t = sets.set[0];
+#pragma unroll
+        for (int s = 1; s < ROCCO_COUNT_INTERVALS_MAX_SETS; ++s) {
+            if (sid == s) {
+                t = sets.set[s];
+            }
+        }
+        t.start = start[p];
+        t.end = stop[p];
+        t.step = t.end - t.start;  // intervalSizeBP = end - start (_hts_counts.c:571-836): one bin
+        t.n_bins = 1;
+        const int count = count_unit(t, pos, end, isize, flag, mapq, mate_same, lo + (unit - first_unit) * kUnit, lo + n, lane);
+        if (lane == 0 && count != 0) {
+            int *cell = out + (row[p] * place.out_stride + place.col0 + (pair - p * F));
+            if (n <= kUnit) {
+                *cell = count;  // the pair's only unit
+            } else {
+                atomicAdd(cell, count);
             }
         }
     }
@@ -265,6 +374,94 @@ int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_
     }
     for (size_t i = 0; i < 2 * T; ++i) {
         track_facts_out_host[i] = facts[i];
+    }
+    return ROCCO_HIP_OK;
+}
+
+size_t count_intervals_sets_scratch_bytes(const int64_t *rec_offsets_host, size_t F, size_t C, size_t P)
+{
+    size_t scan_bytes = 0;
+    if (check_interval_shape(rec_offsets_host, F, C, P) != ROCCO_HIP_OK || size_interval_scan(P * F, scan_bytes) != ROCCO_HIP_OK) {
+        return 0;
+    }
+    return IntervalSetsLayout(F * C, P * F, scan_bytes).bytes;
+}
+
+int launch_count_alignment_intervals_sets(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
+                                          const uint16_t *flag_dev, const uint8_t *mapq_dev, const uint8_t *mate_same_dev,
+                                          const int64_t *rec_offsets_host, size_t F, size_t C,
+                                          const rocco_hip_count_options *options_host, size_t S, const int32_t *set_id_dev,
+                                          const int32_t *contig_id_dev, const int32_t *start_dev, const int32_t *end_region_dev,
+                                          const int64_t *row_dev, size_t P, int32_t *out_dev, size_t out_rows, size_t out_stride,
+                                          size_t col0, int32_t *track_facts_out_host, void *scratch_dev, hipStream_t stream)
+{
+    const size_t T = F * C, pairs = P * F;
+    size_t scan_bytes = 0;
+    int rc = check_interval_shape(rec_offsets_host, F, C, P);
+    if (rc != ROCCO_HIP_OK || (rc = size_interval_scan(pairs, scan_bytes)) != ROCCO_HIP_OK) {
+        return rc;
+    }
+    if (S == 0 || S > (size_t)ROCCO_COUNT_INTERVALS_MAX_SETS || out_rows == 0 || out_rows >= ((size_t)1 << 40) ||
+        out_stride >= ((size_t)1 << 20) || col0 > out_stride || F > out_stride - col0) {
+        set_last_error("count_alignment_intervals_sets: the number of option sets or the output placement is out of range");
+        return ROCCO_HIP_EINVAL;
+    }
+    const IntervalSetsLayout at(T, pairs, scan_bytes);
+    CountSets sets = {};
+    for (size_t s = 0; s < S; ++s) {
+        sets.set[s] = count_track_from_options(options_host[s]);
+    }
+    const OutPlace place = {(long long)out_rows, (long long)out_stride, (long long)col0};
+    std::vector<long long> offsets(rec_offsets_host, rec_offsets_host + T + 1);
+    std::vector<int> facts(2 * T + 1, 0);  // [2 T]: the error flag of the bounds kernel
+    const long long records = offsets[T] - offsets[0];
+    // the copies below read this call's host vectors: no return before the stream has taken them
+    const int queued = queue_then_drain(stream, [&]() -> int {
+        char *sc = (char *)scratch_dev;
+        long long *rec_offsets = (long long *)(sc + at.rec_offsets), *cand_lo = (long long *)(sc + at.cand_lo);
+        long long *units = (long long *)(sc + at.units), *unit_first = (long long *)(sc + at.unit_first);
+        int *facts_dev = (int *)(sc + at.facts), *cand_n = (int *)(sc + at.cand_n);
+        ROCCO_HIP_TRY(hipMemcpyAsync(rec_offsets, offsets.data(), (T + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+        ROCCO_HIP_TRY(hipMemsetAsync(facts_dev, 0, (2 * T + 1) * sizeof(int), stream));
+        if (records > 0) {
+            const long long blocks = (records + kThreads - 1) / kThreads;
+            hipLaunchKernelGGL(interval_track_facts_kernel, dim3((unsigned)(blocks < kFactsMaxGrid ? blocks : kFactsMaxGrid)), dim3(kThreads), 0, stream,
+                               (const int *)pos_dev, (const int *)end_dev, rec_offsets, (int)T, facts_dev);
+        }
+        hipLaunchKernelGGL(interval_sets_bounds_kernel, dim3((unsigned)((pairs + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
+                           (const int *)pos_dev, rec_offsets, facts_dev, (int)F, (int)C, (int)S, (const int *)set_id_dev,
+                           (const int *)contig_id_dev, (const int *)start_dev, (const int *)end_region_dev,
+                           (const long long *)row_dev, place, (long long)pairs, cand_lo, cand_n, units, (int *)out_dev,
+                           facts_dev + 2 * T);
+        ROCCO_HIP_TRY(hipGetLastError());
+        ROCCO_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc + at.scan, scan_bytes, (const long long *)units, unit_first,
+                                                       (int)(pairs + 1), stream));
+        if (records > 0) {
+            // (the grid of launch_count_alignment_intervals)
+            const size_t wanted = (pairs + kWavesPerGroup - 1) / kWavesPerGroup;
+            const size_t by_records = (size_t)((records + kUnit - 1) / kUnit + kWavesPerGroup - 1) / kWavesPerGroup;
+            size_t grid = wanted > by_records ? wanted : by_records;
+            grid = grid < (size_t)kMaxGrid ? grid : (size_t)kMaxGrid;
+            hipLaunchKernelGGL(interval_sets_count_kernel, dim3((unsigned)grid), dim3(kThreads), 0, stream, (const int *)pos_dev,
+                               (const int *)end_dev, (const int *)isize_dev, (const unsigned short *)flag_dev,
+                               (const unsigned char *)mapq_dev, (const unsigned char *)mate_same_dev, sets, (int)F,
+                               (const int *)set_id_dev, (const int *)start_dev, (const int *)end_region_dev,
+                               (const long long *)row_dev, place, (int)pairs, cand_lo, cand_n, unit_first, (int *)out_dev);
+            ROCCO_HIP_TRY(hipGetLastError());
+        }
+        ROCCO_HIP_TRY(hipMemcpyAsync(facts.data(), facts_dev, (2 * T + 1) * sizeof(int), hipMemcpyDeviceToHost, stream));
+        ROCCO_HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait: the facts and the flag are the caller's guard
+        return ROCCO_HIP_OK;
+    });
+    if (queued != ROCCO_HIP_OK) {
+        return queued;
+    }
+    for (size_t i = 0; i < 2 * T; ++i) {
+        track_facts_out_host[i] = facts[i];
+    }
+    if (facts[2 * T] != 0) {
+        set_last_error("count_alignment_intervals_sets: an interval's set id or output row is out of range");
+        return ROCCO_HIP_EINVAL;
     }
     return ROCCO_HIP_OK;
 }

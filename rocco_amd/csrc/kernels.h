@@ -361,6 +361,16 @@ int launch_count_alignment_intervals(const int32_t *pos_dev, const int32_t *end_
                                      const int32_t *contig_id_dev, const int32_t *start_dev, const int32_t *end_region_dev, size_t P,
                                      int32_t *out_dev, int32_t *track_facts_out_host, void *scratch_dev, hipStream_t stream);
 
+// the same for S option sets, with the counts placed at out_dev[row[p] * out_stride + col0 + f]; 0: the shape is out of range
+size_t count_intervals_sets_scratch_bytes(const int64_t *rec_offsets_host, size_t F, size_t C, size_t P);
+int launch_count_alignment_intervals_sets(const int32_t *pos_dev, const int32_t *end_dev, const int32_t *isize_dev,
+                                          const uint16_t *flag_dev, const uint8_t *mapq_dev, const uint8_t *mate_same_dev,
+                                          const int64_t *rec_offsets_host, size_t F, size_t C,
+                                          const rocco_hip_count_options *options_host, size_t S, const int32_t *set_id_dev,
+                                          const int32_t *contig_id_dev, const int32_t *start_dev, const int32_t *end_region_dev,
+                                          const int64_t *row_dev, size_t P, int32_t *out_dev, size_t out_rows, size_t out_stride,
+                                          size_t col0, int32_t *track_facts_out_host, void *scratch_dev, hipStream_t stream);
+
 // ---- fragment_length.hip ----------------------------------------------------------------------
 size_t record_flag_facts_scratch_bytes(size_t T);
 int launch_record_flag_facts(const int32_t *pos_dev, const uint16_t *flag_dev, const int64_t *rec_offsets_host, size_t T,

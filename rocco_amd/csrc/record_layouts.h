@@ -85,6 +85,24 @@ struct IntervalLayout {
     }
 };
 
+// launch_count_alignment_intervals_sets: IntervalLayout with one more int behind the 2 T facts, the call's error flag, so
+// that facts and flag come back in one copy
+struct IntervalSetsLayout {
+    size_t rec_offsets, facts, cand_lo, cand_n, units, unit_first, scan, bytes;
+    IntervalSetsLayout(size_t T, size_t pairs, size_t scan_bytes)
+    {
+        Layout lay;
+        rec_offsets = lay.at((T + 1) * sizeof(long long));
+        facts = lay.at((2 * T + 1) * sizeof(int));
+        cand_lo = lay.at(pairs * sizeof(long long));
+        cand_n = lay.at(pairs * sizeof(int));
+        units = lay.at((pairs + 1) * sizeof(long long));
+        unit_first = lay.at((pairs + 1) * sizeof(long long));
+        scan = lay.at(scan_bytes > 0 ? scan_bytes : 1);
+        bytes = lay.bytes();
+    }
+};
+
 // launch_record_flag_facts
 struct FlagFactsLayout {
     size_t rec_offsets, mapped, unsorted, bytes;

@@ -769,6 +769,72 @@ def count_alignment_intervals_batch_device(records_by_file: Sequence[dict], chro
     return out
 
 
+COUNT_INTERVALS_MAX_SETS = 4  # ROCCO_COUNT_INTERVALS_MAX_SETS of include/rocco_hip.h
+
+
+def count_alignment_intervals_sets_device(records_by_file: Sequence[dict], chroms, starts, ends, set_ids, option_sets: Sequence[dict],
+                                          rows, out, col0: int = 0):
+    """`count_alignment_intervals_batch_device` for a contig group that is resident once: the
+    P intervals belong to ``len(option_sets)`` option sets (``set_ids[p]``; each set a dict of `count_alignment_region`'s
+    keywords) and the count of interval p in file f is stored at ``out[rows[p], col0 + f]``, in one launch series with one
+    wait.  ``out``: an int32 CUDA tensor [R, W] whose rows are contiguous; exactly the addressed cells are written (zeros
+    included), every other cell keeps its contents.  ``rows`` must be distinct and lie in [0, R); ``col0 + F <= W``.
+    Returns ``out``."""
+    import torch
+
+    F = len(records_by_file)
+    if F == 0:
+        raise ValueError("no files")
+    chrom_list, starts_h, ends_h = _check_intervals(chroms, starts, ends)
+    P, S = len(chrom_list), len(option_sets)
+    if not 1 <= S <= COUNT_INTERVALS_MAX_SETS:
+        raise ValueError(f"between 1 and {COUNT_INTERVALS_MAX_SETS} option sets are required")
+    opts = (CountOptions * S)(*[_count_options(int(o.get("read_length", 0)), **{k: v for k, v in o.items() if k != "read_length"})
+                                for o in option_sets])
+    sets_h, rows_h = np.asarray(set_ids), np.asarray(rows)
+    if sets_h.shape != (P,) or rows_h.shape != (P,):
+        raise ValueError("one set id and one row per interval are required")
+    if not _dp._is_tensor(out) or not out.is_cuda or out.dtype != torch.int32 or out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise TypeError("`out` must be a two-dimensional int32 CUDA tensor with contiguous rows")
+    col0 = int(col0)
+    if col0 < 0 or col0 + F > int(out.shape[1]):
+        raise ValueError("`col0` and the files do not fit into a row of `out`")
+    if P == 0:
+        return out
+    if sets_h.dtype.kind not in "iu" or rows_h.dtype.kind not in "iu":
+        raise TypeError("set ids and rows must hold integers")
+    if int(sets_h.min()) < 0 or int(sets_h.max()) >= S:
+        raise ValueError("a set id names no option set")
+    if int(rows_h.min()) < 0 or int(rows_h.max()) >= int(out.shape[0]):
+        raise ValueError("a row lies outside `out`")
+    if np.unique(rows_h).size != P:
+        raise ValueError("the rows of one call must be distinct")
+    contigs = list(dict.fromkeys(chrom_list))
+    for records in records_by_file:
+        for contig in contigs:
+            if contig not in records:
+                raise ValueError("chromosome not found in alignment header")
+    dev = out.device
+    C = len(contigs)
+    index = {contig: c for c, contig in enumerate(contigs)}
+    ids_h = np.fromiter((index[c] for c in chrom_list), dtype=np.int32, count=P)
+    cat, rec_offsets, dev = _record_args([records_by_file[f][contig] for f in range(F) for contig in contigs], dev=dev)
+    ids_t, starts_t, ends_t, sets_t, rows_t = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (
+        ids_h, starts_h, ends_h, sets_h.astype(np.int32), rows_h.astype(np.int64)))
+    facts = (ctypes.c_int * (2 * F * C))()
+    solver, stream = _native.solver_for(dev.index), _dp._stream_ptr(out)
+    _native.check(_native.load().rocco_hip_count_alignment_intervals_sets(
+        solver.handle, cat.pos.data_ptr(), cat.end.data_ptr(), cat.isize.data_ptr(), cat.flag.data_ptr(), cat.mapq.data_ptr(),
+        cat.mate_same.data_ptr(), rec_offsets, F, C, ctypes.cast(opts, ctypes.c_void_p), S, sets_t.data_ptr(), ids_t.data_ptr(),
+        starts_t.data_ptr(), ends_t.data_ptr(), rows_t.data_ptr(), P, out.data_ptr(), int(out.shape[0]),
+        int(out.stride(0)) if out.shape[0] > 1 else int(out.shape[1]), col0, facts, stream), "rocco_hip_count_alignment_intervals_sets")
+    for t in range(F * C):
+        if facts[2 * t + 1]:
+            raise ValueError(f"the records of file {col0 + t // C} on {contigs[t % C]} are not in coordinate order: the interval "
+                             "counter needs the file order of an indexed BAM")
+    return out
+
+
 def count_alignment_intervals_from_records(records_by_chrom: dict, chromosomes, starts, ends, **kw) -> np.ndarray:
     """The reference's ``count_alignment_intervals`` (rocco/_hts_counts.c:571-836) for one file's decoded records
     (``{contig: AlignmentRecords}``): same keyword names and defaults as `count_alignment_region_from_records`
@@ -1281,6 +1347,24 @@ def get_chroms_and_sizes(chrom_sizes_file) -> dict:
             fields = line.rstrip("\n").split("\t")
             sizes[fields[0]] = int(fields[1])
     return sizes
+
+
+def check_type_bam_files(bam_files) -> list:
+    """rocco/readtracks.py:636-652: a list of BAM paths, or a text file naming one per line; every path must exist."""
+    if isinstance(bam_files, str):
+        with open(bam_files, "r") as handle:
+            bam_files_ = [line.strip() for line in handle if line.strip()]
+        for file_ in bam_files_:
+            if not os.path.exists(file_):
+                raise FileNotFoundError(f"File in `bam_files_` not found: {file_}")
+    elif isinstance(bam_files, list):
+        bam_files_ = bam_files
+        for file_ in bam_files_:
+            if not os.path.exists(file_):
+                raise FileNotFoundError(f"File in `bam_files` not found: {file_}")
+    else:
+        raise ValueError("`bam_files` must be either a list or a path to a text file containing a list of BAM file paths.")
+    return bam_files_
 
 
 def get_bam_chrom_reads(bam_file, *_args, **_kwargs):

@@ -1257,20 +1257,24 @@ def _run_chromosomes_sharded(chroms_to_process: list, signal_inputs, args: dict,
     return args["output"]
 
 
-def run_chromosomes(chroms_to_process: list, signal_inputs, args: dict, run_id: Optional[str] = None, group=None) -> str:
-    """What the reference's `main` does between its argument parsing and its narrowPeak step (rocco/rocco.py:1269-1300):
-    cache -> pooled budgets -> solve -> combined BED at `args["output"]`; the per-chromosome files are removed.  Returns
-    the path of the combined BED.  Inside an initialised torch.distributed job of more than one rank the chromosomes are
-    sharded over the ranks (`_run_chromosomes_sharded`: same file, written by rank 0); `run_id` must then be given, the
-    same on every rank.  (`rocco_amd.pipeline.solve_rank` is the multi-GPU form with user-given budgets.)"""
-    import uuid
+def _cleanup_narrowpeak_tempfiles(chrom_cache: dict) -> None:
+    """rocco/rocco.py:875-887: the summit tracks of the cache are temporary files."""
+    for chrom_data in chrom_cache.values():
+        summit_track_file = chrom_data.pop("summit_track_file", None)
+        if summit_track_file is not None:
+            try:
+                os.remove(summit_track_file)
+            except OSError as exc:
+                logger.info("Could not remove narrowPeak summit temp. file %s\n%s", summit_track_file, exc)
 
-    run_id = str(int(uuid.uuid4().hex[:5], base=16)) if run_id is None else str(run_id)
-    this = globals()
-    if _world_size(group) > 1:
-        return _run_chromosomes_sharded(chroms_to_process, signal_inputs, args, run_id, group)
+
+def _run_to_combined_bed(chroms_to_process: list, signal_inputs, args: dict, run_id: str) -> Tuple[str, dict]:
+    """rocco/rocco.py:1269-1300 in one process: cache -> pooled budgets -> solve -> combined BED at `args["output"]`; the
+    per-chromosome files are removed.  Returns (the path of the combined BED, the cache with its summit tracks still on
+    disk: the caller removes them, `_cleanup_narrowpeak_tempfiles`)."""
     import time as _time
 
+    this = globals()
     phases = args.get("_phase_seconds")
     t0 = _time.perf_counter()
     chrom_cache = this["_build_chrom_cache"](chroms_to_process, signal_inputs, args)
@@ -1288,14 +1292,89 @@ def run_chromosomes(chroms_to_process: list, signal_inputs, args: dict, run_id: 
             os.remove(tmp_file)
         except OSError as exc:
             logger.info("Could not remove chromosome-specific temp. file %s\n%s", tmp_file, exc)
-    for chrom_data in chrom_cache.values():  # rocco/rocco.py:875-887
-        summit_track_file = chrom_data.pop("summit_track_file", None)
-        if summit_track_file is not None:
-            try:
-                os.remove(summit_track_file)
-            except OSError as exc:
-                logger.info("Could not remove narrowPeak summit temp. file %s\n%s", summit_track_file, exc)
+    return final_output, chrom_cache
+
+
+def _new_run_id(run_id: Optional[str]) -> str:
+    import uuid
+
+    return str(int(uuid.uuid4().hex[:5], base=16)) if run_id is None else str(run_id)
+
+
+def run_chromosomes(chroms_to_process: list, signal_inputs, args: dict, run_id: Optional[str] = None, group=None) -> str:
+    """What the reference's `main` does between its argument parsing and its narrowPeak step (rocco/rocco.py:1269-1300):
+    cache -> pooled budgets -> solve -> combined BED at `args["output"]`; the per-chromosome files are removed.  Returns
+    the path of the combined BED.  Inside an initialised torch.distributed job of more than one rank the chromosomes are
+    sharded over the ranks (`_run_chromosomes_sharded`: same file, written by rank 0); `run_id` must then be given, the
+    same on every rank.  (`rocco_amd.pipeline.solve_rank` is the multi-GPU form with user-given budgets;
+    `run_to_narrowpeak` goes on to the narrowPeak step.)"""
+    run_id = _new_run_id(run_id)
+    if _world_size(group) > 1:
+        return _run_chromosomes_sharded(chroms_to_process, signal_inputs, args, run_id, group)
+    final_output, chrom_cache = _run_to_combined_bed(chroms_to_process, signal_inputs, args, run_id)
+    _cleanup_narrowpeak_tempfiles(chrom_cache)
     return final_output
+
+
+def narrowpeak_sidecar_root(final_output: str) -> str:
+    """rocco/rocco.py:1213-1217: the name the ``.narrowPeak`` and ``.counts.tsv`` files hang on -- ``final_output`` without a
+    ``.bed`` extension (in any letter case), else ``final_output`` itself."""
+    output_root, output_ext = os.path.splitext(final_output)
+    return output_root if output_ext.lower() == ".bed" else final_output
+
+
+def generate_narrowpeak_if_requested(args: dict, final_output: str, chrom_cache: dict) -> Optional[str]:
+    """``_generate_narrowpeak_if_requested`` (rocco/rocco.py:1199-1255): the post-hoc scores of the combined BED's peaks over
+    the BAM inputs (`rocco_amd.scores.score_peaks`), written to ``<root>.narrowPeak`` with the count matrix beside it at
+    ``<root>.counts.tsv`` (`narrowpeak_sidecar_root`).  Nothing happens unless ``args["narrowPeak"]``; BAM inputs are
+    required; a failure is logged, not raised, as in the reference.  Returns the narrowPeak path, or None."""
+    import tempfile
+
+    from . import scores as posthoc_scores
+
+    if not args["narrowPeak"]:
+        return None
+    if args.get("input_track_type") != "bam":
+        logger.info("Skipping narrowPeak generation because posthoc peak scoring requires BAM inputs.")
+        return None
+    summit_offsets_file, written = None, None
+    try:
+        sidecar_root = narrowpeak_sidecar_root(final_output)
+        narrowpeak_filepath = f"{sidecar_root}.narrowPeak"
+        fd, summit_offsets_file = tempfile.mkstemp(prefix="rocco_pointsource_", suffix=".tsv")
+        os.close(fd)
+        _write_narrowpeak_summit_offsets(final_output, chrom_cache, summit_offsets_file)
+        posthoc_scores.score_peaks(args["input_files"], args["chrom_sizes_file"], final_output,
+                                   count_matrix_file=f"{sidecar_root}.counts.tsv", output_file=narrowpeak_filepath,
+                                   ecdf_nsamples=args["ecdf_samples"], seed=args["ecdf_seed"], proc=args["ecdf_proc"],
+                                   summit_offsets_file=summit_offsets_file)
+        logger.info("Final narrowPeak output: %s", narrowpeak_filepath)
+        written = narrowpeak_filepath
+    except Exception as exc:
+        logger.info("\nCould not generate narrowPeak-formatted output\n%s", exc)
+    finally:
+        if summit_offsets_file is not None:
+            try:
+                os.remove(summit_offsets_file)
+            except Exception as exc:
+                logger.info("Could not remove narrowPeak pointSource temp. file %s\n%s", summit_offsets_file, exc)
+    return written
+
+
+def run_to_narrowpeak(chroms_to_process: list, signal_inputs, args: dict, run_id: Optional[str] = None) -> Tuple[str, Optional[str]]:
+    """What the reference's `main` does from `_build_chrom_cache` to its end (rocco/rocco.py:1269-1305): `run_chromosomes`'
+    steps, then `generate_narrowpeak_if_requested` over the cache's summit tracks, then their removal.  Returns (the
+    combined BED, the narrowPeak path or None).  The narrowPeak step is single-process: inside a torch.distributed job of
+    more than one rank this is a ValueError."""
+    if _world_size() > 1:
+        raise ValueError("run_to_narrowpeak: the narrowPeak step is single-process; run it outside the torch.distributed job "
+                         "(run_chromosomes shards the steps before it)")
+    final_output, chrom_cache = _run_to_combined_bed(chroms_to_process, signal_inputs, args, _new_run_id(run_id))
+    try:
+        narrowpeak = generate_narrowpeak_if_requested(args, final_output, chrom_cache)
+    finally:
+        _cleanup_narrowpeak_tempfiles(chrom_cache)
+    return final_output, narrowpeak
 
 
 # --------------------------------------------------------------------------------------------

@@ -7,12 +7,17 @@
 * the counting itself for records already decoded (interval_count.hip): reads per peak per
   file (`raw_count_matrix_from_records`, rocco/scores.py:250-341), reads per random background region per file
   (`get_ecdf_from_records` / `multi_ecdf_from_records`, rocco/scores.py:642-785) and the composition
-  (`score_peaks_from_records`, rocco/scores.py:381-639).  BAM decoding and the whole-file probes (mapped reads, read
-  length) stay with the reader.
+  (`score_peaks_from_records`, rocco/scores.py:381-639), for a caller that brings the records and the whole-file facts
+  (mapped reads, read length);
+* the same functions over BAM paths under the reference's names and signatures:
+  `raw_count_matrix`, `get_read_length`, `score_peaks`, `get_ecdf`, `multi_ecdf`.  Files come from
+  `rocco_amd.bam._cached_file`, the whole-file facts from the index statistics and decoded heads, and the counting goes
+  contig group by contig group (`_count_paths`), peaks and null regions of a group in one call.
 """
 from __future__ import annotations
 
 import ctypes
+import logging
 import os
 from collections import OrderedDict
 from typing import Callable, Dict, Optional, Sequence
@@ -20,8 +25,11 @@ from typing import Callable, Dict, Optional, Sequence
 import numpy as np
 
 from . import _native
+from . import bam as _bam
 from . import dp as _dp
 from . import readtracks as _readtracks
+
+logger = logging.getLogger(__name__)
 
 
 class EmpiricalNull:
@@ -253,6 +261,20 @@ def _interval_counts_device(records_by_file: Sequence[dict], chroms, starts, end
     return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
 
 
+def _reference_count_matrix(counts: np.ndarray) -> np.ndarray:
+    """The reference's float32 per interval is min(count, 2**24); np.rint(...).astype(np.int64) of it."""
+    return np.minimum(counts, _readtracks.EXACT_COUNT_LIMIT).astype(np.int64)
+
+
+def _write_count_matrix(output_file: str, sample_names: Sequence[str], peak_names: Sequence[str], count_matrix: np.ndarray) -> str:
+    """The TSV of rocco/scores.py:333-339: header ``peak_name`` + samples, one row of integer counts per peak."""
+    with open(output_file, "w", encoding="utf-8") as handle:
+        handle.write("peak_name\t" + "\t".join(str(name) for name in sample_names) + "\n")
+        for peak_idx, peak_name in enumerate(peak_names):
+            handle.write(f"{peak_name}\t" + "\t".join(str(int(value)) for value in count_matrix[peak_idx]) + "\n")
+    return output_file
+
+
 def raw_count_matrix_from_records(records_by_file: Sequence[dict], sample_names: Sequence[str], peak_file: str, output_file: str,
                                   bed_columns: int = 3, files_per_call: Optional[int] = None) -> str:
     """``raw_count_matrix`` (rocco/scores.py:250-341) for decoded records: ``records_by_file[f]`` is ``{contig:
@@ -265,15 +287,9 @@ def raw_count_matrix_from_records(records_by_file: Sequence[dict], sample_names:
     if len(peak_names) == 0:
         raise ValueError("Peak file does not contain any intervals.")
     counts = _interval_counts_device(records_by_file, chroms, starts, ends, files_per_call, **RAW_COUNT_OPTIONS).cpu().numpy()
-    # the reference's float32 per interval is min(count, 2**24); np.rint(...).astype(np.int64) of it
-    count_matrix = np.minimum(counts, _readtracks.EXACT_COUNT_LIMIT).astype(np.int64)
     if output_file is not None and os.path.exists(output_file):
         os.remove(output_file)
-    with open(output_file, "w", encoding="utf-8") as handle:
-        handle.write("peak_name\t" + "\t".join(str(name) for name in sample_names) + "\n")
-        for peak_idx, peak_name in enumerate(peak_names):
-            handle.write(f"{peak_name}\t" + "\t".join(str(int(value)) for value in count_matrix[peak_idx]) + "\n")
-    return output_file
+    return _write_count_matrix(output_file, sample_names, peak_names, _reference_count_matrix(counts))
 
 
 def _scaling_constants(sample_scaling_constants, F: int) -> np.ndarray:
@@ -325,12 +341,22 @@ def multi_ecdf_from_records(records_by_file: Sequence[dict], lengths, chrom_size
     counting call."""
     np.random.seed(seed)  # (as the reference, :757)
     constants = _scaling_constants(sample_scaling_constants, len(records_by_file))
-    uniq_lengths = np.unique(lengths)
-    per_length = [_random_intervals(chrom_sizes_file, length=int(length), nsamples=int(nsamples_per_length), seed=seed)
-                  for length in uniq_lengths]
+    uniq_lengths, per_length = _null_intervals(lengths, chrom_sizes_file, nsamples_per_length, seed)
     everything = [interval for intervals in per_length for interval in intervals]
     counts_t = _interval_counts_device(records_by_file, [i[0] for i in everything], [i[1] for i in everything],
                                        [i[2] for i in everything], files_per_call, **NULL_COUNT_OPTIONS)
+    return _nulls_by_length(counts_t, uniq_lengths, per_length, constants, null_stat, row_scale, pc)
+
+
+def _null_intervals(lengths, chrom_sizes_file: str, nsamples_per_length, seed):
+    """(the unique representative lengths, the random regions `get_ecdf` draws for each of them)"""
+    uniq_lengths = np.unique(lengths)
+    return uniq_lengths, [_random_intervals(chrom_sizes_file, length=int(length), nsamples=int(nsamples_per_length), seed=seed)
+                          for length in uniq_lengths]
+
+
+def _nulls_by_length(counts_t, uniq_lengths, per_length, constants, null_stat, row_scale, pc) -> "OrderedDict":
+    """One `EmpiricalNull` per length from the [regions of all lengths, F] counts, the lengths' regions one behind the other."""
     out, at = OrderedDict(), 0
     for length, intervals in zip(uniq_lengths, per_length):
         out[length] = _nulls_from_counts(counts_t[at: at + len(intervals)], length, constants, null_stat, 0.0, row_scale, pc)
@@ -347,6 +373,48 @@ def _read_count_matrix(count_matrix_file: str) -> np.ndarray:
         return np.array([[int(cell) for cell in row] for row in rows], dtype=np.int64)
     except ValueError:
         return np.array([[float(cell) for cell in row] for row in rows], dtype=np.float64)
+
+
+def _scale_count_matrix(matrix_: np.ndarray, n_peaks: int, F: int, chrom_sizes_file, effective_genome_size, skip_for_norm,
+                        mapped_counts, read_lengths) -> np.ndarray:
+    """rocco/scores.py:499-533: the sample scaling constants, and the matrix scaled IN PLACE in its own dtype (NumPy casts
+    the float64 products back: truncation toward zero for the int64 matrix pandas read).  Returns the constants."""
+    if matrix_.shape != (n_peaks, F):
+        raise ValueError("the count matrix does not hold one row per peak and one column per file")
+    if effective_genome_size is None:
+        effective_genome_size = np.sum([x[1] for x in _readtracks.get_chroms_and_sizes(chrom_sizes_file).items()
+                                        if x[0] not in skip_for_norm])
+    mapped_sizes = np.asarray(mapped_counts, dtype=int) * np.asarray(read_lengths, dtype=int)
+    sample_scaling_constants = (effective_genome_size) / mapped_sizes
+    for sample_idx in range(F):
+        matrix_[:, sample_idx] = matrix_[:, sample_idx] * sample_scaling_constants[sample_idx]
+    return sample_scaling_constants
+
+
+def _read_summit_offsets(summit_offsets_file: Optional[str]) -> dict:
+    """rocco/scores.py:595-607."""
+    summit_offsets = {}
+    if summit_offsets_file is not None:
+        with open(summit_offsets_file, encoding="utf-8") as handle:
+            for line_num, line in enumerate(handle, start=1):
+                line_ = line.strip()
+                if line_ == "":
+                    continue
+                fields = line_.split("\t")
+                if len(fields) < 2:
+                    raise ValueError(f"Summit offset row {line_num} in {summit_offsets_file} has fewer than 2 columns.")
+                summit_offsets[str(fields[0])] = int(fields[1])
+    return summit_offsets
+
+
+def _score_and_write(matrix_, lengths, binned_lengths, ecdf_dict, bed_strings, names, row_scale, pc, ucsc_base,
+                     summit_offsets_file, output_file):
+    """rocco/scores.py:564-639 from the scaled matrix and the nulls: (signal values, UCSC scores, p-values); writes
+    ``output_file``."""
+    scored = score_peak_counts(matrix_.astype(np.float64), lengths, binned_lengths, ecdf_dict, row_scale=row_scale, pc=pc,
+                               ucsc_base=ucsc_base)
+    write_scored_peaks(bed_strings, names, lengths, scored, output_file, _read_summit_offsets(summit_offsets_file))
+    return scored["signal"], scored["bed6_scores"], scored["pvals"]
 
 
 def score_peaks_from_records(records_by_file: Sequence[dict], sample_names: Sequence[str], chrom_sizes_file: str, peak_file: str,
@@ -372,41 +440,361 @@ def score_peaks_from_records(records_by_file: Sequence[dict], sample_names: Sequ
         if len(names) == 0:
             raise ValueError("Peak file does not contain any intervals.")
         counts = _interval_counts_device(records_by_file, chroms, starts, ends, files_per_call, **RAW_COUNT_OPTIONS).cpu().numpy()
-        matrix_ = np.minimum(counts, _readtracks.EXACT_COUNT_LIMIT).astype(np.int64)
+        matrix_ = _reference_count_matrix(counts)
         if count_matrix_file is not None:
-            with open(count_matrix_file, "w", encoding="utf-8") as handle:
-                handle.write("peak_name\t" + "\t".join(str(name) for name in sample_names) + "\n")
-                for peak_idx, peak_name in enumerate(names):
-                    handle.write(f"{peak_name}\t" + "\t".join(str(int(value)) for value in matrix_[peak_idx]) + "\n")
+            _write_count_matrix(count_matrix_file, sample_names, names, matrix_)
     lengths = np.asarray([end - start for start, end in zip(starts, ends)], dtype=np.float64)
-    if matrix_.shape != (len(names), F):
-        raise ValueError("the count matrix does not hold one row per peak and one column per file")
-    if effective_genome_size is None:
-        effective_genome_size = np.sum([x[1] for x in _readtracks.get_chroms_and_sizes(chrom_sizes_file).items()
-                                        if x[0] not in skip_for_norm])
-    mapped_sizes = np.asarray(mapped_counts, dtype=int) * np.asarray(read_lengths, dtype=int)
-    sample_scaling_constants = (effective_genome_size) / mapped_sizes
-    for sample_idx in range(F):
-        # NumPy casts the float64 products back into the matrix's own dtype: truncation toward zero for int64 (:530-533)
-        matrix_[:, sample_idx] = matrix_[:, sample_idx] * sample_scaling_constants[sample_idx]
+    sample_scaling_constants = _scale_count_matrix(matrix_, len(names), F, chrom_sizes_file, effective_genome_size, skip_for_norm,
+                                                   mapped_counts, read_lengths)
     binned_lengths, ecdf_lengths = _assign_length_bins(lengths, max_bins=ecdf_max_length_bins)
     if seed is None:
         seed = np.random.randint(1, 10000)
     ecdf_dict = multi_ecdf_from_records(records_by_file, ecdf_lengths, chrom_sizes_file, nsamples_per_length=ecdf_nsamples,
                                         sample_scaling_constants=sample_scaling_constants, seed=seed, row_scale=row_scale, pc=pc,
                                         files_per_call=files_per_call)
-    scored = score_peak_counts(matrix_.astype(np.float64), lengths, binned_lengths, ecdf_dict, row_scale=row_scale, pc=pc,
-                               ucsc_base=ucsc_base)
-    summit_offsets = {}
-    if summit_offsets_file is not None:
-        with open(summit_offsets_file, encoding="utf-8") as handle:
-            for line_num, line in enumerate(handle, start=1):
-                line_ = line.strip()
-                if line_ == "":
-                    continue
-                fields = line_.split("\t")
-                if len(fields) < 2:
-                    raise ValueError(f"Summit offset row {line_num} in {summit_offsets_file} has fewer than 2 columns.")
-                summit_offsets[str(fields[0])] = int(fields[1])
-    write_scored_peaks(bed_strings, names, lengths, scored, output_file, summit_offsets)
-    return scored["signal"], scored["bed6_scores"], scored["pvals"]
+    return _score_and_write(matrix_, lengths, binned_lengths, ecdf_dict, bed_strings, names, row_scale, pc, ucsc_base,
+                            summit_offsets_file, output_file)
+
+
+# --------------------------------------------------------------------------------------------
+# the same functions over BAM paths (note (33)): the reference's signatures
+# --------------------------------------------------------------------------------------------
+
+# Decoded records of one contig group, summed over the files, at 20 bytes per record (the alignment cache's measure).  Half
+# of the cache's budget, so that a group and the copy the counter takes of it fit together: a choice, not a measurement
+# (DESIGN.md note (33)).
+GROUP_BYTES = _bam.ALIGNMENT_CACHE_BYTES // 2
+_DEFAULT_SKIP_FOR_NORM = ["chrX", "chrY", "chrM"]
+
+
+def _contig_groups(contigs: Sequence[str], costs: Sequence[Optional[int]], budget: int) -> list:
+    """Runs of ``contigs`` (kept in their order) whose costs add up to ``budget`` at most; a contig above the budget, or of
+    unknown cost (None), is a group of its own."""
+    groups, run, total = [], [], 0
+    for contig, cost in zip(contigs, costs):
+        alone = cost is None or int(cost) > budget
+        if run and (alone or total + int(cost) > budget):
+            groups.append(run)
+            run, total = [], 0
+        if alone:
+            groups.append([contig])
+            continue
+        run.append(contig)
+        total += int(cost)
+    if run:
+        groups.append(run)
+    return groups
+
+
+def _sample_names(bam_files: Sequence[str]) -> list:
+    """rocco/scores.py:291-296: the base name without ``.bam``."""
+    samples = []
+    for bam in bam_files:
+        name = os.path.basename(bam)
+        if name.endswith(".bam"):
+            name = name[:-4]
+        samples.append(name)
+    return samples
+
+
+def _open_files(bam_files) -> tuple:
+    bam_files_ = _readtracks.check_type_bam_files(bam_files)
+    return bam_files_, [_bam._cached_file(path) for path in bam_files_]
+
+
+def _known_records(file, contig: str) -> Optional[int]:
+    """The records of a contig by what is known without decoding: ``count(contig)`` of an indexed file (None where the index
+    has no statistics for it), the track length of a resident file."""
+    count = getattr(file, "count", None)
+    return count(contig) if count is not None else len(file.records[contig])
+
+
+def _count_paths(files: Sequence, families: Sequence[tuple], files_per_call: Optional[int] = None):
+    """int32 CUDA tensor [P_total, F]: the counts of one or two interval families over the files (`_cached_file`), rows in
+    the caller's order (the families one behind the other).  ``families[s] = (chroms, starts, ends, options)``.  The pass
+    goes contig group by contig group (`_contig_groups` under `GROUP_BYTES`): a group's (file, contig) pairs are fetched
+    with ONE `_load_contigs` call and counted with ONE `count_alignment_intervals_sets_device` call per column group of
+    ``files_per_call`` files (all files by default), every family under its own option set, into the final rows.  Contigs
+    without intervals are never decoded; a file without an index is resident as a whole and goes through the same call."""
+    import torch
+
+    F = len(files)
+    if F == 0:
+        raise ValueError("no files")
+    if files_per_call is None:
+        per_call = F
+    else:
+        per_call = int(files_per_call)
+        if per_call < 1:
+            raise ValueError("`files_per_call` must be at least 1")
+    chroms, starts, ends, sets = [], [], [], []
+    for s, (chroms_s, starts_s, ends_s, _) in enumerate(families):
+        chroms_s, starts_s, ends_s = _readtracks._check_intervals(chroms_s, starts_s, ends_s)
+        chroms += chroms_s
+        starts.append(starts_s)
+        ends.append(ends_s)
+        sets.append(np.full(len(chroms_s), s, dtype=np.int32))
+    option_sets = [dict(family[3]) for family in families]
+    starts_h, ends_h, sets_h = np.concatenate(starts), np.concatenate(ends), np.concatenate(sets)
+    chroms_h = np.asarray(chroms, dtype=object)
+    P = len(chroms)
+    wanted = list(dict.fromkeys(chroms))
+    for file in files:
+        for contig in wanted:
+            if contig not in file.records:
+                raise ValueError("chromosome not found in alignment header")
+    dev = _dp._device(None)
+    out = torch.empty((P, F), dtype=torch.int32, device=dev)  # (every cell is addressed by exactly one call)
+    if P == 0:
+        return out
+    header_order = {name: k for k, (name, _) in enumerate(files[0].contigs)}
+    wanted.sort(key=lambda contig: header_order[contig])
+    costs = []
+    for contig in wanted:
+        counts = [_known_records(file, contig) for file in files]
+        costs.append(None if any(c is None for c in counts) else 20 * int(sum(counts)))
+    indexed = [f for f, file in enumerate(files) if isinstance(file, _bam.IndexedAlignmentFile)]
+    for group in _contig_groups(wanted, costs, int(GROUP_BYTES)):
+        records = [dict() for _ in range(F)]
+        if indexed:
+            pairs = [(files[f], contig) for f in indexed for contig in group]
+            for (file_, contig), track in zip(((f, c) for f in indexed for c in group), _bam._load_contigs(pairs)):
+                records[file_][contig] = track
+        for f in range(F):
+            if f not in indexed:
+                records[f] = {contig: files[f].records[contig] for contig in group}
+        rows = np.flatnonzero(np.isin(chroms_h, group))
+        for f0 in range(0, F, per_call):
+            _readtracks.count_alignment_intervals_sets_device(records[f0: f0 + per_call], chroms_h[rows].tolist(), starts_h[rows],
+                                                              ends_h[rows], sets_h[rows], option_sets, rows, out, col0=f0)
+    return out
+
+
+def _peak_family(chroms, starts, ends) -> tuple:
+    return (chroms, starts, ends, RAW_COUNT_OPTIONS)
+
+
+def _null_family(intervals) -> tuple:
+    return ([i[0] for i in intervals], [i[1] for i in intervals], [i[2] for i in intervals], NULL_COUNT_OPTIONS)
+
+
+def _log_count_matrix_start(sample_names, n_peaks: int, bam_files) -> None:
+    """The INFO lines of rocco/scores.py:297-313 (the reference counts file by file; here all files are one pass)."""
+    header = "peak_name\t" + "\t".join(sample_names)
+    logger.info(f"\n\nCount matrix header: {header}\n\n")
+    logger.info("Counting %s peak regions across %s alignments.", int(n_peaks), int(len(bam_files)))
+    for sample_idx, bam_file in enumerate(bam_files):
+        logger.info("Counting sample %s of %s: %s", sample_idx + 1, len(bam_files), bam_file)
+
+
+def _finish_count_matrix(output_file: str, sample_names, peak_names, counts_t) -> np.ndarray:
+    """rocco/scores.py:325-341 from the device counts: the int64 matrix, written to ``output_file``."""
+    count_matrix = _reference_count_matrix(counts_t.cpu().numpy())
+    if output_file is not None and os.path.exists(output_file):
+        logger.warning(f"{output_file} already exists...overwriting.")
+        os.remove(output_file)
+    _write_count_matrix(output_file, sample_names, peak_names, count_matrix)
+    logger.info("Count matrix written to %s", output_file)
+    return count_matrix
+
+
+def raw_count_matrix(bam_files, peak_file: str, output_file: str, bed_columns: int = 3, overwrite=True,
+                     files_per_call: Optional[int] = None) -> str:
+    """``raw_count_matrix`` (rocco/scores.py:250-341) over BAM paths: a list of paths or a text file naming them.  Returns
+    ``output_file``.  (``overwrite`` is accepted and, as in the reference, not read.)"""
+    bam_files_, files = _open_files(bam_files)
+    chroms, starts, ends, _, peak_names = _read_peak_intervals(peak_file, min_columns=bed_columns)
+    if len(peak_names) == 0:
+        raise ValueError("Peak file does not contain any intervals.")
+    samples = _sample_names(bam_files_)
+    _log_count_matrix_start(samples, len(peak_names), bam_files_)
+    counts_t = _count_paths(files, [_peak_family(chroms, starts, ends)], files_per_call)
+    _finish_count_matrix(output_file, samples, peak_names, counts_t)
+    return output_file
+
+
+def _qualifies_for_read_length(flag: np.ndarray, mapq: np.ndarray, min_mapping_quality: int) -> np.ndarray:
+    """rocco/scores.py:366-374: not unmapped, secondary or supplementary, and mapping quality at least the floor."""
+    return ((np.asarray(flag).astype(np.int64) & (4 | 256 | 2048)) == 0) & (np.asarray(mapq).astype(np.int64) >= int(min_mapping_quality))
+
+
+def _read_length_value(lengths: np.ndarray, name: str) -> int:
+    """``int(np.percentile(read_lengths, 75))`` (rocco/scores.py:378) of the ``qlen`` taken.  pysam's ``infer_query_length()``
+    is None for a query length of zero, and the list may be empty: NumPy refuses both, and the exception keeps its type
+    with a message that names the file."""
+    taken = [int(v) if int(v) != 0 else None for v in np.asarray(lengths).tolist()]
+    try:
+        return int(np.percentile(taken, 75))
+    except Exception as error:
+        why = "no read qualifies" if len(taken) == 0 else "a qualifying read has no query length (no CIGAR)"
+        raise type(error)(f"get_read_length: {name}: {why}: {error}") from error
+
+
+def read_length_from_fields(flag, mapq, qlen, num_reads: int = 1000, min_mapping_quality: int = 10, name: str = "") -> int:
+    """`get_read_length` as a function of the records' fields in the order ``fetch()`` yields them (the header's contigs one
+    behind the other, every contig in the index iterator's order)."""
+    keep = _qualifies_for_read_length(flag, mapq, min_mapping_quality)
+    return _read_length_value(np.asarray(qlen)[keep][: max(int(num_reads), 1)], name)
+
+
+def _read_lengths(files: Sequence, num_reads: int = 1000, min_mapping_quality: int = 10) -> list:
+    """`get_read_length` of every file.  An indexed file is read contig by contig in header order until ``num_reads``
+    records qualify; per turn the next non-empty contig of EVERY file that is still short is fetched, in ONE `_load_contigs`
+    call.  Of a contig the probe downloads a head (`_head_chunks`), not whole arrays."""
+    quota = max(int(num_reads), 1)  # (the reference appends, then tests ``>= num_reads``: at least one read is taken)
+    taken = [[] for _ in files]
+    have = [0] * len(files)
+
+    def probe(f, tracks):
+        for chunk in _readtracks._head_chunks(tracks, ("flag", "mapq", "qlen"), first=max(quota, 1024)):
+            good = chunk["qlen"][_qualifies_for_read_length(chunk["flag"], chunk["mapq"], min_mapping_quality)][: quota - have[f]]
+            taken[f].append(good)
+            have[f] += good.size
+            if have[f] >= quota:
+                return
+
+    cursors = {}
+    for f, file in enumerate(files):
+        if isinstance(file, _bam.IndexedAlignmentFile):
+            cursors[f] = iter([name for name, _ in file.contigs if file.count(name) != 0])
+        else:
+            tracks = file.tracks()
+            _readtracks._need_qlen(file, tracks, "get_read_length")
+            probe(f, tracks)
+    while cursors:
+        turn = []
+        for f in list(cursors):
+            contig = next(cursors[f], None) if have[f] < quota else None
+            if contig is None:
+                del cursors[f]
+            else:
+                turn.append((f, contig))
+        if turn:
+            for (f, contig), records in zip(turn, _bam._load_contigs([(files[f], contig) for f, contig in turn])):
+                probe(f, [(contig, records)])
+    return [_read_length_value(np.concatenate(t) if t else np.zeros(0, dtype=np.int32), file.name) for t, file in zip(taken, files)]
+
+
+def get_read_length(bam_file: str, num_reads: int = 1000, min_mapping_quality: int = 10) -> int:
+    """``get_read_length`` (rocco/scores.py:344-378): the 75th percentile of the query lengths of the first ``num_reads``
+    records of ``fetch()`` that are mapped, primary and of mapping quality ``min_mapping_quality`` at least."""
+    return _read_lengths([_bam._cached_file(bam_file)], num_reads, min_mapping_quality)[0]
+
+
+def _mapped_reads(file) -> int:
+    """pysam's ``AlignmentFile.mapped``: the index statistics summed over all contigs; for a file without an index, or
+    without statistics, the ``flag & 4 == 0`` count of its decoded records."""
+    from_index = getattr(file, "index_read_counts", None)
+    counted = from_index() if from_index is not None else None
+    if counted is not None:
+        return int(counted[0])
+    tracks = file.tracks()
+    if isinstance(tracks, list):  # (a resident file: one launch over its contigs)
+        return int(sum(_readtracks.record_flag_facts_device([records for _, records in tracks])[0])) if tracks else 0
+    return int(sum(_readtracks.record_flag_facts_device([records])[0][0] for _, records in tracks))  # (decoded contig by contig)
+
+
+def _contig_count(file, contig: str) -> int:
+    """pysam's ``AlignmentFile.count(contig)``: the records the index iterator yields over the whole contig."""
+    if contig not in file.records:
+        raise ValueError(f"invalid contig `{contig}`")
+    known = _known_records(file, contig)
+    return int(known) if known is not None else len(file.records[contig])
+
+
+def _norm_facts(files: Sequence, skip_for_norm) -> tuple:
+    """rocco/scores.py:510-521: (mapped reads outside ``skip_for_norm``, `get_read_length`) of every file."""
+    mapped_counts = []
+    for file in files:
+        mapped = _mapped_reads(file)
+        for chrom in skip_for_norm:
+            mapped -= _contig_count(file, chrom)
+        mapped_counts.append(mapped)
+    return mapped_counts, _read_lengths(files)
+
+
+def get_ecdf(bam_files, length: int, chrom_sizes_file: str, nsamples=500, sample_scaling_constants: list = None, seed: int = None,
+             null_stat: Callable = _null_stat, trim_proportion: float = 0.0, row_scale: float = 1000.0, pc: float = 1.0,
+             files_per_call: Optional[int] = None) -> EmpiricalNull:
+    """``get_ecdf`` (rocco/scores.py:642-733) over BAM paths."""
+    _, files = _open_files(bam_files)
+    constants = _scaling_constants(sample_scaling_constants, len(files))
+    logger.info(f"Computing ECDF for representative length bin: {length} with {nsamples} samples.")
+    intervals = _random_intervals(chrom_sizes_file, length=int(length), nsamples=int(nsamples), seed=seed)
+    counts_t = _count_paths(files, [_null_family(intervals)], files_per_call)
+    return _nulls_from_counts(counts_t, length, constants, null_stat, trim_proportion, row_scale, pc)
+
+
+def multi_ecdf(bam_files, lengths, chrom_sizes_file: str, nsamples_per_length, sample_scaling_constants=None, seed=None,
+               proc: int = None, null_stat: Callable = _null_stat, row_scale: float = 1000.0, pc: float = 1.0,
+               files_per_call: Optional[int] = None) -> "OrderedDict":
+    """``multi_ecdf`` (rocco/scores.py:741-785) over BAM paths: the regions of all lengths in one counting pass (``proc`` is
+    accepted and ignored: the reference's pool runs one `get_ecdf` per length)."""
+    np.random.seed(seed)
+    _, files = _open_files(bam_files)
+    constants = _scaling_constants(sample_scaling_constants, len(files))
+    uniq_lengths, per_length = _null_intervals(lengths, chrom_sizes_file, nsamples_per_length, seed)
+    for length in uniq_lengths:
+        logger.info(f"Computing ECDF for representative length bin: {length} with {nsamples_per_length} samples.")
+    everything = [interval for intervals in per_length for interval in intervals]
+    counts_t = _count_paths(files, [_null_family(everything)], files_per_call)
+    return _nulls_by_length(counts_t, uniq_lengths, per_length, constants, null_stat, row_scale, pc)
+
+
+def score_peaks(bam_files, chrom_sizes_file: str = None, peak_file: str = None, count_matrix_file: str = None,
+                effective_genome_size: float = None, skip_for_norm: list = _DEFAULT_SKIP_FOR_NORM, row_scale=1000, ucsc_base=250,
+                threads: int = None, pc=1, ecdf_nsamples=500, ecdf_max_length_bins: int = 24, output_file="scored_peaks.bed",
+                seed: int = None, proc: int = None, null_stat: Callable = _null_stat, summit_offsets_file: Optional[str] = None,
+                files_per_call: Optional[int] = None):
+    """``score_peaks`` (rocco/scores.py:381-639) over BAM paths; ``threads`` and ``proc`` are accepted and ignored.  The
+    peaks (when ``count_matrix_file`` does not exist yet) and the random regions of every length bin are counted in ONE
+    pass over the files: every contig group is decoded once and counted once, the peaks at `RAW_COUNT_OPTIONS` and the
+    regions at `NULL_COUNT_OPTIONS`.  With an existing matrix file only the regions are counted.  The reference's log lines
+    are emitted in its order, behind that pass.  As in the reference, the nulls always use the default statistic
+    (``null_stat`` is not handed on, :552-562).  Returns (signal values, UCSC scores, p-values) and writes ``output_file``."""
+    bam_files_, files = _open_files(bam_files)
+    F = len(files)
+    chroms, starts, ends, bed_strings, names = _read_peak_intervals(peak_file, min_columns=3)
+    have_matrix = count_matrix_file is not None and os.path.exists(count_matrix_file)
+    if not have_matrix and len(names) == 0:
+        raise ValueError("Peak file does not contain any intervals.")
+    lengths = np.asarray([end - start for start, end in zip(starts, ends)], dtype=np.float64)
+    binned_lengths, ecdf_lengths = _assign_length_bins(lengths, max_bins=ecdf_max_length_bins)
+    drawn = seed is None
+    if drawn:
+        seed = np.random.randint(1, 10000)
+    np.random.seed(seed)  # (multi_ecdf, :757)
+    uniq_lengths, per_length = _null_intervals(ecdf_lengths, chrom_sizes_file, ecdf_nsamples, seed)
+    regions = [interval for intervals in per_length for interval in intervals]
+    families = ([] if have_matrix else [_peak_family(chroms, starts, ends)]) + [_null_family(regions)]
+    counts_t = _count_paths(files, families, files_per_call)
+    if have_matrix:
+        matrix_ = _read_count_matrix(count_matrix_file)
+        null_counts_t = counts_t
+    else:
+        logger.info(f"Generating count matrix from {len(bam_files_)} BAM files and {peak_file} --> {count_matrix_file}")
+        samples = _sample_names(bam_files_)
+        _log_count_matrix_start(samples, len(names), bam_files_)
+        matrix_ = counts_t[: len(names)]
+        null_counts_t = counts_t[len(names):]
+        if count_matrix_file is not None:
+            _finish_count_matrix(count_matrix_file, samples, names, matrix_)
+            matrix_ = _read_count_matrix(count_matrix_file)
+        else:
+            matrix_ = _reference_count_matrix(matrix_.cpu().numpy())
+    mapped_counts, read_lengths = _norm_facts(files, skip_for_norm)
+    constants = _scale_count_matrix(matrix_, len(names), F, chrom_sizes_file, effective_genome_size, skip_for_norm, mapped_counts,
+                                    read_lengths)
+    logger.info("Using %s ECDF length bins for %s unique peak lengths.", int(ecdf_lengths.size), int(np.unique(lengths).size))
+    if drawn:
+        logger.info(f"Using random seed: {seed} to sample length-binned regions for ECDFs.")
+    for length in uniq_lengths:
+        logger.info(f"Computing ECDF for representative length bin: {length} with {ecdf_nsamples} samples.")
+    ecdf_dict = _nulls_by_length(null_counts_t, uniq_lengths, per_length, _scaling_constants(constants, F), _null_stat,
+                                 row_scale, pc)
+    for feature_idx in range(0, len(lengths), 1000):
+        logger.info(f"Processing peak {feature_idx} of {len(lengths)}")
+    out = _score_and_write(matrix_, lengths, binned_lengths, ecdf_dict, bed_strings, names, row_scale, pc, ucsc_base,
+                           summit_offsets_file, output_file)
+    logger.info(f"Scored output: {output_file}")
+    return out
