@@ -511,6 +511,18 @@ long long rocco_hip_buffer_growths(void);
  * (row, parity, sweep) were recomputed so far.  ROCCO_HIP_WHITTAKER_SEGMENT_LOCI / ROCCO_HIP_WHITTAKER_WARM_LOCI (read
  * per call) set the segment length (0: rows are never cut) and the warm-up. */
 long long rocco_hip_whittaker_seam_repairs(void);
+/* Diagnostic: what the batched baseline entries (rocco_hip_crossfit_whittaker_baseline_batch_f64, ..._residual_batch_f64)
+ * would do NOW with matrices of rows[i] x cols[i], at the environment in force at the time of the call -- computed by
+ * the launcher's own steps (csrc/whittaker.hip: launch_crossfit_whittaker_batch), nothing is launched and no result
+ * changes.  residual: 0 for the baseline entry, 1 for the residual ones; with_offsets: non-zero when the call passes an
+ * array of row offsets (the residual entries always do).  n_seg_out[i]: the segments a row of matrix i is cut into
+ * (1: rows stay whole; 0: no sweep walks the matrix -- no rows, or fewer than 25 loci, baseline_backend.c:265-272);
+ * seg_tiles_out[i]: 64-locus tiles per segment (the last segment may be shorter).  info_out[0]: the loci a workgroup may
+ * walk (0 when ROCCO_HIP_WHITTAKER_SEGMENT_LOCI fixes the segment length); [1]: the warm-up in tiles; [2]: workgroups per
+ * sweep; [3]: the path -- 0: the lone matrix of whole rows, one workgroup per row (whittaker_sweep_kernel), 1: the grouped
+ * rows kernels with their seam checks.  With the default warm-up a row is first cut at 2 x warm-up + 1 tile. */
+int rocco_hip_whittaker_batch_plan(rocco_hip_solver *solver, size_t count, const size_t *rows, const size_t *cols, int residual,
+                                   int with_offsets, int *n_seg_out, long long *seg_tiles_out, long long *info_out);
 /* device memory the solver's scratch buffers hold now (they are kept between calls) */
 long long rocco_hip_solver_device_bytes(const rocco_hip_solver *solver);
 /* Diagnostic, process-wide since load: how the last bisection steps of the calibrations (rocco/dp.py:141-162) were

@@ -247,6 +247,9 @@ PROTOTYPES = [
       ctypes.c_double, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     ("rocco_hip_buffer_growths", ctypes.c_longlong, []),
     ("rocco_hip_whittaker_seam_repairs", ctypes.c_longlong, []),
+    ("rocco_hip_whittaker_batch_plan", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_size_t, c_size_p, c_size_p, ctypes.c_int, ctypes.c_int, c_int_p,
+      ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]),
     ("rocco_hip_model_chain_counters", None, [ctypes.POINTER(ctypes.c_longlong)]),
     ("rocco_hip_model_chain_written_counters", None, [ctypes.POINTER(ctypes.c_longlong)]),
     ("rocco_hip_solver_device_bytes", ctypes.c_longlong, [ctypes.c_void_p]),

@@ -1100,6 +1100,16 @@ long long rocco_hip_buffer_growths(void) { return g_buffer_growths.load(std::mem
 
 long long rocco_hip_whittaker_seam_repairs(void) { return whittaker_seam_repairs(); }
 
+int rocco_hip_whittaker_batch_plan(rocco_hip_solver *solver, size_t count, const size_t *rows, const size_t *cols, int residual,
+                                   int with_offsets, int *n_seg_out, long long *seg_tiles_out, long long *info_out)
+{
+    if (solver == nullptr || info_out == nullptr || (count > 0 && (rows == nullptr || cols == nullptr || n_seg_out == nullptr || seg_tiles_out == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    ROCCO_HIP_TRY(hipSetDevice(solver->device));
+    return whittaker_batch_plan(rows, cols, count, residual, with_offsets, n_seg_out, seg_tiles_out, info_out);
+}
+
 void rocco_hip_model_chain_counters(long long out[4])
 {
     if (out != nullptr) {

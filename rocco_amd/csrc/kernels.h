@@ -211,6 +211,11 @@ int whittaker_group_rows();  // rows per workgroup of the batched sweeps
 // how often a segment's warm-up had NOT reached the row's own values at the seam (each such seam was recomputed from
 // the true state: results are the sequential sweep's either way); process-wide, for tests and diagnostics
 long long whittaker_seam_repairs();
+// what launch_crossfit_whittaker_batch would do now with these shapes and flags (nothing is launched): per matrix the
+// segments per row (0: no sweep walks it) and the tiles per segment; info_out[4] = the budget in loci, the warm-up in
+// tiles, the workgroups per sweep, the path (0: whittaker_sweep_kernel per row, 1: the grouped rows kernels)
+int whittaker_batch_plan(const size_t *rows, const size_t *cols, size_t count, int residual, int with_offsets, int *n_seg_out,
+                         long long *seg_tiles_out, long long *info_out);
 // after the stream of a batch launch has been waited for; returns non-zero when a residual launch met a non-finite baseline
 int whittaker_collect_repairs(const void *tasks_host_pinned);
 // offsets_dev (may be null, entries may be null): per matrix, one value per row that the sweeps subtract from their input;

@@ -1154,6 +1154,14 @@ size_t batch_tasks_bound(const size_t *rows, const size_t *cols, size_t count)
     return n_tasks;
 }
 
+// ONE matrix of rows too short to cut, baseline form, no offsets: a workgroup per row with one chain per wavefront
+// (whittaker_sweep_kernel) steps ~25 ns per locus, the grouped wavefronts ~27 ns -- both last as long as one row, so the
+// lone matrix takes the faster step
+bool lone_matrix_takes_row_sweeps(const size_t *rows, const size_t *cols, size_t count, int residual, bool with_offsets, long long budget)
+{
+    return residual == 0 && !with_offsets && count == 1 && rows[0] > 0 && cols[0] >= 25 && plan_segments(cols[0], budget).n_seg < 2;
+}
+
 constexpr size_t kStateDoubles = 8 * kGroupRows;  // per task and sweep: spec | edge, 2 G chains x 2 values each
 
 size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
@@ -1161,6 +1169,43 @@ size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 }  // namespace
 
 long long whittaker_seam_repairs() { return g_seam_repairs.load(std::memory_order_relaxed); }
+
+// What launch_crossfit_whittaker_batch does with these shapes and flags at the environment in force now, through the
+// launcher's own steps (configure_rows_kernels, batch_budget_loci, the lone-matrix condition, plan_segments, group_rows_of);
+// nothing is launched.
+int whittaker_batch_plan(const size_t *rows, const size_t *cols, size_t count, int residual, int with_offsets, int *n_seg_out,
+                         long long *seg_tiles_out, long long *info_out)
+{
+    int rc;
+    if ((rc = configure_rows_kernels()) != ROCCO_HIP_OK) return rc;
+    const long long budget = batch_budget_loci(rows, cols, count);
+    const bool row_sweeps = lone_matrix_takes_row_sweeps(rows, cols, count, residual, with_offsets != 0, budget);
+    long long workgroups = 0, warm_tiles = cut(0, 1).warm_tiles;
+    for (size_t i = 0; i < count; ++i) {
+        n_seg_out[i] = 0;  // (no rows, or rows too short for a baseline: no sweep walks them)
+        seg_tiles_out[i] = 0;
+        if (rows[i] == 0 || cols[i] < 25) {
+            continue;
+        }
+        const SegmentPlan plan = plan_segments(cols[i], budget);
+        n_seg_out[i] = plan.n_seg;
+        seg_tiles_out[i] = plan.seg_tiles;
+        warm_tiles = plan.warm_tiles;
+        if (row_sweeps) {
+            workgroups += (long long)rows[i];
+            continue;
+        }
+        const size_t group_rows = group_rows_of(rows[i]);
+        for (size_t r0 = 0; r0 < rows[i]; r0 += group_rows) {
+            workgroups += plan.n_seg;
+        }
+    }
+    info_out[0] = budget;
+    info_out[1] = warm_tiles;
+    info_out[2] = workgroups;
+    info_out[3] = row_sweeps ? 0 : 1;
+    return ROCCO_HIP_OK;
+}
 
 // what launch_crossfit_whittaker_batch copies up from pinned memory: both sweeps' task records, the seam records, and
 // (coming back) the count of recomputed seams in the first 64 bytes
@@ -1191,9 +1236,7 @@ int launch_crossfit_whittaker_batch(const double *const *matrices_dev, const siz
     std::memset(tasks_host_pinned, 0, 64);  // (the counters whittaker_collect_repairs reads, whichever way this call goes)
     const long long seg_loci = batch_budget_loci(rows, cols, count);
     auto offsets_of = [&](size_t i) { return (offsets_dev != nullptr) ? offsets_dev[i] : (const double *)nullptr; };
-    if (residual == 0 && offsets_dev == nullptr && count == 1 && rows[0] > 0 && cols[0] >= 25 && plan_segments(cols[0], seg_loci).n_seg < 2) {
-        // ONE matrix of rows too short to cut: a workgroup per row with one chain per wavefront steps ~25 ns per locus, the
-        // grouped wavefronts below ~27 ns -- both last as long as one row, so the lone matrix takes the faster step
+    if (lone_matrix_takes_row_sweeps(rows, cols, count, residual, offsets_dev != nullptr, seg_loci)) {
         if (factor_dev == nullptr || factor_cap < cols[0]) {
             return ROCCO_HIP_EINVAL;
         }

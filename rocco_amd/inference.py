@@ -342,6 +342,29 @@ def whittaker_batch_scratch_bytes(shapes) -> int:
         count, (ctypes.c_size_t * count)(*[int(r) for r, _c in shapes]), (ctypes.c_size_t * count)(*[int(c) for _r, c in shapes])))
 
 
+def whittaker_batch_plan(shapes, residual: bool = False, with_offsets=None, device_index: int = 0) -> dict:
+    """What the batched baseline sweeps would do now with matrices of these (rows, cols) shapes, at the environment in force
+    (rocco_hip_whittaker_batch_plan: the launcher's own plan, nothing is launched).  `residual`: the plan of
+    crossfit_whittaker_residual_batch_device (which always hands an offsets array over) instead of
+    crossfit_whittaker_baseline_batch_device.  Returns n_seg and seg_tiles (64-locus tiles) per matrix, the budget in loci,
+    the warm-up in tiles, the workgroups per sweep and `grouped` (False: the lone matrix takes the per-row sweep kernel)."""
+    import ctypes
+
+    shapes = list(shapes)
+    count = len(shapes)
+    with_offsets = bool(residual) if with_offsets is None else bool(with_offsets)
+    n_seg = (ctypes.c_int * max(1, count))()
+    seg_tiles = (ctypes.c_longlong * max(1, count))()
+    info = (ctypes.c_longlong * 4)()
+    solver = _native.solver_for(device_index)
+    _native.check(_native.load().rocco_hip_whittaker_batch_plan(
+        solver.handle, count, (ctypes.c_size_t * max(1, count))(*[int(r) for r, _c in shapes]),
+        (ctypes.c_size_t * max(1, count))(*[int(c) for _r, c in shapes]), 1 if residual else 0, 1 if with_offsets else 0,
+        n_seg, seg_tiles, info), "rocco_hip_whittaker_batch_plan")
+    return {"n_seg": [int(v) for v in n_seg[:count]], "seg_tiles": [int(v) for v in seg_tiles[:count]],
+            "budget_loci": int(info[0]), "warm_tiles": int(info[1]), "workgroups": int(info[2]), "grouped": bool(info[3])}
+
+
 def crossfit_whittaker_residual_batch_device(values_list, offsets_list, penalty_lambda: float, outs=None, scratch=None):
     """rocco/inference.py:330-338 for several matrices of ONE penalty in the baseline sweeps' own launches
     (rocco_hip_crossfit_whittaker_residual_batch_f64): out_i = (values_i - offsets_i[row]) - baseline(values_i - offsets_i[row]),

@@ -61,26 +61,55 @@ def _seam_repairs():
     return int(_native.load().rocco_hip_whittaker_seam_repairs())
 
 
+def _cut_plan(shapes, residual=False):
+    """The library's own plan for matrices of these shapes at the settings in force (rocco_hip_whittaker_batch_plan)."""
+    from rocco_amd import inference
+
+    return inference.whittaker_batch_plan(shapes, residual=residual)
+
+
 def test_rows_cut_into_segments_are_the_sequential_sweeps_bits(gpu, oracle, monkeypatch):
     """Round 5: long rows are cut into segments whose workgroups start from a warm-up (csrc/whittaker.hip).  Default
-    settings on rows long enough to be cut (2 and 3 segments, lengths around the 64-locus tiles, a lone matrix and a
-    batch): every baseline the oracle's bit for bit, and no seam had to be recomputed."""
+    settings on rows the default plan really cuts -- it keeps a row of up to 2 x warm-up + a tile whole --, their lengths
+    taken from the plan query: the first length that gives 2 segments, one that gives 3, a tile boundary, one locus less and
+    one more; a batch and a lone matrix: every baseline the oracle's bit for bit, and no seam had to be recomputed."""
     import torch
     from rocco_amd import inference
 
+    import baseline_cases as bc
+
+    monkeypatch.delenv("ROCCO_HIP_WHITTAKER_SEGMENT_LOCI", raising=False)
+    monkeypatch.delenv("ROCCO_HIP_WHITTAKER_WARM_LOCI", raising=False)
     rng = np.random.default_rng(51)
     lam = inference._consenrich_whittaker_lambda(101)
+    warm = _cut_plan([(1, 1000)])["warm_tiles"] * 64
+    assert warm == 196608
+    three = bc.first_length(lambda c: _cut_plan([(9, c)])["n_seg"][0] >= 3, 2 * warm, 4 * warm)
+    boundary = 2 * warm + 37 * 64
+    rest = [(9, three), (2, boundary - 1), (17, boundary + 1), (3, boundary)]
+    two = bc.first_length(lambda c: _cut_plan([(3, c)] + rest)["n_seg"][0] >= 2, 2 * warm, boundary)
+    shapes = [(3, two)] + rest
+    plan = _cut_plan(shapes)
+    print(f"default plan of {shapes}: {plan}")
+    assert plan["n_seg"] == [2, 3, 2, 2, 2] and plan["grouped"], plan
+    assert _cut_plan([(3, two - 1)] + rest)["n_seg"][0] == 1 and 2 * warm < two <= 2 * warm + 2 * 64 + 1, (two, plan)
+    assert plan["workgroups"] == 2 + 3 + 2 + 2 * 2 + 2 and plan["budget_loci"] >= 2 * warm, plan
+    lone = _cut_plan([shapes[1]])
+    assert lone["n_seg"] == [3] and lone["grouped"], lone
     before = _seam_repairs()
-    shapes = [(3, 262144), (9, 300001), (2, 393279), (17, 262207)]
     hosts = [rng.normal(0.0, 1.3, size=s) for s in shapes]
-    hosts[1][:, 1000:90000] = 0.0  # a long run of exact zeros
+    seam = plan["seg_tiles"][1] * 64
+    hosts[1][:, seam - 50000:seam + 39000] = 0.0  # a long run of exact zeros across the first seam
     hosts[2][:] = np.round(hosts[2] * 4.0) / 4.0  # a coarse grid: many ties
     outs = inference.crossfit_whittaker_baseline_batch_device([torch.from_numpy(h).to(gpu) for h in hosts], lam)
-    for h, o in zip(hosts, outs):
-        assert o.cpu().numpy().tobytes() == oracle.crossfit_whittaker_baseline(h, lam).tobytes(), h.shape
+    wants = [oracle.crossfit_whittaker_baseline(h, lam) for h in hosts]
+    for h, o, w in zip(hosts, outs, wants):
+        assert o.cpu().numpy().tobytes() == w.tobytes(), h.shape
     one = inference.crossfit_whittaker_baseline_batch_device([torch.from_numpy(hosts[1]).to(gpu)], lam)[0]
-    assert one.cpu().numpy().tobytes() == oracle.crossfit_whittaker_baseline(hosts[1], lam).tobytes()
-    assert _seam_repairs() == before, "a warm-up of 131 072 loci did not reach the row's own values"
+    assert one.cpu().numpy().tobytes() == wants[1].tobytes()
+    # (this rests on the meeting statistics of DESIGN.md section 13.2, not on the code: were it to fail while the bits above
+    # are right, that is a finding about the default warm-up, not a kernel bug)
+    assert _seam_repairs() == before, "a warm-up of 196 608 loci did not reach the row's own values"
 
 
 @pytest.mark.parametrize("segment,warm", [(4096, 64), (1024, 128), (8192, 2048), (20000, 20000)])
@@ -95,6 +124,11 @@ def test_seams_that_have_not_met_are_recomputed(gpu, oracle, monkeypatch, segmen
     monkeypatch.setenv("ROCCO_HIP_WHITTAKER_WARM_LOCI", str(warm))
     rng = np.random.default_rng(segment + warm)
     shapes = [(3, 50000), (10, 33333), (1, 70001), (8, 2 * segment), (5, 2 * segment - 1), (4, 3 * segment + 65)]
+    plan = _cut_plan(shapes)
+    # the library's plan of this call: every row of two segments' length or more is cut, the one a locus short of that is whole
+    assert [n >= 2 for n in plan["n_seg"]] == [c >= 2 * segment for _r, c in shapes] and plan["grouped"], plan
+    assert plan["n_seg"][3] == 2 and plan["n_seg"][4] == 1 and plan["n_seg"][5] == 3 and sum(n >= 2 for n in plan["n_seg"]) >= 4, plan
+    assert plan["warm_tiles"] == -(-warm // 64) and plan["budget_loci"] == 0, plan
     for lam in (inference._consenrich_whittaker_lambda(101), inference._consenrich_whittaker_lambda(9)):
         before = _seam_repairs()
         hosts = [rng.normal(0.0, 2.0, size=s) for s in shapes]
@@ -108,6 +142,7 @@ def test_seams_that_have_not_met_are_recomputed(gpu, oracle, monkeypatch, segmen
     h = rng.normal(size=(9, 40000))
     lam = inference._consenrich_whittaker_lambda(101)
     before = _seam_repairs()
+    assert _cut_plan([(9, 40000), (2, 40000)])["n_seg"] == [1, 1]
     o = inference.crossfit_whittaker_baseline_batch_device([torch.from_numpy(h).to(gpu), torch.from_numpy(h[:2]).to(gpu)], lam)[0]
     assert o.cpu().numpy().tobytes() == oracle.crossfit_whittaker_baseline(h, lam).tobytes()
     assert _seam_repairs() == before
@@ -128,6 +163,13 @@ def test_residual_form_is_the_three_statements(gpu, oracle, monkeypatch, segment
     rng = np.random.default_rng(77 + (segment or 0))
     lam = inference._consenrich_whittaker_lambda(101)
     shapes = [(3, 30000), (33, 9001), (1, 24), (2, 25), (40, 129), (8, 20000)]
+    plan = _cut_plan(shapes, residual=True)
+    if segment is None:
+        assert plan["n_seg"] == [1, 1, 0, 1, 1, 1] and plan["grouped"], plan  # (whole rows; the residual form has no per-row shortcut)
+    else:
+        # the three long matrices are cut, and so is the lone one further down
+        assert [n >= 2 for n in plan["n_seg"]] == [True, True, False, False, False, True], plan
+        assert _cut_plan(shapes[:1], residual=True)["n_seg"][0] >= 2
     hosts = [rng.normal(3.0, 2.0, size=s) for s in shapes]
     offs = [np.median(h, axis=1) for h in hosts]
     offs[3] = None
