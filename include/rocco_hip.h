@@ -655,8 +655,9 @@ int rocco_hip_bigwig_dense_fill_f64(rocco_hip_solver *solver, const int64_t *sta
  * arrays in file order (the order the index iterator yields them), 16 bytes per record: pos (core.pos), end
  * (bam_endpos), isize (core.isize) as int32, flag (core.flag) as uint16, mapq (core.qual) and mate_same
  * (core.mtid == core.tid) as uint8.  The records of K tracks are concatenated; rec_offsets_host has K + 1 entries.
- * BAM decoding itself, the fragments (tabix) source, barcode filters and the count modes other than "coverage" stay
- * outside; the whole-file probes (paired-end detection, read length, mapped-read count, fragment length) are row f7 below.
+ * BAM decoding itself is row f8; the fragments (tabix) source with its barcode filters and the count modes other than
+ * "coverage", which only that source gives a meaning, is row f13 (rocco_hip_fragfile_* below); the whole-file probes
+ * (paired-end detection, read length, mapped-read count, fragment length) are row f7 below.
  *
  * rocco_hip_count_alignment_records_batch: ccounts_countRegion's alignment branch (rocco/native/ccounts_backend.c:
  *   2400-2573) for K tracks in one launch series: per record the overlap test of the index iterator on the read as it
@@ -1104,6 +1105,125 @@ int rocco_hip_bigwig_sections_host(rocco_hip_solver *solver, const uint8_t *slot
                                    int64_t *file_offsets_out, int64_t *starts_out, size_t n_starts, int64_t *ends_out, size_t n_ends,
                                    double *values_out, size_t n_values, int64_t *report_out);
 void rocco_hip_bigwig_sections_shape(int *shape_out);
+
+/* ---- fragments files: inflated text -> lines -> fields -> bins (note (34)) ---------------
+ * The reference's third counting source, ccounts_sourceKindFragments (rocco/native/ccounts_backend.c): the BGZF-compressed,
+ * tabix-indexed text of single-cell ATAC pipelines, one line "contig<TAB>start<TAB>end<TAB>barcode<TAB>count" per fragment.
+ * The container (the .tbi index, the BGZF blocks) is read by rocco_amd/tabix_index.py and rocco_amd/fragments.py and
+ * inflated by rocco_hip_bgzf_inflate or on the host; these entries take the inflated bytes.  The rules are written once, in
+ * csrc/fragments_rules.h, for the kernels and for rocco_hip_fragfile_host.
+ *
+ * rocco_hip_fragfile_lines: the lines of bytes_dev[entry0 .. n_bytes).  A facts kernel counts '\n' per tile of
+ *   ROCCO_FRAGFILE_TILE_BYTES bytes (a grid stride under ROCCO_FRAGFILE_LINES_MAX_GRID workgroups), hipcub's exclusive sum
+ *   gives every tile its first line, an emit kernel writes the line starts: starts_out_dev[0] = entry0, one entry behind
+ *   every '\n' that is not the last byte, and starts_out_dev[n_lines] = n_bytes, so that line i is [starts[i], starts[i + 1])
+ *   with its terminator; an unterminated last line is a line.  report_out_host[0..3] = n_lines, the offset behind the last
+ *   '\n' (entry0 where there is none: where a slab is cut), 1 where the last line is unterminated, 0.  With
+ *   starts_out_dev == NULL only the report is made (call once for the size); otherwise ROCCO_HIP_EINVAL where `capacity`
+ *   holds fewer than n_lines + 1 entries.  No byte at or beyond n_bytes is read.
+ * rocco_hip_fragfile_fields: one lane per line (ROCCO_FRAGFILE_THREADS lines per workgroup turn, a grid stride under
+ *   ROCCO_FRAGFILE_FIELDS_MAX_GRID).  The lines are those of K tracks one behind the other (track_first_host[K + 1], in
+ *   lines).  Per line: start and end (columns 2 and 3 by ccounts_parseInt64Field, 359-394), weight (column 5 where it
+ *   parses and is positive, else 1: 2246-2249, 2271), name (the index of column 1 among the n_names packed names:
+ *   names_host[name_offsets_host[i] .. name_offsets_host[i + 1]); -1 where it is none of them) and the status word below;
+ *   the barcode (column 4) is looked up by binary search in the track's own sorted allow-list, the entries
+ *   [allow_first_host[k], allow_first_host[k + 1]) of allow_bytes_dev / allow_offsets_dev (n_allow + 1 offsets; an empty list
+ *   allows everything, as does an empty barcode: 311-357, 2261-2269).
+ *   whole_file == 0, the lines of index spans: a line that begins with '#' is a meta line (the index iterator skips it) and
+ *   gets the status ROCCO_FRAGFILE_META alone; every other line must keep the dialect: at least three fields, columns 2 and
+ *   3 canonical decimals ("0" or [1-9][0-9]*) below 2^31, no NUL, no '\r' but directly before '\n', column 1 equal to name
+ *   expect_host[k] (-1: not checked), column 2 not below that of the track's line before it, column 5 -- where it is an
+ *   optional '-' and digits -- of at most 18 digits and below 2^31.  whole_file != 0, hts_getline's lines (1770, 713): meta
+ *   lines and short lines are lines; the canonical rule holds for columns 2 and 3 of every other line that has them (an
+ *   empty column is one the line does not have).  The range rules hold for EVERY line, meta lines included: a column 2 or 3
+ *   that parses and lies at or beyond 2^31 in magnitude, and a column 5 beyond 18 digits or 2^31, are refused wherever
+ *   they stand (the outputs are int32).  n_lines < 2^32.
+ *   report_out_host[0..3] = the first offending line in line order (-1: none), the lowest ROCCO_FRAGFILE_ERR_* within it, 0, 0.
+ * rocco_hip_fragfile_count_batch: ccounts_countRegion's fragments branch (2212-2353) for K tracks (slices of the line
+ *   arrays, line_offsets_host[K + 1]; each with its own region, mode and one_read_per_bin) in one launch series.  A line
+ *   counts when both integers parsed, end > start, the last field the reference's loop scans is not empty and its barcode
+ *   is allowed.  center, or one_read_per_bin in any mode: weight at the bin of (start + end) / 2 where that lies in the
+ *   region; cutsite and fiveprime: weight at the bin of start and at the bin of end - 1, each tested on its own; coverage:
+ *   the clip to the region, +weight at index0 and -weight behind index1 with the reference's clamp and skips, then the
+ *   running sum.  Integer atomics into a positive sum P and a negative sum N per bin (64-bit cells), so the result does not
+ *   depend on scheduling; coverage scans P - N and converts once to float32, the other modes write P.  The reference adds
+ *   floats in file order; that equals these integers for any order while max(P, N) of every cell and every running value
+ *   stay within 2^24 (every partial sum of a cell lies in [-N, P]).  max_magnitude_out_host[k] is that maximum for track k;
+ *   the caller refuses a result beyond 2^24.  out_dev + out_offsets_host[k] receives the n_bins counts of track k; nothing
+ *   is accumulated into what was there.
+ * rocco_hip_fragfile_chrom_range_batch: ccounts_getChromRange's fragments branch (1583-1631) per track: range_out_host[2 k]
+ *   = start of the first line in file order whose integers parsed and whose end > start, [2 k + 1] = end of the LAST such
+ *   line in file order (not the maximum); 0 / 0 where there is none.  Only lines with start < chrom_len_host[k] count: the
+ *   reference's query over [0, chromLength) yields no other (1579-1580).
+ * rocco_hip_fragfile_mapped_count: the sum of ccounts_getMappedReadCount's fragments branch (1770-1835) over n_lines lines
+ *   of a whole-file field pass whose names were the contigs to leave out: a line counts when name < 0, its fifth field is
+ *   not empty and its barcode is allowed; it adds its weight, twice for cutsite / fiveprime without one_read_per_bin.  An
+ *   integer reduction into *sum_out_host.
+ * rocco_hip_fragfile_host: the line pass and the field pass over HOST memory on the calling thread, from the same
+ *   header (test support; no device is touched, `solver` may be NULL).  track_first may be NULL for one track over all
+ *   lines (expect[0], allow_first[0..1]); the five field outputs may all be NULL for the line pass alone.
+ * rocco_hip_fragfile_shape: shape_out[0..5] = ROCCO_FRAGFILE_THREADS, ROCCO_FRAGFILE_TILE_BYTES, the lines of a workgroup
+ *   turn of the field, count and range kernels (ROCCO_FRAGFILE_THREADS), ROCCO_FRAGFILE_LINES_MAX_GRID,
+ *   ROCCO_FRAGFILE_FIELDS_MAX_GRID, ROCCO_FRAGFILE_COUNT_MAX_GRID. */
+#define ROCCO_FRAGFILE_THREADS 256
+#define ROCCO_FRAGFILE_TILE_BYTES 4096
+#define ROCCO_FRAGFILE_LINES_MAX_GRID 2048  /* unit: one tile of bytes (fragfile_line_facts_kernel, fragfile_line_emit_kernel) */
+#define ROCCO_FRAGFILE_FIELDS_MAX_GRID 2048 /* unit: ROCCO_FRAGFILE_THREADS lines (fragfile_fields_kernel, fragfile_order_kernel) */
+#define ROCCO_FRAGFILE_COUNT_MAX_GRID 1024  /* unit: ROCCO_FRAGFILE_THREADS lines (fragfile_count_kernel, fragfile_range_kernel, fragfile_mapped_kernel) */
+#define ROCCO_FRAGFILE_SCAN_ITEMS 4         /* bins per thread of a scan tile (fragfile_finish_kernel: one workgroup per track) */
+/* the status word of a line */
+#define ROCCO_FRAGFILE_META 0x1u             /* begins with '#' */
+#define ROCCO_FRAGFILE_FIELDS_SHIFT 1        /* bits 1..3: min(the fields the count rule's loop scans, 5) */
+#define ROCCO_FRAGFILE_FIELDS_MASK 0x7u
+#define ROCCO_FRAGFILE_START_OK 0x10u        /* column 2 parsed (and lies within int32) */
+#define ROCCO_FRAGFILE_END_OK 0x20u          /* column 3 parsed */
+#define ROCCO_FRAGFILE_LAST_EMPTY 0x40u      /* the count rule: the last field scanned is empty (2257) */
+#define ROCCO_FRAGFILE_FIFTH_EMPTY 0x80u     /* the mapped rule: the fifth field is empty or absent (1812) */
+#define ROCCO_FRAGFILE_WEIGHT_PARSED 0x100u  /* column 5 parsed */
+#define ROCCO_FRAGFILE_BARCODE_PRESENT 0x200u
+#define ROCCO_FRAGFILE_BARCODE_ALLOWED 0x400u /* the barcode is empty or absent, the list is empty, or it holds the barcode */
+#define ROCCO_FRAGFILE_NONCANONICAL 0x800u   /* column 2 or 3 is no canonical decimal */
+#define ROCCO_FRAGFILE_BEYOND 0x1000u        /* column 2, 3 or 5 at or beyond 2^31 (column 5: or more than 18 digits) */
+/* what a line is refused for, lowest first */
+#define ROCCO_FRAGFILE_ERR_FIELDS 1
+#define ROCCO_FRAGFILE_ERR_NUL 2
+#define ROCCO_FRAGFILE_ERR_CR 3
+#define ROCCO_FRAGFILE_ERR_NONCANONICAL 4
+#define ROCCO_FRAGFILE_ERR_BEYOND 5
+#define ROCCO_FRAGFILE_ERR_COUNT 6
+#define ROCCO_FRAGFILE_ERR_CONTIG 7
+#define ROCCO_FRAGFILE_ERR_ORDER 8
+/* the reference's ccounts_countMode */
+#define ROCCO_FRAGFILE_MODE_COVERAGE 0
+#define ROCCO_FRAGFILE_MODE_CUTSITE 1
+#define ROCCO_FRAGFILE_MODE_FIVEPRIME 2
+#define ROCCO_FRAGFILE_MODE_CENTER 3
+typedef struct rocco_hip_fragfile_options {
+    int32_t count_mode, one_read_per_bin;
+} rocco_hip_fragfile_options;
+int rocco_hip_fragfile_lines(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, size_t entry0, int64_t *starts_out_dev,
+                             size_t capacity, int64_t *report_out_host, void *stream);
+int rocco_hip_fragfile_fields(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, const int64_t *starts_dev, size_t n_lines,
+                              int whole_file, const int64_t *track_first_host, const int32_t *expect_host, size_t K,
+                              const uint8_t *names_host, const int64_t *name_offsets_host, size_t n_names, const uint8_t *allow_bytes_dev,
+                              const int64_t *allow_offsets_dev, size_t n_allow, const int64_t *allow_first_host, int32_t *start_out_dev,
+                              int32_t *end_out_dev, int32_t *weight_out_dev, int32_t *name_out_dev, uint32_t *status_out_dev,
+                              int64_t *report_out_host, void *stream);
+int rocco_hip_fragfile_count_batch(rocco_hip_solver *solver, const int32_t *start_dev, const int32_t *end_dev, const int32_t *weight_dev,
+                                   const uint32_t *status_dev, const int64_t *line_offsets_host, size_t K,
+                                   const rocco_hip_fragfile_options *options_host, const rocco_hip_count_region *regions_host,
+                                   const int64_t *out_offsets_host, float *out_dev, int64_t *max_magnitude_out_host, void *stream);
+int rocco_hip_fragfile_chrom_range_batch(rocco_hip_solver *solver, const int32_t *start_dev, const int32_t *end_dev,
+                                         const uint32_t *status_dev, const int64_t *line_offsets_host, const int64_t *chrom_len_host,
+                                         size_t K, int64_t *range_out_host, void *stream);
+int rocco_hip_fragfile_mapped_count(rocco_hip_solver *solver, const int32_t *weight_dev, const int32_t *name_dev, const uint32_t *status_dev,
+                                    size_t n_lines, int count_mode, int one_read_per_bin, uint64_t *sum_out_host, void *stream);
+int rocco_hip_fragfile_host(rocco_hip_solver *solver, const uint8_t *bytes, size_t n_bytes, size_t entry0, int64_t *starts_out, size_t capacity,
+                            int64_t *lines_report_out, int whole_file, const int64_t *track_first, const int32_t *expect, size_t K,
+                            const uint8_t *names, const int64_t *name_offsets, size_t n_names, const uint8_t *allow_bytes,
+                            const int64_t *allow_offsets, size_t n_allow, const int64_t *allow_first, int32_t *start_out, int32_t *end_out,
+                            int32_t *weight_out, int32_t *name_out, uint32_t *status_out, int64_t *fields_report_out);
+void rocco_hip_fragfile_shape(int *shape_out);
 
 /* ---- the grid caps of the record and select kernels -----------------------------------------------------------------
  * Every kernel behind the data front end caps its grid; past cap x unit a workgroup takes several units in turn (a grid

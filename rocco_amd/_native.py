@@ -367,6 +367,28 @@ PROTOTYPES = [
       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, ctypes.c_void_p, ctypes.c_size_t,
       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, c_ll_p]),
     ("rocco_hip_bigwig_sections_shape", None, [c_int_p]),
+    # row f13 (csrc/fragments_file.hip, csrc/fragments_rules.h): the reference's fragments source over the inflated text
+    # (ccounts_backend.c:2212-2353 the region count, 1583-1631 the range, 1770-1835 the mapped count)
+    ("rocco_hip_fragfile_lines", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_fragfile_fields", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, c_ll_p, c_int_p, ctypes.c_size_t,
+      ctypes.c_void_p, c_ll_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_fragfile_count_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_size_t, ctypes.c_void_p,
+      ctypes.c_void_p, c_ll_p, ctypes.c_void_p, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_fragfile_chrom_range_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_size_t, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_fragfile_mapped_count", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+      ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]),
+    # (test support: the line and field passes over host memory, on the calling thread)
+    ("rocco_hip_fragfile_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, ctypes.c_int, c_ll_p, c_int_p,
+      ctypes.c_size_t, ctypes.c_void_p, c_ll_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p]),
+    ("rocco_hip_fragfile_shape", None, [c_int_p]),
     # (no reference line: the grid caps of the record and select kernels, for the tests that go past one launch's first turn)
     ("rocco_hip_launch_caps", None, [c_int_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,

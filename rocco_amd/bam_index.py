@@ -54,7 +54,13 @@ def parse_bam_index(raw, name: str = "<bytes>") -> BamIndex:
     (n_ref,) = struct.unpack_from("<i", raw, 4)
     if n_ref < 0:
         raise _bad(name, "the header", 4, f"n_ref is negative ({n_ref})")
-    at = 8
+    return BamIndex(name, len(raw), *parse_index_body(raw, name, 8, n_ref))
+
+
+def parse_index_body(raw, name: str, at: int, n_ref: int):
+    """The per-reference body that a ``.bai`` and a ``.tbi`` index share, from file offset ``at``: (per reference its bins, its
+    pseudo-bin, the length of its linear index; the trailing count of records without a contig or None).  The errors of
+    `parse_bam_index`."""
     bins_of, pseudo_of, n_intv_of = [], [], []
     for tid in range(n_ref):
         what = f"reference {tid}"
@@ -100,7 +106,7 @@ def parse_bam_index(raw, name: str = "<bytes>") -> BamIndex:
     n_no_coor = None
     if at + 8 <= len(raw):
         (n_no_coor,) = struct.unpack_from("<Q", raw, at)
-    return BamIndex(name, len(raw), bins_of, pseudo_of, n_intv_of, None if n_no_coor is None else int(n_no_coor))
+    return bins_of, pseudo_of, n_intv_of, None if n_no_coor is None else int(n_no_coor)
 
 
 _BAM_INDEX_CACHE: "collections.OrderedDict" = collections.OrderedDict()

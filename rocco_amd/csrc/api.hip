@@ -8,6 +8,7 @@
 #include "budget.h"
 #include "inflate_core.h"
 #include "bigwig_sections.h"
+#include "fragments_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1990,6 +1991,162 @@ void rocco_hip_bigwig_sections_shape(int *shape_out)
     shape_out[0] = ROCCO_BIGWIG_THREADS;
     shape_out[1] = ROCCO_BIGWIG_MAX_GRID;
     shape_out[2] = (int)kSectionHeaderBytes;
+}
+
+// ---- fragments files (row f13): the checks of every pointer and size; the launchers check what the host arrays hold ----
+
+static bool fragfile_fields_args_ok(const void *bytes, size_t n_bytes, const void *starts, size_t n_lines, const void *expect, size_t K,
+                                    const void *names, const int64_t *name_offsets, size_t n_names, const void *allow_bytes, const void *allow_offsets,
+                                    size_t n_allow, const void *allow_first, const void *report)
+{
+    // (n_lines < 2^32: the word of the first offending line keeps the line in its upper 32 bits)
+    return report != nullptr && K >= 1 && K < (size_t)0x7fffffff && n_lines < ((size_t)1 << 32) && n_bytes < ((size_t)1 << 40) && n_names < 65536 &&
+           n_allow < ((size_t)1 << 40) && expect != nullptr && allow_first != nullptr && name_offsets != nullptr && starts != nullptr &&
+           (n_bytes == 0 || bytes != nullptr) && (n_names == 0 || names != nullptr || name_offsets[n_names] == 0) &&
+           (n_allow == 0 || (allow_bytes != nullptr && allow_offsets != nullptr));
+}
+
+int rocco_hip_fragfile_lines(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, size_t entry0, int64_t *starts_out_dev,
+                             size_t capacity, int64_t *report_out_host, void *stream)
+{
+    if (solver == nullptr || report_out_host == nullptr || n_bytes >= ((size_t)1 << 40) || entry0 > n_bytes || (n_bytes > 0 && bytes_dev == nullptr)) {
+        set_last_error("fragfile_lines: a null pointer with a size, entry0 beyond n_bytes, or 2^40 bytes and more");
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, fragfile_lines_scratch_bytes(n_bytes, entry0)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_fragfile_lines(bytes_dev, n_bytes, entry0, starts_out_dev, capacity, report_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_fragfile_fields(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, const int64_t *starts_dev, size_t n_lines,
+                              int whole_file, const int64_t *track_first_host, const int32_t *expect_host, size_t K,
+                              const uint8_t *names_host, const int64_t *name_offsets_host, size_t n_names, const uint8_t *allow_bytes_dev,
+                              const int64_t *allow_offsets_dev, size_t n_allow, const int64_t *allow_first_host, int32_t *start_out_dev,
+                              int32_t *end_out_dev, int32_t *weight_out_dev, int32_t *name_out_dev, uint32_t *status_out_dev,
+                              int64_t *report_out_host, void *stream)
+{
+    if (solver == nullptr || track_first_host == nullptr ||
+        !fragfile_fields_args_ok(bytes_dev, n_bytes, starts_dev, n_lines, expect_host, K, names_host, name_offsets_host, n_names, allow_bytes_dev,
+                                 allow_offsets_dev, n_allow, allow_first_host, report_out_host) ||
+        (n_lines > 0 && (start_out_dev == nullptr || end_out_dev == nullptr || weight_out_dev == nullptr || name_out_dev == nullptr ||
+                         status_out_dev == nullptr))) {
+        set_last_error("fragfile_fields: a null pointer with a size, no track, or a size beyond its limit");
+        return ROCCO_HIP_EINVAL;
+    }
+    const size_t name_bytes = name_offsets_host[n_names] > 0 ? (size_t)name_offsets_host[n_names] : 0;
+    if (const int rc = enter_record_call(solver, fragfile_fields_scratch_bytes(K, n_names, name_bytes)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_fragfile_fields(bytes_dev, n_bytes, starts_dev, n_lines, whole_file, track_first_host, expect_host, K, names_host,
+                                  name_offsets_host, n_names, allow_bytes_dev, allow_offsets_dev, n_allow, allow_first_host, start_out_dev,
+                                  end_out_dev, weight_out_dev, name_out_dev, status_out_dev, report_out_host, solver->dev_misc.ptr,
+                                  (hipStream_t)stream);
+}
+
+int rocco_hip_fragfile_count_batch(rocco_hip_solver *solver, const int32_t *start_dev, const int32_t *end_dev, const int32_t *weight_dev,
+                                   const uint32_t *status_dev, const int64_t *line_offsets_host, size_t K,
+                                   const rocco_hip_fragfile_options *options_host, const rocco_hip_count_region *regions_host,
+                                   const int64_t *out_offsets_host, float *out_dev, int64_t *max_magnitude_out_host, void *stream)
+{
+    if (solver == nullptr || K == 0 || K >= (size_t)0x7fffffff || line_offsets_host == nullptr || options_host == nullptr ||
+        regions_host == nullptr || out_offsets_host == nullptr || out_dev == nullptr || max_magnitude_out_host == nullptr) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (line_offsets_host[K] > line_offsets_host[0] &&
+        (start_dev == nullptr || end_dev == nullptr || weight_dev == nullptr || status_dev == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, fragfile_count_scratch_bytes(K, regions_host)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_fragfile_count_batch(start_dev, end_dev, weight_dev, status_dev, line_offsets_host, K, options_host, regions_host,
+                                       out_offsets_host, out_dev, max_magnitude_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_fragfile_chrom_range_batch(rocco_hip_solver *solver, const int32_t *start_dev, const int32_t *end_dev,
+                                         const uint32_t *status_dev, const int64_t *line_offsets_host, const int64_t *chrom_len_host,
+                                         size_t K, int64_t *range_out_host, void *stream)
+{
+    if (solver == nullptr || K == 0 || K >= (size_t)0x7fffffff || line_offsets_host == nullptr || chrom_len_host == nullptr ||
+        range_out_host == nullptr) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (line_offsets_host[K] > line_offsets_host[0] && (start_dev == nullptr || end_dev == nullptr || status_dev == nullptr)) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, fragfile_range_scratch_bytes(K)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_fragfile_chrom_range_batch(start_dev, end_dev, status_dev, line_offsets_host, chrom_len_host, K, range_out_host,
+                                             solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_fragfile_mapped_count(rocco_hip_solver *solver, const int32_t *weight_dev, const int32_t *name_dev, const uint32_t *status_dev,
+                                    size_t n_lines, int count_mode, int one_read_per_bin, uint64_t *sum_out_host, void *stream)
+{
+    if (solver == nullptr || sum_out_host == nullptr || n_lines >= ((size_t)1 << 40) || count_mode < 0 || count_mode > ROCCO_FRAGFILE_MODE_CENTER ||
+        (n_lines > 0 && (weight_dev == nullptr || name_dev == nullptr || status_dev == nullptr))) {
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, 256); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_fragfile_mapped_count(weight_dev, name_dev, status_dev, n_lines, count_mode, one_read_per_bin, sum_out_host,
+                                        solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_fragfile_host(rocco_hip_solver *, const uint8_t *bytes, size_t n_bytes, size_t entry0, int64_t *starts_out, size_t capacity,
+                            int64_t *lines_report_out, int whole_file, const int64_t *track_first, const int32_t *expect, size_t K,
+                            const uint8_t *names, const int64_t *name_offsets, size_t n_names, const uint8_t *allow_bytes,
+                            const int64_t *allow_offsets, size_t n_allow, const int64_t *allow_first, int32_t *start_out, int32_t *end_out,
+                            int32_t *weight_out, int32_t *name_out, uint32_t *status_out, int64_t *fields_report_out)
+{
+    if (lines_report_out == nullptr || n_bytes >= ((size_t)1 << 40) || entry0 > n_bytes || (n_bytes > 0 && bytes == nullptr)) {
+        set_last_error("fragfile_host: a null pointer with a size, entry0 beyond n_bytes, or 2^40 bytes and more");
+        return ROCCO_HIP_EINVAL;
+    }
+    if (!fragfile_lines_host(bytes, n_bytes, entry0, starts_out, capacity, lines_report_out)) {
+        set_last_error("fragfile_host: the bytes hold " + std::to_string(lines_report_out[0]) + " lines, starts_out has room for " +
+                       std::to_string(capacity) + " entries where one more than the lines belong");
+        return ROCCO_HIP_EINVAL;
+    }
+    const bool fields = start_out != nullptr || end_out != nullptr || weight_out != nullptr || name_out != nullptr || status_out != nullptr;
+    if (!fields) {
+        return ROCCO_HIP_OK;
+    }
+    const size_t n_lines = (size_t)lines_report_out[0];
+    const int64_t whole[2] = {0, (int64_t)n_lines};
+    const size_t tracks = track_first == nullptr ? 1 : K;
+    const int64_t *first = track_first == nullptr ? whole : track_first;
+    if (start_out == nullptr || end_out == nullptr || weight_out == nullptr || name_out == nullptr || status_out == nullptr ||
+        !fragfile_fields_args_ok(bytes, n_bytes, starts_out, n_lines, expect, tracks, names, name_offsets, n_names, allow_bytes, allow_offsets,
+                                 n_allow, allow_first, fields_report_out)) {
+        set_last_error("fragfile_host: the field pass needs the starts, all five outputs and its report; a null pointer with a size, or no track");
+        return ROCCO_HIP_EINVAL;
+    }
+    for (size_t k = 0; k < tracks; ++k) {
+        if (first[k] > first[k + 1] || first[0] != 0 || first[tracks] != (int64_t)n_lines || allow_first[k] > allow_first[k + 1] || allow_first[0] < 0 ||
+            allow_first[tracks] > (int64_t)n_allow || expect[k] >= (int32_t)n_names) {
+            set_last_error("fragfile_host: track_first must ascend from 0 to the number of lines, allow_first within the n_allow entries, expect "
+                           "within the names");
+            return ROCCO_HIP_EINVAL;
+        }
+    }
+    const FragNames table = {names, name_offsets, 0, (long long)n_names};
+    fragfile_fields_host(bytes, starts_out, n_lines, whole_file, first, expect, tracks, table, allow_bytes, allow_offsets, allow_first, start_out,
+                         end_out, weight_out, name_out, status_out, fields_report_out);
+    return ROCCO_HIP_OK;
+}
+
+void rocco_hip_fragfile_shape(int *shape_out)
+{
+    shape_out[0] = ROCCO_FRAGFILE_THREADS;
+    shape_out[1] = ROCCO_FRAGFILE_TILE_BYTES;
+    shape_out[2] = ROCCO_FRAGFILE_THREADS;
+    shape_out[3] = ROCCO_FRAGFILE_LINES_MAX_GRID;
+    shape_out[4] = ROCCO_FRAGFILE_FIELDS_MAX_GRID;
+    shape_out[5] = ROCCO_FRAGFILE_COUNT_MAX_GRID;
 }
 
 void rocco_hip_launch_caps(int *out)

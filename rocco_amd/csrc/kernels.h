@@ -441,6 +441,29 @@ int launch_bigwig_sections_emit(const uint8_t *slots_dev, size_t n_slots, const 
                                 const int64_t *block_first_dev, size_t capacity, int64_t *starts_out_dev, int64_t *ends_out_dev,
                                 double *values_out_dev, void *scratch_dev, hipStream_t stream);
 
+// ---- fragments_file.hip -----------------------------------------------------------------------
+// the inflated text of fragments files -> lines, fields, bins (row f13); the rules and the host twin are fragments_rules.h's.
+// The entry points of api.hip have checked every pointer and size; the launchers check what the host arrays hold
+size_t fragfile_lines_scratch_bytes(size_t n_bytes, size_t entry0);
+int launch_fragfile_lines(const uint8_t *bytes_dev, size_t n_bytes, size_t entry0, int64_t *starts_out_dev, size_t capacity,
+                          int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
+size_t fragfile_fields_scratch_bytes(size_t K, size_t n_names, size_t name_bytes);
+int launch_fragfile_fields(const uint8_t *bytes_dev, size_t n_bytes, const int64_t *starts_dev, size_t n_lines, int whole_file,
+                           const int64_t *track_first_host, const int32_t *expect_host, size_t K, const uint8_t *names_host,
+                           const int64_t *name_offsets_host, size_t n_names, const uint8_t *allow_bytes_dev, const int64_t *allow_offsets_dev,
+                           size_t n_allow, const int64_t *allow_first_host, int32_t *start_out_dev, int32_t *end_out_dev, int32_t *weight_out_dev,
+                           int32_t *name_out_dev, uint32_t *status_out_dev, int64_t *report_out_host, void *scratch_dev, hipStream_t stream);
+size_t fragfile_count_scratch_bytes(size_t K, const rocco_hip_count_region *regions_host);
+int launch_fragfile_count_batch(const int32_t *start_dev, const int32_t *end_dev, const int32_t *weight_dev, const uint32_t *status_dev,
+                                const int64_t *line_offsets_host, size_t K, const rocco_hip_fragfile_options *options_host,
+                                const rocco_hip_count_region *regions_host, const int64_t *out_offsets_host, float *out_dev,
+                                int64_t *max_magnitude_out_host, void *scratch_dev, hipStream_t stream);
+size_t fragfile_range_scratch_bytes(size_t K);
+int launch_fragfile_chrom_range_batch(const int32_t *start_dev, const int32_t *end_dev, const uint32_t *status_dev, const int64_t *line_offsets_host,
+                                      const int64_t *chrom_len_host, size_t K, int64_t *range_out_host, void *scratch_dev, hipStream_t stream);
+int launch_fragfile_mapped_count(const int32_t *weight_dev, const int32_t *name_dev, const uint32_t *status_dev, size_t n_lines, int count_mode,
+                                 int one_read_per_bin, uint64_t *sum_out_host, void *scratch_dev, hipStream_t stream);
+
 // ---- synth.hip ------------------------------------------------------------------------------
 int launch_synth(void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, uint64_t seed,
                  hipStream_t stream);
