@@ -73,8 +73,8 @@ class Noise(ctypes.Structure):
 
 def build(force: bool = False) -> str:
     """Compile oracle/liboracle.so (and oracle/_ref when the reference is mounted)."""
-    if force or not os.path.isfile(_LIB_PATH):
-        subprocess.run(["make", "-C", _HERE, "liboracle.so"], check=True, capture_output=True)
+    # (make compares the library with its sources: a library left by an older tree is rebuilt, a current one is kept)
+    subprocess.run(["make", "-C", _HERE, "liboracle.so"] + (["-B"] if force else []), check=True, capture_output=True)
     if os.path.isdir("/root/reference"):
         subprocess.run(["make", "-C", _HERE, "ref"], check=False, capture_output=True)
     return _LIB_PATH
@@ -125,6 +125,18 @@ def lib() -> ctypes.CDLL:
             _c_double_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double,
             ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
             _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]
+        _lib.oracle_score_centered_wls_given_variances_f64.restype = ctypes.c_int
+        _lib.oracle_score_centered_wls_given_variances_f64.argtypes = [
+            _c_double_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+            ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+            _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]
+        _lib.oracle_wls_spatial_window.restype = ctypes.c_size_t
+        _lib.oracle_wls_spatial_window.argtypes = [ctypes.c_size_t, ctypes.c_int]
+        _lib.oracle_rolling_ar1_innovation_variance_starts_f64.restype = ctypes.c_int
+        _lib.oracle_rolling_ar1_innovation_variance_starts_f64.argtypes = [
+            _c_double_p, ctypes.c_size_t, ctypes.c_size_t, _c_double_p]
+        _lib.oracle_monotone_variance_trend_f64.restype = ctypes.c_int
+        _lib.oracle_monotone_variance_trend_f64.argtypes = [_c_double_p, _c_double_p, ctypes.c_size_t, _c_double_p]
         _lib.oracle_crossfit_whittaker_baseline_matrix_f64.restype = ctypes.c_int
         _lib.oracle_crossfit_whittaker_baseline_matrix_f64.argtypes = [
             _c_double_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_double, _c_double_p]
@@ -410,19 +422,60 @@ def crossfit_whittaker_baseline(values, penalty_lambda: float) -> np.ndarray:
     return out
 
 
-def score_centered_wls(centered_matrix, lower_bound_z: float = 1.0, prior_df: float = 5.0, min_effect=None,
-                       spatial_window: int = 31, precision_floor_ratio: float = 0.01):
-    """rocco/_wls.c `score_centered_wls` over rocco/native/wls_backend.c:744-947: returns
-    (scores, mean, raw_variance, prior_variance, moderated_variance, standard_error, total_df, window)."""
+def wls_spatial_window(n: int, requested: int = 31) -> int:
+    """rocco/native/wls_backend.c:232-260: odd, at least 5, at most n; 0 for fewer than 5 loci."""
+    return int(lib().oracle_wls_spatial_window(int(n), int(requested)))
+
+
+def rolling_variances_at_starts(centered_matrix, spatial_window: int = 31):
+    """rocco/native/wls_backend.c:610-726 on every row: the AR(1) innovation variance of every window BY ITS START
+    POSITION, [K, n - window + 1] (locus i of the scoring reads start clamp(i - window // 2, 0, n - window)); None where
+    the row has no window (fewer than 5 loci)."""
     m = np.ascontiguousarray(centered_matrix, dtype=np.float64)
     if m.ndim != 2 or m.shape[0] == 0 or m.shape[1] == 0:
         raise ValueError("`centered_matrix` must be a non-empty two-dimensional array")
     K, n = m.shape
+    window = wls_spatial_window(n, spatial_window)
+    if window == 0:
+        return None
+    out = np.empty((K, n - window + 1), dtype=np.float64)
+    for k in range(K):
+        _check(lib().oracle_rolling_ar1_innovation_variance_starts_f64(_dptr(m[k]), n, window, _dptr(out[k])))
+    return out
+
+
+def monotone_variance_trend(covariate, raw_variance) -> np.ndarray:
+    """rocco/native/wls_backend.c:394-608 on one row: the monotone trend of the variances over |covariate|."""
+    cov = np.ascontiguousarray(covariate, dtype=np.float64)
+    raw = np.ascontiguousarray(raw_variance, dtype=np.float64)
+    if cov.ndim != 1 or raw.shape != cov.shape:
+        raise ValueError("`covariate` and `raw_variance` must be one-dimensional and of one length")
+    out = np.empty(cov.shape[0], dtype=np.float64)
+    _check(lib().oracle_monotone_variance_trend_f64(_dptr(cov), _dptr(raw), cov.shape[0], _dptr(out)))
+    return out
+
+
+def score_centered_wls(centered_matrix, lower_bound_z: float = 1.0, prior_df: float = 5.0, min_effect=None,
+                       spatial_window: int = 31, precision_floor_ratio: float = 0.01, variances=None):
+    """rocco/_wls.c `score_centered_wls` over rocco/native/wls_backend.c:744-947: returns
+    (scores, mean, raw_variance, prior_variance, moderated_variance, standard_error, total_df, window).
+    `variances` [K, n - window + 1]: every row's rolling variances by window start, dictated by the caller in place of
+    `rolling_variances_at_starts` (the reference has no such entry; everything behind the variances is its code path)."""
+    m = np.ascontiguousarray(centered_matrix, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] == 0 or m.shape[1] == 0:
+        raise ValueError("`centered_matrix` must be a non-empty two-dimensional array")
+    K, n = m.shape
+    given = None
+    if variances is not None:
+        window = wls_spatial_window(n, spatial_window)
+        given = np.ascontiguousarray(variances, dtype=np.float64)
+        if window == 0 or given.shape != (K, n - window + 1):
+            raise ValueError("`variances` must be [K, n - window + 1]")
     tracks = [np.empty(n, dtype=np.float64) for _ in range(6)]
     df, win = ctypes.c_double(), ctypes.c_int()
-    _check(lib().oracle_score_centered_wls_f64(
+    _check(lib().oracle_score_centered_wls_given_variances_f64(
         _dptr(m), K, n, float(lower_bound_z), float(prior_df), float(0.0 if min_effect is None else min_effect),
-        0 if min_effect is None else 1, int(spatial_window), float(precision_floor_ratio),
+        0 if min_effect is None else 1, int(spatial_window), float(precision_floor_ratio), _dptr(given),
         *[_dptr(t) for t in tracks], ctypes.byref(df), ctypes.byref(win)))
     mean, raw, prior, mod, se, scores = tracks
     return scores, mean, raw, prior, mod, se, float(df.value), int(win.value)

@@ -59,18 +59,11 @@ size_t oracle_wls_spatial_window(size_t n, int requested)
     return (w < 5) ? 0 : w;
 }
 
-/* wls_backend.c:610-742 */
-int oracle_rolling_ar1_innovation_variance_f64(const double *v, size_t n, size_t window, double *out)
+/* wls_backend.c:610-726: the variance of every window, by its start position (n - window + 1 values); `window` is
+ * resolved already (odd, 5 <= window <= n) */
+static void rolling_at_starts(const double *v, size_t n, size_t window, double *at_start)
 {
-    if (v == NULL || out == NULL || n == 0) return -2;
-    window = oracle_wls_spatial_window(n, (int)window);
-    if (window == 0 || n < 4) {
-        memset(out, 0, n * sizeof(double));
-        return 0;
-    }
-    const size_t half = window / 2, max_start = n - window;
-    double *at_start = (double *)malloc((max_start + 1) * sizeof(double));
-    if (at_start == NULL) return -1;
+    const size_t max_start = n - window;
     double sum_y = 0.0, sum_sq = 0.0, sum_lag = 0.0;
     for (size_t i = 0; i < window; ++i) {
         sum_y += v[i];
@@ -104,11 +97,41 @@ int oracle_rolling_ar1_innovation_variance_f64(const double *v, size_t n, size_t
             sum_lag = sum_lag - (leaving * lag_right) + (lag_left * next);
         }
     }
+}
+
+int oracle_rolling_ar1_innovation_variance_starts_f64(const double *v, size_t n, size_t window, double *at_start)
+{
+    if (v == NULL || at_start == NULL || n == 0) return -2;
+    window = oracle_wls_spatial_window(n, (int)window);
+    if (window == 0 || n < 4) return -2;
+    rolling_at_starts(v, n, window, at_start);
+    return 0;
+}
+
+/* wls_backend.c:727-738: locus i reads the window centred on it, clamped to the row */
+static void expand_starts(const double *at_start, size_t n, size_t window, double *out)
+{
+    const size_t half = window / 2, max_start = n - window;
     for (size_t i = 0; i < n; ++i) {
         size_t c = (i < half) ? 0 : (i - half);
         if (c > max_start) c = max_start;
         out[i] = at_start[c];
     }
+}
+
+/* wls_backend.c:610-742 */
+int oracle_rolling_ar1_innovation_variance_f64(const double *v, size_t n, size_t window, double *out)
+{
+    if (v == NULL || out == NULL || n == 0) return -2;
+    window = oracle_wls_spatial_window(n, (int)window);
+    if (window == 0 || n < 4) {
+        memset(out, 0, n * sizeof(double));
+        return 0;
+    }
+    double *at_start = (double *)malloc((n - window + 1) * sizeof(double));
+    if (at_start == NULL) return -1;
+    rolling_at_starts(v, n, window, at_start);
+    expand_starts(at_start, n, window, out);
     free(at_start);
     return 0;
 }
@@ -255,6 +278,20 @@ int oracle_score_centered_wls_f64(const double *centered, size_t K, size_t n, do
                                   double precision_floor_ratio, double *mean, double *raw_var, double *prior_var,
                                   double *mod_var, double *se, double *scores, double *df_out, int *window_out)
 {
+    return oracle_score_centered_wls_given_variances_f64(centered, K, n, lower_bound_z, prior_df, min_effect, use_min_effect,
+                                                         spatial_window, precision_floor_ratio, NULL, mean, raw_var, prior_var,
+                                                         mod_var, se, scores, df_out, window_out);
+}
+
+/* The same scoring with every row's rolling variances handed over: `variances` holds K x (n - window + 1) doubles, row k's
+ * variance of the window that starts at c at [k * (n - window + 1) + c] (ignored for rows shorter than 5 loci, which have
+ * no window); NULL: the oracle's own rolling variances, i.e. oracle_score_centered_wls_f64. */
+int oracle_score_centered_wls_given_variances_f64(const double *centered, size_t K, size_t n, double lower_bound_z,
+                                                  double prior_df, double min_effect, int use_min_effect, int spatial_window,
+                                                  double precision_floor_ratio, const double *variances, double *mean,
+                                                  double *raw_var, double *prior_var, double *mod_var, double *se,
+                                                  double *scores, double *df_out, int *window_out)
+{
     if (centered == NULL || mean == NULL || raw_var == NULL || prior_var == NULL || mod_var == NULL || se == NULL ||
         scores == NULL || K == 0 || n == 0)
         return -2;
@@ -276,7 +313,9 @@ int oracle_score_centered_wls_f64(const double *centered, size_t K, size_t n, do
             sf = fmax(sf * sf, 1.0e-8);
             for (size_t i = 0; i < n; ++i) obs[i] = prior[i] = sf;
         } else {
-            int rc = oracle_rolling_ar1_innovation_variance_f64(row, n, window, obs);
+            int rc = 0;
+            if (variances != NULL) expand_starts(variances + k * (n - window + 1), n, window, obs);
+            else rc = oracle_rolling_ar1_innovation_variance_f64(row, n, window, obs);
             if (rc != 0) {
                 free(buf);
                 return rc == -1 ? -1 : -2;
