@@ -1225,6 +1225,57 @@ int rocco_hip_fragfile_host(rocco_hip_solver *solver, const uint8_t *bytes, size
                             int32_t *weight_out, int32_t *name_out, uint32_t *status_out, int64_t *fields_report_out);
 void rocco_hip_fragfile_shape(int *shape_out);
 
+/* ---- the barcode census of a fragments file (note (35)) -------------------------------------
+ * ccounts_getCellCount (rocco/native/ccounts_backend.c:1890-2046): the distinct barcodes of a whole fragments file under an
+ * optional allow-list -- here with the number of lines of every barcode besides.  The rule of a line (1937-1975; csrc/
+ * fragments_rules.h, frag_barcode_field): fields end at '\t', the scan of the line ends at '\n', '\r' or NUL wherever they
+ * stand, the barcode is field 3; a line whose scan ends before it, whose field 3 is empty (1964) or whose barcode the list
+ * does not hold (1968-1975, ccounts_barcodeAllowed) contributes nothing.  A '#' line is a line; no other column is parsed,
+ * so the dialect errors of rocco_hip_fragfile_fields do not apply.  The reference's khash set (1930, 1999) is replaced by:
+ *
+ * the table: `capacity` (a power of two >= ROCCO_BARCODE_CENSUS_MIN_CAPACITY) 64-bit slots and as many 64-bit counters,
+ *   caller-owned and zeroed before their first use; a slot is 0 (empty) or bit 63 | a 24-bit tag of the masked hash << 39 |
+ *   bit 38 (the payload is an arena entry; clear: a line of the slab in flight) | the index.  The arena: the bytes of the
+ *   barcodes settled so far one behind the other, their entries + 1 offsets (arena_offsets_dev[0] = 0) and their full
+ *   64-bit hashes (frag_hash64).  It persists across the slabs of a file.
+ * rocco_hip_barcode_census_insert: one slab.  One lane per line of starts_dev[n_lines + 1] (ROCCO_FRAGFILE_THREADS lines per
+ *   workgroup turn, a grid stride under ROCCO_BARCODE_CENSUS_MAX_GRID) hashes its barcode, ANDs the hash with hash_mask and
+ *   probes linearly from there: one compare-and-swap on an empty slot; a lane that loses it or finds the slot taken compares
+ *   bytes through the word the atomic returned (the slab's text and the arena were written before the launch) and adds 1 to
+ *   the slot's counter on equal bytes, probes the next slot otherwise.  No lane waits for another; slot words are read
+ *   through agent-scope atomics only.  Then hipcub's exclusive sum over the winners' lengths and a settle kernel copy the new
+ *   representatives into the arena and rewrite their slots to arena form, so that the slab may be released when the call
+ *   returns.  Required (ROCCO_HIP_EINVAL otherwise): capacity >= 2 * (entries + n_lines), arena_entries_capacity >= entries +
+ *   n_lines, arena_bytes_capacity >= arena_used + n_bytes, n_lines < 2^26, n_bytes < 2^38.  With that bound every probe ends;
+ *   a probe of `capacity` steps raises a flag and the call fails with ROCCO_HIP_EINVAL.  allow_*: one sorted packed list, n_allow == 0 for none.
+ *   report_out_host[0..3] = new entries, the bytes they added to the arena, 0, 0.
+ * rocco_hip_barcode_census_rehash: the entries of a table into a larger zeroed-by-this-call table by their stored hashes
+ *   (no barcode byte is read), counters with them.
+ * rocco_hip_barcode_census_records: records_out_dev[e] = the counter of entry e, for the `entries` entries.
+ * rocco_hip_barcode_census_host: the same census over HOST memory on the calling thread, all lines of `bytes` at once, from
+ *   the same header (test support; `solver` may be NULL): a sequential table of initial_capacity slots (raised to the
+ *   minimum) that grows under the same bound.  Entries in the order of their first line.  With the three outputs NULL only
+ *   the report is made: report_out[0..3] = entries, the bytes of all barcodes, lines, grows.
+ * rocco_hip_barcode_census_shape: shape_out[0..3] = ROCCO_FRAGFILE_THREADS, the lines of a workgroup turn (the same),
+ *   ROCCO_BARCODE_CENSUS_MAX_GRID, ROCCO_BARCODE_CENSUS_MIN_CAPACITY. */
+#define ROCCO_BARCODE_CENSUS_MAX_GRID 1024   /* unit: ROCCO_FRAGFILE_THREADS lines or slots (every kernel of barcode_census.hip) */
+#define ROCCO_BARCODE_CENSUS_MIN_CAPACITY 64 /* slots */
+int rocco_hip_barcode_census_insert(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, const int64_t *starts_dev, size_t n_lines,
+                                    const uint8_t *allow_bytes_dev, const int64_t *allow_offsets_dev, size_t n_allow, uint64_t *slots_dev,
+                                    int64_t *counts_dev, size_t capacity, uint8_t *arena_bytes_dev, size_t arena_bytes_capacity,
+                                    int64_t *arena_offsets_dev, uint64_t *arena_hashes_dev, size_t arena_entries_capacity, size_t entries,
+                                    size_t arena_used, uint64_t hash_mask, int64_t *report_out_host, void *stream);
+int rocco_hip_barcode_census_rehash(rocco_hip_solver *solver, const uint64_t *slots_dev, const int64_t *counts_dev, size_t capacity,
+                                    uint64_t *new_slots_dev, int64_t *new_counts_dev, size_t new_capacity, const uint64_t *arena_hashes_dev,
+                                    size_t entries, uint64_t hash_mask, void *stream);
+int rocco_hip_barcode_census_records(rocco_hip_solver *solver, const uint64_t *slots_dev, const int64_t *counts_dev, size_t capacity,
+                                     size_t entries, int64_t *records_out_dev, void *stream);
+int rocco_hip_barcode_census_host(rocco_hip_solver *solver, const uint8_t *bytes, size_t n_bytes, const uint8_t *allow_bytes,
+                                  const int64_t *allow_offsets, size_t n_allow, uint64_t hash_mask, size_t initial_capacity, uint8_t *bytes_out,
+                                  size_t bytes_capacity, int64_t *offsets_out, int64_t *records_out, size_t entries_capacity,
+                                  int64_t *report_out);
+void rocco_hip_barcode_census_shape(int *shape_out);
+
 /* ---- the grid caps of the record and select kernels -----------------------------------------------------------------
  * Every kernel behind the data front end caps its grid; past cap x unit a workgroup takes several units in turn (a grid
  * stride).  The caps are stated here once, the .hip files are built to them, and rocco_hip_launch_caps hands them to the

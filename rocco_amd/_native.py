@@ -389,6 +389,22 @@ PROTOTYPES = [
       ctypes.c_size_t, ctypes.c_void_p, c_ll_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, ctypes.c_void_p,
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p]),
     ("rocco_hip_fragfile_shape", None, [c_int_p]),
+    # row f14 (csrc/barcode_census.hip, csrc/fragments_rules.h): ccounts_getCellCount (ccounts_backend.c:1890-2046) -- the
+    # distinct barcodes of a fragments file, with the lines of each
+    ("rocco_hip_barcode_census_insert", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint64, c_ll_p, ctypes.c_void_p]),
+    ("rocco_hip_barcode_census_rehash", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]),
+    ("rocco_hip_barcode_census_records", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    # (test support: the same census over host memory, on the calling thread)
+    ("rocco_hip_barcode_census_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_ll_p]),
+    ("rocco_hip_barcode_census_shape", None, [c_int_p]),
     # (no reference line: the grid caps of the record and select kernels, for the tests that go past one launch's first turn)
     ("rocco_hip_launch_caps", None, [c_int_p]),
     ("rocco_hip_synth_matrix", ctypes.c_int,

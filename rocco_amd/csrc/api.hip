@@ -2149,6 +2149,100 @@ void rocco_hip_fragfile_shape(int *shape_out)
     shape_out[5] = ROCCO_FRAGFILE_COUNT_MAX_GRID;
 }
 
+// ---- the barcode census (row f14): the checks of every pointer, size and bound the kernels rely on --------------------------
+
+static bool census_table_ok(const void *slots, const void *counts, size_t capacity)
+{
+    return slots != nullptr && counts != nullptr && capacity >= ROCCO_BARCODE_CENSUS_MIN_CAPACITY && capacity <= ((size_t)1 << 40) &&
+           (capacity & (capacity - 1)) == 0;
+}
+
+int rocco_hip_barcode_census_insert(rocco_hip_solver *solver, const uint8_t *bytes_dev, size_t n_bytes, const int64_t *starts_dev, size_t n_lines,
+                                    const uint8_t *allow_bytes_dev, const int64_t *allow_offsets_dev, size_t n_allow, uint64_t *slots_dev,
+                                    int64_t *counts_dev, size_t capacity, uint8_t *arena_bytes_dev, size_t arena_bytes_capacity,
+                                    int64_t *arena_offsets_dev, uint64_t *arena_hashes_dev, size_t arena_entries_capacity, size_t entries,
+                                    size_t arena_used, uint64_t hash_mask, int64_t *report_out_host, void *stream)
+{
+    if (solver == nullptr || report_out_host == nullptr || !census_table_ok(slots_dev, counts_dev, capacity) || starts_dev == nullptr ||
+        (n_bytes > 0 && bytes_dev == nullptr) || n_lines >= ((size_t)1 << 26) || n_bytes >= ((size_t)1 << 38) || n_allow >= ((size_t)1 << 40) ||
+        (n_allow > 0 && (allow_bytes_dev == nullptr || allow_offsets_dev == nullptr)) || arena_offsets_dev == nullptr ||
+        arena_hashes_dev == nullptr || (arena_bytes_capacity > 0 && arena_bytes_dev == nullptr) || entries >= ((size_t)1 << 37) ||
+        arena_used >= ((size_t)1 << 40)) {
+        set_last_error("barcode_census_insert: a null pointer with a size, a capacity that is no power of two from the minimum on, or a size "
+                       "beyond its limit");
+        return ROCCO_HIP_EINVAL;
+    }
+    if (capacity < 2 * (entries + n_lines) || arena_entries_capacity < entries + n_lines || arena_bytes_capacity < arena_used + n_bytes) {
+        set_last_error("barcode_census_insert: the table needs 2 * (entries + n_lines) slots, the arena entries + n_lines entries and "
+                       "arena_used + n_bytes bytes (" + std::to_string(capacity) + " slots, " + std::to_string(arena_entries_capacity) + " entries, " +
+                       std::to_string(arena_bytes_capacity) + " bytes for " + std::to_string(entries) + " entries and " + std::to_string(n_lines) +
+                       " lines)");
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, barcode_census_insert_scratch_bytes(n_lines)); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_barcode_census_insert(bytes_dev, n_bytes, starts_dev, n_lines, allow_bytes_dev, allow_offsets_dev, n_allow, slots_dev, counts_dev,
+                                        capacity, arena_bytes_dev, arena_bytes_capacity, arena_offsets_dev, arena_hashes_dev, arena_entries_capacity,
+                                        entries, arena_used, hash_mask, report_out_host, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_barcode_census_rehash(rocco_hip_solver *solver, const uint64_t *slots_dev, const int64_t *counts_dev, size_t capacity,
+                                    uint64_t *new_slots_dev, int64_t *new_counts_dev, size_t new_capacity, const uint64_t *arena_hashes_dev,
+                                    size_t entries, uint64_t hash_mask, void *stream)
+{
+    if (solver == nullptr || !census_table_ok(slots_dev, counts_dev, capacity) || !census_table_ok(new_slots_dev, new_counts_dev, new_capacity) ||
+        new_capacity < 2 * entries || (entries > 0 && arena_hashes_dev == nullptr) || slots_dev == new_slots_dev || counts_dev == new_counts_dev) {
+        set_last_error("barcode_census_rehash: two distinct tables of a power of two of slots are required, the new one of at least 2 * entries");
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, 256); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_barcode_census_rehash(slots_dev, counts_dev, capacity, new_slots_dev, new_counts_dev, new_capacity, arena_hashes_dev, entries,
+                                        hash_mask, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_barcode_census_records(rocco_hip_solver *solver, const uint64_t *slots_dev, const int64_t *counts_dev, size_t capacity,
+                                     size_t entries, int64_t *records_out_dev, void *stream)
+{
+    if (solver == nullptr || !census_table_ok(slots_dev, counts_dev, capacity) || (entries > 0 && records_out_dev == nullptr)) {
+        set_last_error("barcode_census_records: a table of a power of two of slots and room for the entries' records are required");
+        return ROCCO_HIP_EINVAL;
+    }
+    if (const int rc = enter_record_call(solver, 256); rc != ROCCO_HIP_OK) {
+        return rc;
+    }
+    return launch_barcode_census_records(slots_dev, counts_dev, capacity, entries, records_out_dev, solver->dev_misc.ptr, (hipStream_t)stream);
+}
+
+int rocco_hip_barcode_census_host(rocco_hip_solver *, const uint8_t *bytes, size_t n_bytes, const uint8_t *allow_bytes, const int64_t *allow_offsets,
+                                  size_t n_allow, uint64_t hash_mask, size_t initial_capacity, uint8_t *bytes_out, size_t bytes_capacity,
+                                  int64_t *offsets_out, int64_t *records_out, size_t entries_capacity, int64_t *report_out)
+{
+    if (report_out == nullptr || n_bytes >= ((size_t)1 << 40) || (n_bytes > 0 && bytes == nullptr) || initial_capacity > ((size_t)1 << 40) ||
+        (n_allow > 0 && (allow_bytes == nullptr || allow_offsets == nullptr))) {
+        set_last_error("barcode_census_host: a null pointer with a size, or a size beyond its limit");
+        return ROCCO_HIP_EINVAL;
+    }
+    const FragNames allow = {allow_bytes, allow_offsets, 0, (long long)n_allow};
+    if (!barcode_census_host(bytes, n_bytes, allow, hash_mask, initial_capacity, bytes_out, bytes_capacity, offsets_out, records_out,
+                             entries_capacity, report_out)) {
+        set_last_error("barcode_census_host: the bytes hold " + std::to_string(report_out[0]) + " barcodes of " + std::to_string(report_out[1]) +
+                       " bytes; offsets_out (one more than the entries) and records_out are both required and an output has room for fewer");
+        return ROCCO_HIP_EINVAL;
+    }
+    return ROCCO_HIP_OK;
+}
+
+void rocco_hip_barcode_census_shape(int *shape_out)
+{
+    shape_out[0] = ROCCO_FRAGFILE_THREADS;
+    shape_out[1] = ROCCO_FRAGFILE_THREADS;
+    shape_out[2] = ROCCO_BARCODE_CENSUS_MAX_GRID;
+    shape_out[3] = ROCCO_BARCODE_CENSUS_MIN_CAPACITY;
+}
+
 void rocco_hip_launch_caps(int *out)
 {
     const int caps[] = {ROCCO_SELECT_GRID_TARGET,      ROCCO_SELECT_CHUNK_VALUES,     ROCCO_SELECT_THREADS,           ROCCO_BH_MAX_GRID,

@@ -401,4 +401,171 @@ inline void fragfile_fields_host(const uint8_t *bytes, const int64_t *starts, si
     }
 }
 
+// ---- the barcode census (note (35)): ccounts_getCellCount (1890-2046) -----------------------
+
+// The field the loop at 1937-1975 finds in one line [at, at + length): fields are separated by '\t'; the scan of the line
+// ends at '\n', '\r' or NUL wherever they stand (and at the end of the bytes: hts_getline's string ends there); the barcode is
+// field 3, with or without a field behind it.  false where the scan ends before field 3 or field 3 is empty: the line
+// contributes nothing.  A line that begins with '#' is a line like any other; no other column is parsed or checked.
+ROCCO_FRAGRULES_HD bool frag_barcode_field(const uint8_t *at, long long length, long long *offset, long long *n)
+{
+    long long cursor = 0;
+    int field = 0;
+    while (cursor < length && at[cursor] != 0 && at[cursor] != '\n' && at[cursor] != '\r') {
+        const long long begin = cursor;
+        while (cursor < length && at[cursor] != 0 && at[cursor] != '\t' && at[cursor] != '\n' && at[cursor] != '\r') {
+            ++cursor;
+        }
+        if (field == 3) {
+            *offset = begin;
+            *n = cursor - begin;
+            return cursor > begin;
+        }
+        if (cursor < length && at[cursor] == '\t') {
+            ++cursor;
+        }
+        ++field;
+    }
+    return false;
+}
+
+// a 64-bit hash of a byte string: FNV-1a over the bytes, then the finalizer of splitmix64 (the low bits choose the slot, the
+// high bits the tag: both must mix).  The census is exact whatever this returns; it only decides how long the probes are.
+ROCCO_FRAGRULES_HD uint64_t frag_hash64(const uint8_t *bytes, long long n)
+{
+    uint64_t h = 0xcbf29ce484222325ULL;
+    for (long long i = 0; i < n; ++i) {
+        h = (h ^ (uint64_t)bytes[i]) * 0x100000001b3ULL;
+    }
+    h ^= h >> 30;
+    h *= 0xbf58476d1ce4e5b9ULL;
+    h ^= h >> 27;
+    h *= 0x94d049bb133111ebULL;
+    h ^= h >> 31;
+    return h;
+}
+
+// A slot of the census table: 0 for empty, otherwise bit 63 set, bits 39..62 a tag from the masked hash, bit 38 set where the
+// payload is an arena entry (clear: a line of the current slab), bits 0..37 that index.
+constexpr int kCensusIndexBits = 38;
+constexpr uint64_t kCensusIndexMask = (1ULL << kCensusIndexBits) - 1;
+constexpr uint64_t kCensusArenaBit = 1ULL << kCensusIndexBits;
+constexpr uint64_t kCensusTagMask = ((1ULL << 24) - 1) << 39;
+constexpr uint64_t kCensusTaken = 1ULL << 63;
+
+ROCCO_FRAGRULES_HD uint64_t census_word(uint64_t masked_hash, bool arena, uint64_t index)
+{
+    return kCensusTaken | ((masked_hash >> 1) & kCensusTagMask) | (arena ? kCensusArenaBit : 0) | (index & kCensusIndexMask);
+}
+
+ROCCO_FRAGRULES_HD uint64_t census_first_slot(uint64_t masked_hash, uint64_t capacity) { return masked_hash & (capacity - 1); }
+
+// the smallest power of two that is at least 2 * wanted and at least ROCCO_BARCODE_CENSUS_MIN_CAPACITY
+inline uint64_t census_capacity_for(uint64_t wanted)
+{
+    uint64_t capacity = ROCCO_BARCODE_CENSUS_MIN_CAPACITY;
+    while (capacity < 2 * wanted) {
+        capacity *= 2;
+    }
+    return capacity;
+}
+
+// The host twin: a plain sequential table under the same rule, hash, mask and growth bound, over all lines of `bytes` at
+// once.  The entries come out in the order of their first line; `bytes_out` / `offsets_out` / `records_out` may be null for
+// the sizes alone.  report: entries, the bytes of all barcodes, lines, grows.  false where an output is too small.
+inline bool barcode_census_host(const uint8_t *bytes, size_t n_bytes, const FragNames &allow, uint64_t hash_mask, uint64_t initial_capacity,
+                                uint8_t *bytes_out, size_t bytes_capacity, int64_t *offsets_out, int64_t *records_out, size_t entries_capacity,
+                                int64_t *report)
+{
+    struct Entry {
+        long long at, n;  // the barcode's bytes in `bytes`
+        uint64_t hash;
+        long long records;
+    };
+    uint64_t capacity = census_capacity_for(0);
+    while (capacity < initial_capacity) {
+        capacity *= 2;
+    }
+    // (index + 1 of the entry per slot, 0 for empty; grown by rehashing the stored hashes, as the device table is)
+    size_t n_entries = 0, room = 64, total = 0;
+    long long lines = 0, grows = 0;
+    Entry *entries = new Entry[room];
+    uint64_t *slots = new uint64_t[capacity]();
+    size_t p = 0;
+    while (p < n_bytes) {
+        size_t end = p;
+        while (end < n_bytes && bytes[end] != '\n') {
+            ++end;
+        }
+        const long long length = (long long)(end < n_bytes ? end + 1 : end) - (long long)p;
+        ++lines;
+        long long offset = 0, n = 0;
+        if (frag_barcode_field(bytes + p, length, &offset, &n) && frag_allowed(allow, bytes + p + offset, n)) {
+            if (capacity < 2 * (n_entries + 1)) {
+                const uint64_t grown = census_capacity_for(n_entries + 1);
+                uint64_t *fresh = new uint64_t[grown]();
+                for (size_t e = 0; e < n_entries; ++e) {
+                    uint64_t slot = census_first_slot(entries[e].hash & hash_mask, grown);
+                    while (fresh[slot] != 0) {
+                        slot = (slot + 1) & (grown - 1);
+                    }
+                    fresh[slot] = e + 1;
+                }
+                delete[] slots;
+                slots = fresh;
+                capacity = grown;
+                ++grows;
+            }
+            const uint64_t hash = frag_hash64(bytes + p + offset, n);
+            uint64_t slot = census_first_slot(hash & hash_mask, capacity);
+            while (slots[slot] != 0) {
+                const Entry &e = entries[slots[slot] - 1];
+                if (e.n == n && frag_compare(bytes + e.at, e.n, bytes + p + offset, n) == 0) {
+                    break;
+                }
+                slot = (slot + 1) & (capacity - 1);
+            }
+            if (slots[slot] == 0) {
+                if (n_entries == room) {
+                    Entry *more = new Entry[2 * room];
+                    for (size_t e = 0; e < n_entries; ++e) {
+                        more[e] = entries[e];
+                    }
+                    delete[] entries;
+                    entries = more;
+                    room *= 2;
+                }
+                entries[n_entries] = {(long long)p + offset, n, hash, 0};
+                slots[slot] = ++n_entries;
+                total += (size_t)n;
+            }
+            ++entries[slots[slot] - 1].records;
+        }
+        p = end < n_bytes ? end + 1 : end;
+    }
+    report[0] = (int64_t)n_entries;
+    report[1] = (int64_t)total;
+    report[2] = lines;
+    report[3] = grows;
+    bool fits = true;
+    if (offsets_out != nullptr || records_out != nullptr || bytes_out != nullptr) {
+        fits = offsets_out != nullptr && (records_out != nullptr || n_entries == 0) && entries_capacity >= n_entries && bytes_capacity >= total &&
+               (bytes_out != nullptr || total == 0);
+        if (fits) {
+            size_t to = 0;
+            offsets_out[0] = 0;
+            for (size_t e = 0; e < n_entries; ++e) {
+                for (long long j = 0; j < entries[e].n; ++j) {
+                    bytes_out[to++] = bytes[entries[e].at + j];
+                }
+                offsets_out[e + 1] = (int64_t)to;
+                records_out[e] = entries[e].records;
+            }
+        }
+    }
+    delete[] entries;
+    delete[] slots;
+    return fits;
+}
+
 }  // namespace rocco

@@ -464,6 +464,20 @@ int launch_fragfile_chrom_range_batch(const int32_t *start_dev, const int32_t *e
 int launch_fragfile_mapped_count(const int32_t *weight_dev, const int32_t *name_dev, const uint32_t *status_dev, size_t n_lines, int count_mode,
                                  int one_read_per_bin, uint64_t *sum_out_host, void *scratch_dev, hipStream_t stream);
 
+// ---- barcode_census.hip -----------------------------------------------------------------------
+// the distinct barcodes of a fragments file and the lines of each (row f14); rule, hash, slot word and host twin are fragments_rules.h's
+size_t barcode_census_insert_scratch_bytes(size_t n_lines);
+int launch_barcode_census_insert(const uint8_t *bytes_dev, size_t n_bytes, const int64_t *starts_dev, size_t n_lines, const uint8_t *allow_bytes_dev,
+                                 const int64_t *allow_offsets_dev, size_t n_allow, uint64_t *slots_dev, int64_t *counts_dev, size_t capacity,
+                                 uint8_t *arena_bytes_dev, size_t arena_bytes_capacity, int64_t *arena_offsets_dev, uint64_t *arena_hashes_dev,
+                                 size_t arena_entries_capacity, size_t entries, size_t arena_used, uint64_t hash_mask, int64_t *report_out_host,
+                                 void *scratch_dev, hipStream_t stream);
+int launch_barcode_census_rehash(const uint64_t *slots_dev, const int64_t *counts_dev, size_t capacity, uint64_t *new_slots_dev,
+                                 int64_t *new_counts_dev, size_t new_capacity, const uint64_t *arena_hashes_dev, size_t entries, uint64_t hash_mask,
+                                 void *scratch_dev, hipStream_t stream);
+int launch_barcode_census_records(const uint64_t *slots_dev, const int64_t *counts_dev, size_t capacity, size_t entries, int64_t *records_out_dev,
+                                  void *scratch_dev, hipStream_t stream);
+
 // ---- synth.hip ------------------------------------------------------------------------------
 int launch_synth(void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride, uint64_t seed,
                  hipStream_t stream);

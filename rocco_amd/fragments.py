@@ -10,8 +10,14 @@ and K allow-lists (one per cluster) become a K-row pseudo-bulk count matrix with
 (`generate_chrom_matrix_device`); the file is inflated and split into lines once for all K.
 
 Read: the dialect of DESIGN.md note (34) -- what tabix's own parser and the reference's strict parser read alike.  A span
-that leaves it is a ValueError naming the file, the contig, the line and the rule; there is no CPU fallback.  Not read:
-``.csi`` and ``.tbi.csi`` indexes, plain-gzip files, the reference's ``ccounts_getCellCount``, its unused ``barcodeTag`` /
+that leaves it is a ValueError naming the file, the contig, the line and the rule; there is no CPU fallback.
+
+Which barcodes a file holds, how many lines each has and how many cells an allow-list really matches (row f14, note (35);
+csrc/barcode_census.hip): `barcode_census` walks the whole file once on the device and returns a `BarcodeCensus`;
+`get_fragments_cell_count` is the reference's ``ccounts_getCellCount``; `BarcodeCensus.write_allowlist` writes the list that
+`FragmentsSource` reads back -- cell calling by fragments per barcode without a second tool or a second inflate.
+
+Not read: ``.csi`` and ``.tbi.csi`` indexes, plain-gzip files, the reference's unused ``barcodeTag`` /
 ``barcodeGroupMapFile``, tabix presets other than BED."""
 from __future__ import annotations
 
@@ -683,6 +689,271 @@ def get_fragments_mapped_read_count(source, exclude_chromosomes=(), count_mode: 
                 ordinal += n_lines
             slab = following
     return total, 0
+
+
+# --------------------------------------------------------------------------------------------
+# the barcode census: the distinct barcodes of a file and the lines of each (row f14, note (35))
+# --------------------------------------------------------------------------------------------
+
+ALL_HASH_BITS = (1 << 64) - 1
+_ALLOWLIST_SPACE = b" \t\n\v\f\r"
+
+
+def barcode_census_shape() -> dict:
+    """`rocco_hip_barcode_census_shape`: the sizes at which the census kernels take a second turn and the smallest table.
+    No device is touched."""
+    shape = (ctypes.c_int * 4)()
+    _native.load().rocco_hip_barcode_census_shape(shape)
+    return {"threads": int(shape[0]), "lines_per_turn": int(shape[1]), "max_grid": int(shape[2]), "min_capacity": int(shape[3])}
+
+
+class BarcodeCensus:
+    """The distinct barcodes of a fragments file (or of some text) and how many lines each has.  ``packed``: (the barcodes'
+    bytes one behind the other as uint8, the D + 1 offsets as int64), the layout of `parse_barcode_allowlist`, ordered as
+    ``strcmp`` orders, bytes compared unsigned; ``barcodes``: the same as a list of ``bytes``; ``records``: int64, the lines
+    per barcode; ``lines``: the lines read, with or without a barcode; ``stats``: ``capacity`` (slots of the table at the
+    end), ``grows``, ``slabs``, ``entries``, ``status`` (of the last native call).  ``len()`` is the reference's cell count.
+    The order is made on the host over the D distinct entries, never over the lines."""
+
+    __slots__ = ("packed", "records", "lines", "stats", "_barcodes")
+
+    def __init__(self, raw: np.ndarray, offsets: np.ndarray, records: np.ndarray, lines: int, stats: dict):
+        raw, offsets = np.ascontiguousarray(raw, dtype=np.uint8), np.ascontiguousarray(offsets, dtype=np.int64)
+        found = [raw[int(offsets[e]): int(offsets[e + 1])].tobytes() for e in range(len(offsets) - 1)]
+        order = sorted(range(len(found)), key=found.__getitem__)  # (bytes compare unsigned, the shorter of two first: strcmp without NUL)
+        self._barcodes = [found[e] for e in order]
+        sorted_offsets = np.zeros(len(order) + 1, dtype=np.int64)
+        np.cumsum([len(b) for b in self._barcodes], out=sorted_offsets[1:])
+        self.packed = (np.frombuffer(b"".join(self._barcodes), dtype=np.uint8).copy(), sorted_offsets)
+        self.records = np.ascontiguousarray(records, dtype=np.int64)[order] if order else np.zeros(0, dtype=np.int64)
+        self.lines, self.stats = int(lines), dict(stats, entries=len(order))
+
+    @property
+    def barcodes(self) -> List[bytes]:
+        return list(self._barcodes)
+
+    def __len__(self) -> int:
+        return len(self._barcodes)
+
+    def write_allowlist(self, path, min_records: int = 1) -> int:
+        """One barcode per line, those with at least ``min_records`` lines, in census order, so that
+        ``FragmentsSource(file, path)`` admits exactly those.  ValueError naming the barcode for one the allow-list loader
+        (`parse_barcode_allowlist`) could not read back: whitespace inside it, a leading ``#``, 4 095 bytes or more (with its
+        line feed it would not fit the reference's 4 096-byte buffer).  Nothing is written then.  Returns how many it wrote."""
+        kept = [b for b, n in zip(self._barcodes, self.records.tolist()) if n >= int(min_records)]
+        for barcode in kept:
+            why = ("it holds whitespace" if any(c in _ALLOWLIST_SPACE for c in barcode) else "it begins with `#`" if barcode.startswith(b"#") else
+                   f"it has {len(barcode)} bytes, the reference's buffer of {ALLOWLIST_LINE_BYTES} takes {ALLOWLIST_LINE_BYTES - 2} and a line feed"
+                   if len(barcode) >= ALLOWLIST_LINE_BYTES - 1 else "it holds a NUL byte" if b"\x00" in barcode else None)
+            if why:
+                shown = barcode if len(barcode) <= 64 else barcode[:64] + b"..."
+                raise ValueError(f"write_allowlist: the barcode {shown!r} cannot stand in an allow-list: {why}")
+        with open(os.fspath(path), "wb") as handle:
+            handle.write(b"".join(b + b"\n" for b in kept))
+        return len(kept)
+
+
+def _census_arguments(hash_mask, initial_capacity) -> Tuple[int, int]:
+    mask = ALL_HASH_BITS if hash_mask is None else int(hash_mask)
+    if not 0 <= mask <= ALL_HASH_BITS:
+        raise ValueError("hash_mask must be a 64-bit pattern")
+    capacity = barcode_census_shape()["min_capacity"]
+    if initial_capacity is not None and int(initial_capacity) < 1:
+        raise ValueError("initial_capacity must be positive")
+    while initial_capacity is not None and capacity < int(initial_capacity):
+        capacity *= 2
+    return mask, capacity
+
+
+def barcode_census_host(data, allowlist: Tuple[np.ndarray, np.ndarray] = _NO_LIST, hash_mask: Optional[int] = None,
+                        initial_capacity: Optional[int] = None) -> BarcodeCensus:
+    """`rocco_hip_barcode_census_host`: the census of all lines of host bytes on the calling thread, from the rules header the
+    kernels compile, every array at its exact size (test support; no device is touched)."""
+    out_bytes, offsets, records, lines, grows, capacity = barcode_census_host_arrays(data, allowlist, hash_mask, initial_capacity)
+    return BarcodeCensus(out_bytes, offsets, records, lines, {"capacity": capacity, "grows": grows, "slabs": 1, "status": _native.OK})
+
+
+def barcode_census_host_arrays(data, allowlist: Tuple[np.ndarray, np.ndarray] = _NO_LIST, hash_mask: Optional[int] = None,
+                               initial_capacity: Optional[int] = None):
+    """What `rocco_hip_barcode_census_host` writes, as it writes it: (the barcodes' bytes, the D + 1 offsets, the records -- in
+    the order of the barcodes' first lines --, lines, grows, the capacity at the end)."""
+    lib = _native.load()
+    mask, capacity = _census_arguments(hash_mask, initial_capacity)
+    raw = np.frombuffer(bytes(data), dtype=np.uint8).copy() if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    allow_bytes, allow_offsets = np.ascontiguousarray(allowlist[0], dtype=np.uint8), np.ascontiguousarray(allowlist[1], dtype=np.int64)
+    n_allow = len(allow_offsets) - 1
+    head = (raw.ctypes.data if raw.size else None, raw.size, allow_bytes.ctypes.data if allow_bytes.size else None,
+            allow_offsets.ctypes.data if n_allow else None, n_allow, mask, capacity)
+    report = (ctypes.c_longlong * 4)()
+    _native.check(lib.rocco_hip_barcode_census_host(None, *head, None, 0, None, None, 0, report), "rocco_hip_barcode_census_host")
+    entries, total = int(report[0]), int(report[1])
+    out_bytes, offsets, records = np.empty(total, dtype=np.uint8), np.empty(entries + 1, dtype=np.int64), np.empty(entries, dtype=np.int64)
+    _native.check(lib.rocco_hip_barcode_census_host(None, *head, out_bytes.ctypes.data if total else None, total, offsets.ctypes.data,
+                                                    records.ctypes.data, entries, report), "rocco_hip_barcode_census_host")
+    final = capacity
+    while final < 2 * entries:
+        final *= 2
+    return out_bytes, offsets, records, int(report[2]), int(report[3]), final
+
+
+class BarcodeCensusTable:
+    """The device structure of the census: an open-addressing table of 64-bit slots with a 64-bit counter each, and an arena
+    with the bytes, offsets and hashes of the barcodes settled so far, as CUDA tensors this object owns.  `insert` takes one
+    slab (text in HBM and its line starts), `census` hands the result to the host.  Before a slab the table is grown by
+    `rocco_hip_barcode_census_rehash` until it has twice as many slots as there are entries and lines of the slab together;
+    with that bound every probe ends.  ``allowlist``: a packed, sorted list (`parse_barcode_allowlist`), applied per line."""
+
+    def __init__(self, device=None, allowlist: Tuple[np.ndarray, np.ndarray] = _NO_LIST, hash_mask: Optional[int] = None,
+                 initial_capacity: Optional[int] = None):
+        import torch
+
+        self.device = _dp._device(device)
+        self.mask, self.capacity = _census_arguments(hash_mask, initial_capacity)
+        self.entries = self.used = self.lines = self.grows = self.slabs = 0
+        self.status = _native.OK
+        self.n_allow = len(allowlist[1]) - 1
+        with torch.cuda.device(self.device):
+            self.allow_bytes = torch.from_numpy(np.ascontiguousarray(allowlist[0], dtype=np.uint8)).to(self.device)
+            self.allow_offsets = torch.from_numpy(np.ascontiguousarray(allowlist[1], dtype=np.int64)).to(self.device)
+            self.slots = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
+            self.counts = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
+            self.arena_bytes = torch.empty(0, dtype=torch.uint8, device=self.device)
+            self.arena_offsets = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self.arena_hashes = torch.empty(0, dtype=torch.int64, device=self.device)
+
+    def _solver(self):
+        return _native.solver_for(self.device.index).handle
+
+    def _room(self, n_lines: int, n_bytes: int, stream) -> None:
+        import torch
+
+        need = self.entries + n_lines
+        if self.capacity < 2 * need:
+            capacity = self.capacity
+            while capacity < 2 * need:
+                capacity *= 2
+            slots = torch.empty(capacity, dtype=torch.int64, device=self.device)
+            counts = torch.empty(capacity, dtype=torch.int64, device=self.device)
+            self.status = _native.load().rocco_hip_barcode_census_rehash(
+                self._solver(), self.slots.data_ptr(), self.counts.data_ptr(), self.capacity, slots.data_ptr(), counts.data_ptr(), capacity,
+                self.arena_hashes.data_ptr(), self.entries, self.mask, stream)
+            _native.check(self.status, "rocco_hip_barcode_census_rehash")
+            self.slots, self.counts, self.capacity, self.grows = slots, counts, capacity, self.grows + 1
+        if int(self.arena_hashes.shape[0]) < max(need, 1):
+            room = max(need, 1, 2 * int(self.arena_hashes.shape[0]))
+            offsets = torch.zeros(room + 1, dtype=torch.int64, device=self.device)
+            hashes = torch.empty(room, dtype=torch.int64, device=self.device)
+            offsets[: self.entries + 1] = self.arena_offsets[: self.entries + 1]
+            hashes[: self.entries] = self.arena_hashes[: self.entries]
+            self.arena_offsets, self.arena_hashes = offsets, hashes
+        if int(self.arena_bytes.shape[0]) < self.used + n_bytes:
+            grown = torch.empty(max(self.used + n_bytes, 2 * int(self.arena_bytes.shape[0])), dtype=torch.uint8, device=self.device)
+            grown[: self.used] = self.arena_bytes[: self.used]
+            self.arena_bytes = grown
+
+    def insert(self, bytes_t, starts_t, n_bytes: Optional[int] = None) -> Tuple[int, int]:
+        """`rocco_hip_barcode_census_insert` of the lines ``starts_t`` (n_lines + 1 starts, as `lines_device` gives them) of the
+        text ``bytes_t``: (new entries, the bytes they added to the arena).  The slab is not needed afterwards."""
+        import torch
+
+        if (not _dp._is_tensor(bytes_t) or bytes_t.dtype != torch.uint8 or bytes_t.dim() != 1 or bytes_t.device != self.device or
+                not _dp._is_tensor(starts_t) or starts_t.dtype != torch.int64 or starts_t.dim() != 1 or starts_t.device != self.device or
+                int(starts_t.shape[0]) < 1):
+            raise TypeError("BarcodeCensusTable.insert: a uint8 tensor and the int64 tensor of its n_lines + 1 line starts, on the table's device, are required")
+        bytes_t, starts_t = bytes_t.contiguous(), starts_t.contiguous()
+        n = int(bytes_t.shape[0]) if n_bytes is None else int(n_bytes)
+        n_lines = int(starts_t.shape[0]) - 1
+        if not 0 <= n <= int(bytes_t.shape[0]):
+            raise ValueError("BarcodeCensusTable.insert: n_bytes lies outside the tensor")
+        report = (ctypes.c_longlong * 4)()
+        with torch.cuda.device(self.device):
+            stream = _dp._stream_ptr(bytes_t)
+            self._room(n_lines, n, stream)
+            self.status = _native.load().rocco_hip_barcode_census_insert(
+                self._solver(), bytes_t.data_ptr(), n, starts_t.data_ptr(), n_lines, self.allow_bytes.data_ptr(), self.allow_offsets.data_ptr(),
+                self.n_allow, self.slots.data_ptr(), self.counts.data_ptr(), self.capacity, self.arena_bytes.data_ptr(),
+                int(self.arena_bytes.shape[0]), self.arena_offsets.data_ptr(), self.arena_hashes.data_ptr(), int(self.arena_hashes.shape[0]),
+                self.entries, self.used, self.mask, report, stream)
+            _native.check(self.status, "rocco_hip_barcode_census_insert")
+        self.entries, self.used = self.entries + int(report[0]), self.used + int(report[1])
+        self.lines, self.slabs = self.lines + n_lines, self.slabs + 1
+        return int(report[0]), int(report[1])
+
+    def census(self) -> BarcodeCensus:
+        """`rocco_hip_barcode_census_records`, then the D entries go to the host and are put in order there."""
+        import torch
+
+        with torch.cuda.device(self.device):
+            records = torch.zeros(self.entries, dtype=torch.int64, device=self.device)
+            self.status = _native.load().rocco_hip_barcode_census_records(
+                self._solver(), self.slots.data_ptr(), self.counts.data_ptr(), self.capacity, self.entries, records.data_ptr(),
+                _dp._stream_ptr(self.slots))
+            _native.check(self.status, "rocco_hip_barcode_census_records")
+            return BarcodeCensus(self.arena_bytes[: self.used].cpu().numpy(), self.arena_offsets[: self.entries + 1].cpu().numpy(),
+                                 records.cpu().numpy(), self.lines,
+                                 {"capacity": self.capacity, "grows": self.grows, "slabs": self.slabs, "status": self.status})
+
+
+def barcode_census_device(bytes_t, starts_t=None, allowlist: Tuple[np.ndarray, np.ndarray] = _NO_LIST, hash_mask: Optional[int] = None,
+                          initial_capacity: Optional[int] = None, n_bytes: Optional[int] = None) -> BarcodeCensus:
+    """The census of text that already lies in HBM: a one-dimensional uint8 CUDA tensor and, where the caller has them, its
+    line starts (`lines_device` makes them otherwise).  Several slabs go through one `BarcodeCensusTable`."""
+    if starts_t is None:
+        starts_t, _ = lines_device(bytes_t, 0, n_bytes)
+    table = BarcodeCensusTable(bytes_t.device, allowlist, hash_mask, initial_capacity)
+    table.insert(bytes_t, starts_t, n_bytes)
+    return table.census()
+
+
+def barcode_census(source, device=None, inflate: Optional[str] = None, slab_bytes: int = DEFAULT_SLAB_BYTES, threads: Optional[int] = None,
+                   hash_mask: Optional[int] = None, initial_capacity: Optional[int] = None) -> BarcodeCensus:
+    """The distinct barcodes of the WHOLE fragments file ``source`` (a path or a `FragmentsSource`; its allow-list, where it
+    has one, is applied per line) and the lines of each, in one pass on the device: the file goes through in slabs cut at
+    BGZF block boundaries exactly as `get_fragments_mapped_read_count` walks it -- host or device inflate, the unfinished
+    last line of a slab carried into the next --, every slab through the line pass and `BarcodeCensusTable.insert`.
+
+    The rule of a line is ``ccounts_getCellCount``'s (ccounts_backend.c:1937-1975), not the field pass's: fields end at TAB,
+    the scan of a line ends at LF, CR or NUL, the barcode is field 3; a line without one or with an empty one contributes
+    nothing; a ``#`` line is a line like any other; an unterminated last line is read.  No other column is parsed, so the
+    dialect errors of the field pass (`_ERROR_TEXT`) do NOT apply to this call: a file the count refuses has a census.
+    ``hash_mask`` (ANDed with every hash; the result never depends on it) and ``initial_capacity`` are for tests."""
+    import torch
+
+    source = _as_source(source)
+    inflate = _bam.DEFAULT_INFLATE if inflate is None else inflate
+    if inflate not in ("host", "device"):
+        raise ValueError(f"barcode_census: inflate must be \"host\" or \"device\", not {inflate!r}")
+    dev = _dp._device(device)
+    table, carry = BarcodeCensusTable(dev, source.allowlist(), hash_mask, initial_capacity), None
+    with torch.cuda.device(dev):
+        slabs = iter(_whole_file_slabs(source, dev, inflate, max(1, int(slab_bytes)), threads))
+        slab = next(slabs, None)
+        while slab is not None:
+            following = next(slabs, None)
+            data = slab if carry is None or not int(carry.shape[0]) else torch.cat([carry, slab])
+            n, carry = int(data.shape[0]), None
+            starts, report = lines_device(data)
+            n_lines = report["lines"]
+            if following is not None and report["open"]:
+                n_lines, n = n_lines - 1, report["cut"]
+                starts, carry = starts[: n_lines + 1], data[n:].clone()
+            if n_lines:
+                table.insert(data, starts, n_bytes=n)
+            slab = following
+    return table.census()
+
+
+def get_fragments_cell_count(source, device=None, inflate: Optional[str] = None, slab_bytes: int = DEFAULT_SLAB_BYTES,
+                             threads: Optional[int] = None) -> int:
+    """``ccounts_getCellCount`` (ccounts_backend.c:1890-2046): the number of distinct barcodes of a fragments file under the
+    source's allow-list, ``len(barcode_census(...))``.  The index is opened first, as the reference opens the source with it
+    (RuntimeError with the reference's words for a file without one); a ``.bam`` path is the reference's RuntimeError "cell
+    count is only supported for fragments sources"."""
+    source = _as_source(source)
+    if source.path.lower().endswith(".bam"):
+        raise RuntimeError("cell count is only supported for fragments sources")
+    _index_of(source)
+    return len(barcode_census(source, device=device, inflate=inflate, slab_bytes=slab_bytes, threads=threads))
 
 
 def get_fragments_read_length(source, min_reads: int = 32, max_iterations: int = 4096) -> int:
