@@ -124,7 +124,9 @@ int rocco_hip_score_percentile_range(rocco_hip_solver *solver, const void *matri
 /* method="std" (rocco.py:328-329, np.std(m, axis=0)): sum / K, the squared deviations summed and divided by K, sqrt.
  * Summation order, both sums alike: pairwise_order == 0 adds the rows one after the other, as NumPy reduces axis 0 of a
  * matrix with n > 1; pairwise_order != 0 adds the K entries of each column in NumPy's pairwise order (see
- * rocco_hip_score_trimmed_mean), as NumPy reduces the single column of a K x 1 matrix -- K <= 1024 then. */
+ * rocco_hip_score_trimmed_mean), as NumPy reduces the single column of a K x 1 matrix -- K <= 1024 then (ROCCO_HIP_EINVAL
+ * above; see rocco_hip_score_trimmed_std).  In the pairwise order finite entries can give NaN, as in NumPy: +-1.5e308 in
+ * turn over K >= 16 rows drive one of the eight accumulators to +inf and its neighbour to -inf.  Row after row they cannot. */
 int rocco_hip_score_std(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n, size_t row_stride,
                         int pairwise_order, double *scores_dev, void *stream);
 
@@ -142,7 +144,10 @@ int rocco_hip_score_std(rocco_hip_solver *solver, const void *matrix_dev, int dt
  * function on every host, so no device algorithm reproduces it everywhere.
  * The sort destroys the row order the sums need: for K <= 80 and K == 100 an unpermuted copy of the column stays in
  * registers beside the sorted one (one read of the matrix); only for 80 < K < 100 the column is read a second time.
- * K <= 1024 (the written-out depth of the pairwise order); ROCCO_HIP_EINVAL above. */
+ * K <= 1024, ROCCO_HIP_EINVAL above: the pairwise order (ranges of more than 128 terms split at n/2 rounded DOWN TO A
+ * MULTIPLE OF 8, so into uneven halves) is written out to four levels (rocco_amd/csrc/pairwise_sum.h), which is NumPy's
+ * order for every K up to 1928; three levels leave a block of more than 128 terms from K = 969 on.  Kept values near the
+ * overflow threshold can give NaN where all are finite (see rocco_hip_score_std), as they do in SciPy. */
 int rocco_hip_score_trimmed_std(rocco_hip_solver *solver, const void *matrix_dev, int dtype, size_t K, size_t n,
                                 size_t row_stride, int rank_lo, int rank_hi, int take_root, double *scores_dev, void *stream);
 

@@ -17,12 +17,15 @@
 //                                column is READ A SECOND TIME into the sorted registers instead: 16 K read, of which
 //                                the second 8 K follow the first from the same workgroup (a cache hit where the
 //                                256 x K tile is still resident).
-// K > 100: rank counting and plain loops over memory (O(K^2) reads served from L1 / L2).  Correct for any K the
-// summation order allows; NO speed claim is attached to that path.
+// K > 100: rank counting and plain loops over memory (O(K^2) reads served from L1 / L2).  mad, iqr and the row-after-row
+// std take any K; tstd and the std of a single column, which sum in NumPy's pairwise order, take K <= kPairwiseMax = 1024.
+// NO speed claim is attached to that path.
 //
 // Every kernel here keeps its arrays in registers with compile-time indices and calls nothing recursive: the private
-// segment is 0 bytes (NumPy's pairwise order is unrolled to a fixed depth instead, see pairwise()).
+// segment is 0 bytes (NumPy's pairwise order is written out to kPairwiseDepth = 4 levels instead, see pairwise_sum.h:
+// NumPy's halves are uneven, and three levels leave a block of more than 128 terms from K = 969 on).
 #include "kernels.h"
+#include "pairwise_sum.h"
 #include "select_network.h"
 
 #include <limits>
@@ -38,10 +41,16 @@ constexpr int kNetworkMax = 100;  // largest column the register kernels take
 // under -fno-honor-nans a function's double result is declared NaN-free, and a result known to be NaN is folded away.
 #define ROCCO_QUIET_NAN __longlong_as_double(0x7FF8000000000000LL)
 
-__device__ __forceinline__ bool is_finite_bits(double x)
-{
-    return (__double_as_longlong(x) & 0x7FF0000000000000LL) != 0x7FF0000000000000LL;
-}
+// A COMPUTED value whose bit pattern is to be tested goes through an empty asm statement first: this file's arithmetic is
+// declared NaN-free, and what the compiler can trace of a result's origin it may use on the bit tests.  Behind the asm
+// statement they are the integer compares they are written as.  Statements, not functions: see ROCCO_QUIET_NAN.
+#define ROCCO_OPAQUE(variable) asm volatile("" : "+v"(variable))
+#define ROCCO_COMPUTED_IS_NAN(flag, value)                                                                                     \
+    do {                                                                                                                       \
+        double probe_ = (value);                                                                                               \
+        ROCCO_OPAQUE(probe_);                                                                                                  \
+        (flag) = is_nan_bits(probe_);                                                                                          \
+    } while (0)
 
 // the upper 32 bits of |x|: at least kNonFiniteTop exactly for an infinity or a NaN
 constexpr unsigned kNonFiniteTop = 0x7FF00000U;
@@ -50,15 +59,35 @@ __device__ __forceinline__ unsigned magnitude_top(double x)
     return (unsigned)((unsigned long long)__double_as_longlong(x) >> 32) & 0x7FFFFFFFU;
 }
 
+// FOR VALUES THAT ARE NO NaN ONLY (the limits of tstd: entries of a column without NaN).  The compiler recognises every
+// test of the exponent bits, and the hardware class test too, as a class test and -- the file being declared NaN-free --
+// compiles it to the floating-point compare |x| != inf, which calls a NaN finite; an empty asm statement on the way does
+// not help.  What survives as written are is_nan_bits() (an integer compare) and is_inf_bits(): a value that may be NaN is
+// asked those two, one after the other (the median of MAD, which is NaN for -inf and +inf in the middle).
+__device__ __forceinline__ bool is_finite_bits(double x)
+{
+    return (__double_as_longlong(x) & 0x7FF0000000000000LL) != 0x7FF0000000000000LL;
+}
+
+// +inf or -inf; false for a NaN, also where it is compiled to |x| == inf
+__device__ __forceinline__ bool is_inf_bits(double x)
+{
+    return (__double_as_longlong(x) & 0x7FFFFFFFFFFFFFFFLL) == 0x7FF0000000000000LL;
+}
+
 // tstd: the answer where the arithmetic does not give it.  The limits are the smallest and the largest kept value, so an
 // infinite limit is a kept infinity and the mean is infinite with it.  SciPy 1.15 (stats.tvar -> _xp_var with
 // nan_policy="omit") leaves the NaN deviations (inf - inf) OUT of the second mean: with one infinite limit the finite
 // kept values are infinitely far from the mean and the variance is +inf; with two (of either signs) no deviation is
-// left, or the mean itself is NaN: NaN.  Finite kept values give no NaN (an overflowing sum stays infinite).  Decided
-// on the bit patterns of the limits, never on `computed`: this file's arithmetic is declared NaN-free.  Stores to `r`
-// instead of returning, see ROCCO_QUIET_NAN.
-#define trimmed_result(column_has_nan, kept_count, lo, hi, computed)                                                         \
-    (((column_has_nan) || (kept_count) <= 1.0 || (!is_finite_bits(lo) && !is_finite_bits(hi)))                                \
+// left, or the mean itself is NaN: NaN.  Finite kept values CAN give NaN as well, in NumPy as here: the pairwise order
+// keeps eight accumulators, and on entries near the overflow threshold of alternating sign (+-1.5e308, K >= 16) one of
+// them reaches +inf and its neighbour -inf.  That NaN is not decided here: it comes out of the additions of `computed`
+// themselves, which the hardware performs as IEEE 754 states whatever the compiler may assume.  The same overflow beside
+// ONE infinite limit (a kept -inf, finite kept values whose sum reaches +inf) makes the mean NaN, every deviation with it,
+// and SciPy's answer NaN instead of +inf: `mean_is_nan`, from ROCCO_COMPUTED_IS_NAN.  Everything else is decided on the
+// bit patterns of the limits, never by testing `computed`.  Stores to `r` instead of returning, see ROCCO_QUIET_NAN.
+#define trimmed_result(column_has_nan, mean_is_nan, kept_count, lo, hi, computed)                                            \
+    (((column_has_nan) || (mean_is_nan) || (kept_count) <= 1.0 || (!is_finite_bits(lo) && !is_finite_bits(hi)))               \
          ? ROCCO_QUIET_NAN                                                                                                    \
          : ((!is_finite_bits(lo) || !is_finite_bits(hi)) ? std::numeric_limits<double>::infinity() : (computed)))
 
@@ -70,56 +99,8 @@ __device__ __forceinline__ double lerp(double a, double b, double g)
     return (g >= 0.5) ? (b - d * (1.0 - g)) : (a + d * g);
 }
 
-// ---- NumPy's pairwise sum (numpy/_core/src/umath/loops_utils.h.src), term(i) the i-th addend ------------------
-// fewer than 8 terms one after the other; up to 128 with eight interleaved accumulators combined as
-// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and the remainder appended; longer ranges split at n/2 rounded down to a
-// multiple of 8.  The recursion is written out to DEPTH levels (no call, no stack): DEPTH = 3 sums 128 * 2^3 terms.
-constexpr int kPairwiseDepth = 3;
-constexpr int kPairwiseMax = 128 << kPairwiseDepth;
-
-template <typename F>
-__device__ __forceinline__ double pairwise_block(int start, int n, F term)
-{
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) {
-            res += term(start + i);
-        }
-        return res;
-    }
-    double r[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        r[q] = term(start + q);
-    }
-    int i;
-    for (i = 8; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            r[q] += term(start + i + q);
-        }
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) {
-        res += term(start + i);
-    }
-    return res;
-}
-
-template <int DEPTH, typename F>
-__device__ __forceinline__ double pairwise(int start, int n, F term)
-{
-    if constexpr (DEPTH == 0) {
-        return pairwise_block(start, n, term);
-    } else {
-        if (n <= 128) {
-            return pairwise_block(start, n, term);
-        }
-        int n2 = n / 2;
-        n2 -= n2 % 8;
-        return pairwise<DEPTH - 1>(start, n2, term) + pairwise<DEPTH - 1>(start + n2, n - n2, term);
-    }
-}
+// NumPy's pairwise sum over memory -- pairwise_block(), pairwise<DEPTH>() and kPairwiseDepth / kPairwiseMax -- is in
+// pairwise_sum.h, which a host program compiles too (tests/tools/pairwise_order_check.cpp).
 
 // the same order over the first K (<= KP <= 128) entries of a register array: every index a compile-time constant, the
 // conditions on K uniform across the wavefront
@@ -270,9 +251,10 @@ __global__ __launch_bounds__(256) void dispersion_kernel(const T *__restrict__ m
                 acc += d * d;
             }
         }
-        // NumPy answers NaN exactly when the column holds a NaN or an infinity (inf - inf among the deviations): finite
-        // entries give no NaN, an overflowing sum stays +inf.  Decided on the entries' bit patterns, not on the sum: this
-        // file's arithmetic is declared NaN-free, so no result of it is tested for being one.
+        // In this order (one accumulator, row after row) NumPy answers NaN exactly when the column holds a NaN or an
+        // infinity (inf - inf among the deviations): finite entries give no NaN here, an overflowing sum stays +inf.  (Not
+        // so in the pairwise order of std_loop_kernel and of tstd, see trimmed_result.)  Decided on the entries' bit
+        // patterns, not on the sum: this file's arithmetic is declared NaN-free, so no result of it is tested for being one.
         r = (top >= kNonFiniteTop) ? ROCCO_QUIET_NAN : sqrt(acc / (double)K);
     } else if constexpr (METHOD == kMad) {
         // K is padded to the even network size with -inf / +inf in equal numbers (one extra +inf for odd K), which
@@ -280,7 +262,25 @@ __global__ __launch_bounds__(256) void dispersion_kernel(const T *__restrict__ m
         const int n_lo = (KP - K) / 2;
         const bool has_nan = pad_and_park<KP, EXACT>(v, K, n_lo);
         select_middle<KP>(v);
-        const double med = (K & 1) ? v[KP / 2 - 1] : (v[KP / 2 - 1] + v[KP / 2]) / 2.0;
+        double med = (K & 1) ? v[KP / 2 - 1] : (v[KP / 2 - 1] + v[KP / 2]) / 2.0;
+        // (-inf + +inf) / 2 is NaN: the bit tests below must see the register, not a result "that is never NaN"
+        ROCCO_OPAQUE(med);
+        const bool med_is_nan = is_nan_bits(med), med_is_inf = is_inf_bits(med);  // asked separately, see is_finite_bits
+        // A median that is not finite (rare).  NaN: +inf and -inf in the middle.  Infinite: where an ENTRY is that same
+        // infinity its deviation is inf - inf and np.median answers NaN; where none is -- the two middle values are finite and
+        // their sum overflowed -- every deviation is +inf and so is the answer.  The entries are counted on their bit patterns,
+        // less the padding of that sign.
+        bool undefined = has_nan || med_is_nan;
+        if (med_is_inf) {
+            const long long med_bits = __double_as_longlong(med);
+            int equal = 0;
+#pragma unroll
+            for (int k = 0; k < KP; ++k) {
+                equal += (__double_as_longlong(v[k]) == med_bits) ? 1 : 0;
+            }
+            const int padded = EXACT ? 0 : ((med_bits < 0) ? n_lo : KP - K - n_lo);
+            undefined = undefined || equal > padded;
+        }
         // The network has permuted the registers but kept the multiset, which is all the second median needs.  The
         // padding must stay balanced: |+inf - med| is +inf again, and of the entries that come out as -inf (padding and
         // data alike: equal values) the first n_lo stay -inf while the others, data, become +inf.
@@ -298,8 +298,8 @@ __global__ __launch_bounds__(256) void dispersion_kernel(const T *__restrict__ m
         }
         select_middle<KP>(v);
         r = (K & 1) ? v[KP / 2 - 1] : (v[KP / 2 - 1] + v[KP / 2]) / 2.0;
-        // an infinite or NaN median leaves a NaN among the deviations (inf - inf), and np.median answers NaN then
-        r = (has_nan || !is_finite_bits(med)) ? ROCCO_QUIET_NAN : r;
+        // (around a median that is not finite the registers above held inf - inf: answered from the count, not from them)
+        r = undefined ? ROCCO_QUIET_NAN : (med_is_inf ? inf : r);
     } else {
         // all of the padding is +inf: position i of the sorted registers is position i of the sorted column
         [[maybe_unused]] double rows[(METHOD == kTstd && !kRereadForSums<KP, EXACT>) ? KP : 1];  // tstd: the column in row order
@@ -346,7 +346,9 @@ __global__ __launch_bounds__(256) void dispersion_kernel(const T *__restrict__ m
                              return kept(x) ? d * d : 0.0;
                          }) / cnt;
             var *= cnt / (cnt - 1.0);
-            r = trimmed_result(has_nan, cnt, lo, hi, args.g0 != 0.0 ? sqrt(var) : var);
+            bool mean_is_nan;
+            ROCCO_COMPUTED_IS_NAN(mean_is_nan, mean);
+            r = trimmed_result(has_nan, mean_is_nan, cnt, lo, hi, args.g0 != 0.0 ? sqrt(var) : var);
         }
     }
     out[j] = r;
@@ -400,12 +402,21 @@ __global__ __launch_bounds__(256) void dispersion_rank_kernel(const T *__restric
         const int want[2] = {(K - 1) / 2, K / 2};
         double mid[2];
         bool ok = order_statistics<2>(K, want, mid, entry);
-        const double med = (K & 1) ? mid[0] : (mid[0] + mid[1]) / 2.0;
-        ok = ok && is_finite_bits(med);
-        if (ok) {
+        double med = (K & 1) ? mid[0] : (mid[0] + mid[1]) / 2.0;
+        ROCCO_OPAQUE(med);  // (as in dispersion_kernel)
+        const bool med_is_nan = is_nan_bits(med), med_is_inf = is_inf_bits(med);  // asked separately, see is_finite_bits
+        if (ok && !med_is_nan && !med_is_inf) {
             order_statistics<2>(K, want, mid, [&](int k) -> double { return fabs(entry(k) - med); });
+            r = (K & 1) ? mid[0] : (mid[0] + mid[1]) / 2.0;
+        } else {
+            // a median that is not finite, as in dispersion_kernel: NaN where it is NaN or an entry is that same infinity,
+            // +inf where the sum of two finite middle values overflowed
+            bool undefined = !ok || med_is_nan;
+            for (int k = 0; k < K; ++k) {
+                undefined = undefined || (__double_as_longlong(entry(k)) == __double_as_longlong(med));
+            }
+            r = undefined ? ROCCO_QUIET_NAN : std::numeric_limits<double>::infinity();
         }
-        r = ok ? ((K & 1) ? mid[0] : (mid[0] + mid[1]) / 2.0) : ROCCO_QUIET_NAN;
     } else if constexpr (METHOD == kIqr) {
         const int want[4] = {args.index0, min(args.index0 + 1, K - 1), args.index1, min(args.index1 + 1, K - 1)};
         double s[4];
@@ -431,7 +442,9 @@ __global__ __launch_bounds__(256) void dispersion_rank_kernel(const T *__restric
                          return kept(x) ? d * d : 0.0;
                      }) / cnt;
         var *= cnt / (cnt - 1.0);
-        r = trimmed_result(!ok, cnt, lo, hi, args.g0 != 0.0 ? sqrt(var) : var);
+        bool mean_is_nan;
+        ROCCO_COMPUTED_IS_NAN(mean_is_nan, mean);
+        r = trimmed_result(!ok, mean_is_nan, cnt, lo, hi, args.g0 != 0.0 ? sqrt(var) : var);
     }
     out[j] = r;
 }

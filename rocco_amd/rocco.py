@@ -286,7 +286,7 @@ def _trim_ranks(K: int, tprop) -> Tuple[int, int]:
     return (int(np.quantile(ramp, tprop, method="nearest")), int(np.quantile(ramp, 1.0 - tprop, method="nearest")))
 
 
-_PAIRWISE_MAX_K = 1024  # kPairwiseMax of dispersion.hip: NumPy's pairwise order is written out to that many entries
+_PAIRWISE_MAX_K = 1024  # kPairwiseMax of csrc/pairwise_sum.h: the longest column its written-out pairwise order is used for
 
 
 def score_dispersion_chrom_device(matrix_t, out_t=None, method: str = "mad", rng=(25, 75), tprop: float = 0.05,
@@ -299,8 +299,9 @@ def score_dispersion_chrom_device(matrix_t, out_t=None, method: str = "mad", rng
     stats.tvar bit for bit).  SciPy's own root, ``var ** 0.5`` on a NumPy scalar, is the host libm's pow and differs from
     it in the last place for about 8 values in 10 000; :func:`score_dispersion_chrom` takes the root SciPy's way.
 
-    ``tstd``, and ``std`` of a single column, take K <= 1024 (ValueError above): NumPy's pairwise summation order is
-    written out to that length in the kernels.  ``mad``, ``iqr`` and ``std`` of a wider matrix take any K."""
+    ``tstd``, and ``std`` of a single column, take K <= 1024 (ValueError above): NumPy's pairwise summation order, with
+    its uneven halves, is written out in the kernels to four levels of splitting, which covers every such K.  ``mad``,
+    ``iqr`` and ``std`` of a wider matrix take any K."""
     import torch
 
     if matrix_t.ndim != 2:

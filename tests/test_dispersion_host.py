@@ -157,7 +157,7 @@ def tvar_restated(c, lo, hi):
     return var * (cnt / (cnt - 1.0))
 
 
-@pytest.mark.parametrize("K", (2, 3, 5, 7, 8, 9, 10, 15, 16, 17, 33, 64, 100, 101, 128, 129, 137, 255, 256, 257, 300))
+@pytest.mark.parametrize("K", (2, 3, 5, 7, 8, 9, 10, 15, 16, 17, 33, 64, 100, 101, 128, 129, 137, 255, 256, 257, 300, 968, 969, 1023, 1024))
 def test_restated_trimmed_variance_and_root_are_scipys_per_column(K):
     """Pins the SPECIFICATION, not a kernel: the arithmetic dispersion.hip's tstd is written after (dropped values as
     0.0, NumPy's pairwise order, kept / (kept - 1), the scalar `** 0.5`) is what this host's SciPy computes.  Of the
@@ -184,7 +184,7 @@ def test_restated_trimmed_variance_and_root_are_scipys_per_column(K):
             assert np.float64(got ** 0.5).tobytes() == np.float64(want_root).tobytes(), (K, tprop, j)
 
 
-@pytest.mark.parametrize("K", (2, 3, 7, 8, 9, 33, 100, 101, 128, 129, 137, 256, 257, 300))
+@pytest.mark.parametrize("K", (2, 3, 7, 8, 9, 33, 100, 101, 128, 129, 137, 256, 257, 300, 968, 969, 1023, 1024))
 def test_restated_std_orders_are_numpys(K):
     """Pins the SPECIFICATION, not a kernel, and touches no project code: the two summation orders dispersion.hip's std
     is written after (row after row for n > 1, pairwise for the single column) are this host's NumPy's.  If a NumPy
@@ -209,6 +209,61 @@ def test_restated_std_orders_are_numpys(K):
         d = c - mean
         got = np.sqrt(pairwise_sum(d * d) / K)
         assert np.float64(got).tobytes() == np.std(m[:, j:j + 1].copy(), axis=0).tobytes(), (K, j)
+
+
+# ---- the summation order the kernels compile, on the host, for every length ---------------------------------------------
+
+@pytest.fixture(scope="module")
+def pairwise_order_check(tmp_path_factory):
+    """tests/tools/pairwise_order_check.cpp: rocco_amd/csrc/pairwise_sum.h -- the functions dispersion.hip compiles -- in one
+    stand-alone host program, without FMA contraction as the kernels are built."""
+    import subprocess
+
+    program = str(tmp_path_factory.mktemp("pairwise") / "pairwise_order_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", os.path.join(HERE, "tools", "pairwise_order_check.cpp"),
+                    "-o", program], check=True, capture_output=True)
+    return program
+
+
+def pairwise_data(kind):
+    gen = np.random.default_rng(1024)
+    if kind == "normal":
+        return gen.standard_normal(1024)
+    if kind == "thirty binades":
+        return gen.standard_normal(1024) * np.exp2(gen.integers(-15, 16, size=1024).astype(float))
+    assert kind == "overflowing"  # +-1.5e308 in turn: from n = 16 on one accumulator reaches +inf and its neighbour -inf
+    return np.where(np.arange(1024) % 2 == 0, 1.5e308, -1.5e308)
+
+
+@pytest.mark.parametrize("kind", ("normal", "thirty binades", "overflowing"))
+def test_the_written_out_pairwise_order_is_np_sum_for_every_length(pairwise_order_check, tmp_path, kind):
+    """Every n in 1 ... 1024 (the K that tstd and the single-column std take) at the depth the kernels use: the bit pattern
+    of the sum against np.sum of the contiguous prefix; a NaN (the third data set: inf - inf between two accumulators) must
+    be a NaN.  The halves of NumPy's split are uneven, so a depth that serves n = 1024 need not serve every n below it:
+    written out to three levels the order is another for every n in 969 ... 1023 that is no multiple of 8 (a block of 129 to 135
+    terms is left unsplit), and the sums of each data set differ in the last place at some of those n and nowhere else."""
+    import subprocess
+
+    data = np.ascontiguousarray(pairwise_data(kind), dtype=np.float64)
+    path = tmp_path / "values.f64"
+    path.write_bytes(data.tobytes())
+    run = subprocess.run([pairwise_order_check, str(path)], check=True, capture_output=True, text=True, timeout=60)
+    lines = run.stdout.split("\n")[:-1]
+    assert len(lines) == 1024
+    wrong, nans = [], 0
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # overflow and inf - inf inside np.sum
+        for n, line in enumerate(lines, start=1):
+            n_text, bits = line.split()
+            assert int(n_text) == n
+            got = np.frombuffer(int(bits, 16).to_bytes(8, "little"), dtype="<f8")[0]
+            want = np.sum(data[:n].copy())
+            nans += bool(np.isnan(want))
+            if not (np.float64(got).tobytes() == np.float64(want).tobytes() or (np.isnan(got) and np.isnan(want))):
+                wrong.append(n)
+    assert wrong == []
+    # the third data set: NumPy's own answer is NaN from n = 16 on (two full rounds of the eight accumulators)
+    assert nans == (1024 - 15 if kind == "overflowing" else 0)
 
 
 # ---- the built kernels use no scratch memory --------------------------------------------------------------------------
